@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Headline benchmark: Mrays/s of the per-pass ray kernel at 1920x1080, 8 bounces (BASELINE.json).
 
-  python bench.py --gpus N --steps K --warmup W           (N > 1: launched by torch.distributed.run)
+  python bench.py --gpus N --steps K --warmup W [--full] [--dump-outputs DIR]     (N > 1: launched by torch.distributed.run)
 
 A "step" is one pass (one sample per pixel) of the hot path — primary-ray generation, BVH traversal,
 PBR/glass shading with NEE + environment, accumulation — over the whole frame; the scene, BVH, sample
@@ -10,8 +10,14 @@ sharded by 32x32-pixel tile across the ranks (strong scaling: the frame is fixed
 owned tiles are gathered on rank 0 over RCCL on a side stream, and the assembled final image is checked
 inside the timed region.  A small shard batches several passes into each kernel launch.
 
-Rank 0 prints ONE JSON line.  `roofline` describes the dominant kernel (k_trace: closest-hit + occlusion traversal).
-Its fraction is COUNTER-BASED and cannot exceed 1: before the parent process touches the GPU, the same command
+Rank 0 prints ONE JSON line.  A plain run does only what the headline needs: it sets up, warms up, times the K steps,
+writes the timed path's output with --dump-outputs DIR, and prints the line.  `--full` adds every other measurement and
+check: the counter passes, the cpu_baseline leg, the traversal-counter pass, parity of the timed frame against the CPU
+oracle, the display resolve and the live passes-to-converge leg (without them the line quotes the committed figures of
+profiles/, marked as such).
+
+`roofline` describes the dominant kernel (k_trace: closest-hit + occlusion traversal).
+Its fraction is COUNTER-BASED and cannot exceed 1: with --full, before the parent process touches the GPU, the same command
 is run under `rocprofv3 --pmc` in child processes (FETCH_SIZE, WRITE_SIZE and SQ_INSTS_VALU in separate passes, as
 MI355X_MICROARCH.md prescribes), which yields HBM-side bytes and VALU instructions per ray of THIS configuration and
 step count; multiplied by the rays of the timed region and divided by its wall time they give the achieved bandwidth
@@ -165,6 +171,25 @@ def parity_leg(sc, eng_frame, first_pass, n_passes, budget_s, world_label):
             "checker": "oracle/liboracle.so (parity build), OpenMP on the host cores", "seconds": time.perf_counter() - t0}
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, frame):
+    """--dump-outputs: what a caller of the timed path receives, the accumulated RGBA32F frame (sum of the passes' radiance in RGB,
+    the pass count in A), as out_dir/frame.npy.  A frame above 64 MB (c5's 3840x2160) is written as a fixed, seeded sample of its
+    pixels instead: frame_sample.npy (n x 4, float32) and frame_sample_pixels.npy (their row-major pixel indices, float64)."""
+    os.makedirs(out_dir, exist_ok=True)
+    frame = np.ascontiguousarray(frame, dtype=np.float32)
+    if frame.nbytes <= DUMP_LIMIT_BYTES:
+        np.save(os.path.join(out_dir, "frame.npy"), frame)
+        return
+    px = frame.reshape(-1, frame.shape[-1])
+    n = DUMP_LIMIT_BYTES // 2 // (px.shape[1] * 4)
+    idx = np.sort(np.random.default_rng(20240601).choice(px.shape[0], size=n, replace=False))
+    np.save(os.path.join(out_dir, "frame_sample.npy"), px[idx])
+    np.save(os.path.join(out_dir, "frame_sample_pixels.npy"), idx.astype(np.float64))
+
+
 def _short_kernel(name):
     n = name.split("(")[0].replace("void ", "").replace("hr::", "")
     return n.split("<")[0]
@@ -194,7 +219,7 @@ def pmc_legs(args, keep_dir=None):
     # busy fractions and bytes per ray then describe a warm device at the step count the line is quoted on, not a cold process's
     # first milliseconds (on a fresh box those run up to a fifth slower).
     child = [sys.executable if os.path.basename(sys.executable).startswith("python") else "python3", os.path.join(ROOT, "bench.py"),
-             "--pmc-child", "--workload", args.workload, "--steps", str(args.steps), "--warmup", str(args.warmup), "--cpu-seconds", "0", "--parity-seconds", "0", "--no-stats-pass",
+             "--pmc-child", "--full", "--workload", args.workload, "--steps", str(args.steps), "--warmup", str(args.warmup), "--cpu-seconds", "0", "--parity-seconds", "0", "--no-stats-pass",
              "--no-pmc", "--no-converge", "--estimator", args.estimator, "--width", str(args.width), "--height", str(args.height), "--depth", str(args.depth)]
     env = dict(os.environ, TMPDIR="/tmp")
     res = {"kernels": {}, "passes": {}, "dir": out_root if keep_dir else None}
@@ -379,7 +404,11 @@ def main():
     ap.add_argument("--workload", default="c3", choices=sorted(WORKLOADS))
     ap.add_argument("--width", type=int, default=0)
     ap.add_argument("--height", type=int, default=0)
-    ap.add_argument("--cpu-seconds", type=float, default=15.0, help="time budget of the cpu_baseline leg (0 = skip)")
+    ap.add_argument("--full", action="store_true", help="besides the headline, run every other measurement and check: rocprofv3 counter passes, "
+                    "cpu_baseline, the traversal-counter pass, parity against the CPU oracle, the display resolve and the live passes-to-converge leg")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR", help="after the timed steps, write the frame the timed path accumulated (RGBA32F) "
+                    "to DIR/frame.npy; above 64 MB a fixed, seeded sample of its pixels (DIR/frame_sample.npy and DIR/frame_sample_pixels.npy)")
+    ap.add_argument("--cpu-seconds", type=float, default=None, help="time budget of the cpu_baseline leg (default 15 with --full, else 0 = skip)")
     ap.add_argument("--shard-of", type=int, default=0, help="tuning aid, single process: render only rank 0's tiles of a W-way "
                     "sharded frame (no collective); the JSON line is marked emulated and is not a benchmark result")
     ap.add_argument("--converge", action="store_true", help="passes-to-converge p50 (BASELINE metric 2): no time budget for the leg (all --converge-runs "
@@ -398,17 +427,24 @@ def main():
                     "launch rocprofv3 sees then belongs to the timed region)")
     ap.add_argument("--no-stats-pass", action="store_true", help="skip the extra counted pass that measures V and T")
     ap.add_argument("--parity-seconds", type=float, default=None, help="host-time budget of the parity leg: the timed region's frame against the "
-                    "CPU oracle's render of the same passes (default 25; 0 = skip, which is also --quick's default: the line then carries no parity object)")
+                    "CPU oracle's render of the same passes (default 25 with --full; 0 = skip, which is the default without --full and --quick's: "
+                    "the line then carries no parity object)")
     ap.add_argument("--no-pmc", action="store_true", help="skip the rocprofv3 counter passes (the roofline then quotes the committed per-ray "
                     "figures of profiles/traffic.json, scaled by this run's rays, and says so)")
     ap.add_argument("--quick", action="store_true", help="tuning runs: only the timed region (= --cpu-seconds 0 --no-stats-pass --no-pmc --no-converge)")
     ap.add_argument("--pmc-child", action="store_true", help=argparse.SUPPRESS)
     ap.add_argument("--pmc-keep", default="", help="keep the rocprofv3 output of the counter passes in this directory")
     args = ap.parse_args()
+    if not args.full:
+        # a plain run: the headline only (a leg asked for by name still runs: a --cpu-seconds / --parity-seconds budget, --converge)
+        args.no_stats_pass, args.no_pmc = True, True
+        args.no_converge = args.no_converge or not args.converge
+    if args.cpu_seconds is None:
+        args.cpu_seconds = 15.0 if args.full else 0.0
     if args.quick:
         args.cpu_seconds, args.no_stats_pass, args.no_pmc, args.no_converge = 0.0, True, True, True
     if args.parity_seconds is None:
-        args.parity_seconds = 0.0 if args.quick else 25.0
+        args.parity_seconds = 25.0 if args.full and not args.quick else 0.0
 
     if args.gpus < 1:
         raise SystemExit("--gpus must be >= 1")
@@ -582,6 +618,8 @@ def main():
         import hashlib
         frame_host = full.cpu().numpy()
         frame_sha256 = None if emulated else hashlib.sha256(frame_host.tobytes()).hexdigest()
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, frame_host)
         # SURVEY 8d metric 1 asks for min / median per pass beside the mean.  The renderer is a pipeline: a macro step advances every
         # in-flight pass by one stage, and a step in which the pipeline is FULL (stages x batch passes in flight) does one pass's worth
         # of work per pass it injects.  libhrcore logs every step's k_trace launch by the device clock (hr_get_step_log): the period
@@ -802,7 +840,7 @@ def main():
 
         # the display resolve, outside the timed region: device-side displayGL.frag -> RGBA8
         disp_ms = None
-        if not emulated:
+        if args.full and not emulated:
             shown = torch.empty((sc.height, sc.width), dtype=torch.int32, device=dev)
             P = ffi.display_params(tonemapping_enabled=True)
             eng.display_device(shown.data_ptr(), P, ffi.HR_DISPLAY_RGBA8)

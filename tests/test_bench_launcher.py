@@ -51,7 +51,7 @@ def test_plain_start_with_two_gpus_launches_ranks_and_fails_loudly_without_devic
 
 @pytest.mark.gpu
 def test_two_rank_rehearsal_on_one_device():
-    args = ["--quick", "--parity-seconds", "30", "--steps", "70", "--warmup", "1", "--workload", "c2", "--width", "512", "--height", "288"]  # (two exchanges on the way + the final one)
+    args = ["--full", "--quick", "--parity-seconds", "30", "--steps", "70", "--warmup", "1", "--workload", "c2", "--width", "512", "--height", "288"]  # (two exchanges on the way + the final one)
     r = _run(["--gpus", "2"] + args, env={"HR_BENCH_ONE_DEVICE": "1"}, timeout=900)
     assert r.returncode == 0, r.stderr.decode(errors="replace")[-3000:]
     lines = _json_lines(r.stdout)
@@ -82,7 +82,7 @@ def test_rccl_exchange_path_with_one_rank():
     # The real collective library on the real device, as far as one GPU allows: HR_BENCH_FORCE_EXCHANGE=1 runs the N > 1 code path — an
     # "nccl" (= RCCL) process group, hr_frame_pack_owned -> dist.gather on a side stream after every resolved batch, hr_frame_unpack,
     # the final assembly — in a single rank.  Same passes => the same digest as the plain run, and the oracle's frame.
-    args = ["--quick", "--parity-seconds", "30", "--steps", "70", "--warmup", "1", "--workload", "c2", "--width", "512", "--height", "288"]
+    args = ["--full", "--quick", "--parity-seconds", "30", "--steps", "70", "--warmup", "1", "--workload", "c2", "--width", "512", "--height", "288"]
     r = _run(["--gpus", "1"] + args, env={"HR_BENCH_FORCE_EXCHANGE": "1"}, timeout=900)
     assert r.returncode == 0, r.stderr.decode(errors="replace")[-3000:]
     d = json.loads(_json_lines(r.stdout)[0])
