@@ -164,6 +164,15 @@ ABI_SYMBOLS = [
     "frame_pass_batch", "interactive_blocks_set", "scene_cache",
 ]
 
+# every symbol include/hrcore_group.h declares (context groups; a library without them still loads, create_group then fails)
+HR_GROUP_API_VERSION = 1
+HR_GROUP_MAX_MEMBERS = 16
+GROUP_SYMBOLS = ["group_api_version", "ctx_create_group", "group_get_info", "group_member_stats"]
+
+
+class GroupInfo(C.Structure):
+    _fields_ = [("n_members", C.c_int32), ("device_ids", C.c_int32 * HR_GROUP_MAX_MEMBERS), ("owned_pixels", C.c_uint64 * HR_GROUP_MAX_MEMBERS)]
+
 
 class EngineError(RuntimeError):
     pass
@@ -469,3 +478,43 @@ class Engine:
         self._call("debug_trace", C.c_int32(n), _ptr(o), _ptr(d), _ptr(tm), _ptr(sk, i32p), C.c_int32(int(any_hit)),
                    out.ctypes.data_as(C.POINTER(Hit)))
         return out
+
+
+class GroupEngine(Engine):
+    """An Engine whose handle is a context group (include/hrcore_group.h): member i renders the tiles t % n == i on
+    device_ids[i]; every Engine call works on it, plus the group's own two."""
+
+    def __init__(self, lib, device_ids=None, tile_size=32, stream=None, flags=0, memory_budget=0):
+        self._lib = lib
+        self._p = "hr_"
+        self._ctx = C.c_void_p()
+        self.width = self.height = 0
+        missing = [s for s in GROUP_SYMBOLS if not hasattr(lib, "hr_" + s)]
+        if missing:
+            raise EngineError(f"the loaded libhrcore has no context groups (lacks {missing}): rebuild it")
+        for fn, want in (("abi_version", HR_ABI_VERSION), ("group_api_version", HR_GROUP_API_VERSION)):
+            f = getattr(lib, "hr_" + fn)
+            f.restype = C.c_uint32
+            if f() != want:
+                raise EngineError(f"hr_{fn}() = {f()}, this binding was written against {want}: rebuild the library")
+        ids = None if device_ids is None else (C.c_int32 * max(1, len(device_ids)))(*device_ids)
+        n = 0 if device_ids is None else len(device_ids)
+        desc = CtxDesc(0, 0, 1, tile_size, stream, flags, int(memory_budget))
+        rc = self._fn("ctx_create_group")(C.byref(desc), ids, C.c_int32(n), C.byref(self._ctx))
+        if rc != HR_OK:
+            self._ctx = C.c_void_p()
+            raise EngineError(f"hr_ctx_create_group({list(device_ids) if device_ids is not None else 'every device'}) failed with status {rc} "
+                              "(no usable HIP device, a bad device id or more than 16 members?)")
+
+    def group_info(self):
+        """{"n_members", "device_ids", "owned_pixels"} of the group."""
+        g = GroupInfo()
+        self._call("group_get_info", C.byref(g))
+        n = g.n_members
+        return {"n_members": n, "device_ids": list(g.device_ids[:n]), "owned_pixels": list(g.owned_pixels[:n])}
+
+    def member_stats(self, member, kernel_times=False):
+        """PassStats of one member (completes its passes first); with kernel_times, (stats, KernelTimes)."""
+        s, t = PassStats(), KernelTimes()
+        self._call("group_member_stats", C.c_int32(member), C.byref(s), C.byref(t) if kernel_times else None)
+        return (s, t) if kernel_times else s

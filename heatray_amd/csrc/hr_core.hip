@@ -8,7 +8,8 @@
 //   hr_core.hip       this file: context life cycle, frame, display, read-backs, statistics
 //   hr_scene.inl      geometry ingest, commit (build / refit / tree cache), textures, materials, lights, sample tables
 //   hr_pipeline.inl   ray memory, the macro step, batching and the packet selector, hr_render_pass, the step log
-// (one translation unit: the two .inl files are sections of this one, included below)
+//   hr_group.inl      context groups (include/hrcore_group.h): member threads, the assembly of the members' tiles
+// (one translation unit: the .inl files are sections of this one, included below)
 #include "hr_ctx.h"
 
 static const int kTableRing = 4;
@@ -83,19 +84,23 @@ static int ensureLagged(hr_ctx *c, hr_ctx::Lagged &L, size_t bytes, bool withDev
 
 // slot to fill now; afterwards `finishLagged` picks what to hand out
 static int beginLagged(hr_ctx::Lagged &L) { return L.turn++ % 3; }
-static int finishLagged(hr_ctx *c, hr_ctx::Lagged &L, int k, int32_t format, const void **out, uint32_t *passes)
+// (`passesNow`: complete passes in the snapshot just enqueued; `idle`: no pass is pending or in flight — a context group's are its members')
+static int finishLaggedAt(hr_ctx *c, hr_ctx::Lagged &L, int k, int32_t format, const void **out, uint32_t *passes, uint32_t passesNow, bool idle)
 {
     HIP_TRY(c, hipEventRecord(L.ev[k], c->stream));
     L.pending[k] = true, L.epoch[k] = c->snapshotEpoch, L.format[k] = format;
-    L.passes[k] = (uint32_t)(c->nextResolveOrder - c->resolvedAtClear);
+    L.passes[k] = passesNow;
     const int prev = (k + 2) % 3;
     // nothing in flight (e.g. right after a complete readback): the current snapshot is final, hand it out itself
-    const bool idle = c->pendingInject.empty() && occupiedSlots(c) == 0;
     const int use = (!idle && L.pending[prev] && L.epoch[prev] == c->snapshotEpoch && L.format[prev] == format && L.passes[prev] > 0) ? prev : k;
     HIP_TRY(c, hipEventSynchronize(L.ev[use]));
     *out = L.pinned[use];
     if (passes) *passes = L.passes[use];
     return HR_OK;
+}
+static int finishLagged(hr_ctx *c, hr_ctx::Lagged &L, int k, int32_t format, const void **out, uint32_t *passes)
+{
+    return finishLaggedAt(c, L, k, format, out, passes, (uint32_t)(c->nextResolveOrder - c->resolvedAtClear), c->pendingInject.empty() && occupiedSlots(c) == 0);
 }
 
 static void freeQueues(hr_ctx *c)
@@ -154,6 +159,27 @@ template <class T> static int ensureCap(hr_ctx *c, T **p, size_t *cap, size_t ne
     *cap = need;
     return HR_OK;
 }
+
+// Context groups (hr_group.inl, included at the end of this file): every entry point hands a group handle to one of these.
+static int groupAll(hr_ctx *c, const std::function<int(hr_ctx *, int)> &fn);
+static int groupOne(hr_ctx *c, int i, const std::function<int(hr_ctx *)> &fn);
+static int groupAllId(hr_ctx *c, int32_t *out, const char *what, const std::function<int(hr_ctx *, int, int32_t *)> &fn);
+static int groupUnsupported(hr_ctx *c, const char *what);
+static int groupDestroy(hr_ctx *c);
+static int groupSetStream(hr_ctx *c, void *stream);
+static int groupResize(hr_ctx *c, int32_t w, int32_t h);
+static int groupReadback(hr_ctx *c, const float **rgba, int32_t *w, int32_t *h);
+static int groupReadbackProgressive(hr_ctx *c, const float **rgba, int32_t *w, int32_t *h, uint32_t *passes);
+static int groupDisplay(hr_ctx *c, const hr_display_params *params, int32_t format, void *out, uint32_t *shown);
+static int groupDisplayReadback(hr_ctx *c, const hr_display_params *params, int32_t format, const void **pixels, int32_t *width, int32_t *height, uint32_t *shown);
+static int groupDevicePtr(hr_ctx *c, void **deviceRgba);
+static int groupPassesResolved(hr_ctx *c, uint64_t *passes);
+static int groupSync(hr_ctx *c, bool wait);
+static int groupClear(hr_ctx *c);
+static int groupRenderPass(hr_ctx *c, const hr_pass_params *pp);
+static int groupStats(hr_ctx *c, hr_pass_stats *out);
+static int groupCommit(hr_ctx *c);
+static int groupMultiscatter(hr_ctx *c, float *out, hr_tex_id *outTex);
 
 extern "C" {
 
@@ -260,6 +286,7 @@ int hr_ctx_create(const hr_ctx_desc *desc, hr_ctx **out)
 int hr_ctx_destroy(hr_ctx *c)
 {
     if (!c) return HR_OK;
+    if (c->grp) return groupDestroy(c);
     hipSetDevice(c->device);
     if (getenv("HR_DEBUG_PIPE"))
         fprintf(stderr, "hr_ctx %p: ray-memory growths %llu (last sizes summed %.1f MiB); queue-length waits %llu, of which %llu had to spin, %.2f ms in total\n", (void *)c,
@@ -326,6 +353,7 @@ const char *hr_last_error(const hr_ctx *c) { return c ? c->err.c_str() : "null c
 int hr_ctx_set_stream(hr_ctx *c, void *stream)
 {
     ENTER(c);
+    if (c->grp) return groupSetStream(c, stream);
     QUIESCE(c);
     c->stream = (hipStream_t)stream;
     return HR_OK;
@@ -344,6 +372,7 @@ static FrameDev frameOf(const hr_ctx *c, int32_t rank, int32_t world)
 int hr_frame_packed_slots(hr_ctx *c, int32_t rank, int32_t world, uint64_t *n_slots)
 {
     ENTER(c);
+    if (c->grp) return groupUnsupported(c, "hr_frame_packed_slots");
     if (!n_slots || world <= 0 || rank < 0 || rank >= world) FAIL(c, HR_ERR_INVALID, "bad rank / world");
     if (c->W <= 0) FAIL(c, HR_ERR_INVALID, "no frame");
     *n_slots = (uint64_t)frameOf(c, rank, world).nOwnedTiles * (uint64_t)(c->tile * c->tile);
@@ -353,6 +382,7 @@ int hr_frame_packed_slots(hr_ctx *c, int32_t rank, int32_t world, uint64_t *n_sl
 int hr_frame_pack_owned(hr_ctx *c, void *device_out, void *stream)
 {
     ENTER(c);
+    if (c->grp) return groupUnsupported(c, "hr_frame_pack_owned");
     if (!device_out) FAIL(c, HR_ERR_INVALID, "null output");
     if (c->W <= 0) FAIL(c, HR_ERR_INVALID, "no frame");
     FrameDev fr = c->frame;
@@ -375,6 +405,7 @@ int hr_frame_pack_owned(hr_ctx *c, void *device_out, void *stream)
 int hr_frame_unpack(hr_ctx *c, int32_t src_rank, int32_t world, const void *device_packed, void *device_full_frame, void *stream)
 {
     ENTER(c);
+    if (c->grp) return groupUnsupported(c, "hr_frame_unpack");
     if (!device_packed || !device_full_frame) FAIL(c, HR_ERR_INVALID, "null argument");
     if (world <= 0 || src_rank < 0 || src_rank >= world) FAIL(c, HR_ERR_INVALID, "bad rank / world");
     if (c->W <= 0) FAIL(c, HR_ERR_INVALID, "no frame");
@@ -389,6 +420,7 @@ static size_t displayPixelBytes(int32_t format) { return format == HR_DISPLAY_RG
 int hr_display(hr_ctx *c, const hr_display_params *params, int32_t format, void *device_out, uint32_t *passes_shown)
 {
     ENTER(c);
+    if (c->grp) return groupDisplay(c, params, format, device_out, passes_shown);
     if (!params || !device_out) FAIL(c, HR_ERR_INVALID, "null argument");
     if (c->W <= 0) FAIL(c, HR_ERR_INVALID, "no frame");
     const bool progressive = (format & HR_DISPLAY_PROGRESSIVE) != 0;
@@ -409,6 +441,7 @@ int hr_display(hr_ctx *c, const hr_display_params *params, int32_t format, void 
 int hr_frame_passes_resolved(hr_ctx *c, uint64_t *passes)
 {
     ENTER(c);
+    if (c->grp) return groupPassesResolved(c, passes);
     if (!passes) FAIL(c, HR_ERR_INVALID, "null output");
     *passes = c->nextResolveOrder - c->resolvedAtClear;
     return HR_OK;
@@ -417,6 +450,7 @@ int hr_frame_passes_resolved(hr_ctx *c, uint64_t *passes)
 int hr_display_readback(hr_ctx *c, const hr_display_params *params, int32_t format, const void **pixels, int32_t *width, int32_t *height, uint32_t *passes_shown)
 {
     ENTER(c);
+    if (c->grp) return groupDisplayReadback(c, params, format, pixels, width, height, passes_shown);
     if (!pixels) FAIL(c, HR_ERR_INVALID, "null output");
     if (c->W <= 0) FAIL(c, HR_ERR_INVALID, "no frame");
     {
@@ -465,6 +499,7 @@ int hr_display_readback(hr_ctx *c, const hr_display_params *params, int32_t form
 int hr_synchronize(hr_ctx *c)
 {
     ENTER(c);
+    if (c->grp) return groupSync(c, true);
     QUIESCE(c);
     return overflowCheck(c);
 }
@@ -473,6 +508,7 @@ int hr_synchronize(hr_ctx *c)
 int hr_frame_resize(hr_ctx *c, int32_t w, int32_t h)
 {
     ENTER(c);
+    if (c->grp) return groupResize(c, w, h);
     if (w <= 0 || h <= 0 || (long long)w * h > (1ll << 28)) FAIL(c, HR_ERR_INVALID, "bad frame size");
     QUIESCE(c);
     c->W = w, c->H = h;
@@ -529,6 +565,7 @@ int hr_frame_resize(hr_ctx *c, int32_t w, int32_t h)
 int hr_frame_bind_external(hr_ctx *c, void *deviceRgba)
 {
     ENTER(c);
+    if (c->grp) return groupUnsupported(c, "hr_frame_bind_external");
     if (c->W <= 0) FAIL(c, HR_ERR_INVALID, "no frame");
     QUIESCE(c);
     c->fbExternal = (float *)deviceRgba;
@@ -539,6 +576,7 @@ int hr_frame_bind_external(hr_ctx *c, void *deviceRgba)
 int hr_frame_device_ptr(hr_ctx *c, void **deviceRgba)
 {
     ENTER(c);
+    if (c->grp) return groupDevicePtr(c, deviceRgba);
     if (c->W <= 0 || !deviceRgba) FAIL(c, HR_ERR_INVALID, "no frame");
     *deviceRgba = c->fb();
     return HR_OK;
@@ -551,6 +589,7 @@ int hr_frame_device_ptr(hr_ctx *c, void **deviceRgba)
 int hr_readback(hr_ctx *c, const float **rgba, int32_t *w, int32_t *h)
 {
     ENTER(c);
+    if (c->grp) return groupReadback(c, rgba, w, h);
     if (c->W <= 0 || !rgba) FAIL(c, HR_ERR_INVALID, "no frame");
     const size_t bytes = (size_t)c->W * c->H * 4 * sizeof(float);
     {
@@ -572,6 +611,7 @@ int hr_readback(hr_ctx *c, const float **rgba, int32_t *w, int32_t *h)
 int hr_readback_progressive(hr_ctx *c, const float **rgba, int32_t *w, int32_t *h, uint32_t *passes)
 {
     ENTER(c);
+    if (c->grp) return groupReadbackProgressive(c, rgba, w, h, passes);
     if (c->W <= 0 || !rgba) FAIL(c, HR_ERR_INVALID, "no frame");
     const size_t bytes = (size_t)c->W * c->H * 4 * sizeof(float);
     int rc = completeForSlowCaller(c);
@@ -594,6 +634,7 @@ int hr_readback_progressive(hr_ctx *c, const float **rgba, int32_t *w, int32_t *
 int hr_debug_trace(hr_ctx *c, int32_t n, const float *o, const float *d, const float *tmax, const int32_t *skip, int32_t anyHit, hr_hit *out)
 {
     ENTER(c);
+    if (c->grp) return groupOne(c, 0, [&](hr_ctx *m) { return hr_debug_trace(m, n, o, d, tmax, skip, anyHit, out); });
     if (!c->committed) FAIL(c, HR_ERR_INVALID, "scene not committed");
     if (n <= 0 || !o || !d || !out) FAIL(c, HR_ERR_INVALID, "bad arguments");
     int rc = uploadScene(c);
@@ -623,3 +664,6 @@ int hr_debug_trace(hr_ctx *c, int32_t n, const float *o, const float *d, const f
 }
 
 } // extern "C"
+
+// ------------------------------------------------------------------------------------------ context groups
+#include "hr_group.inl"

@@ -2,6 +2,7 @@
 #pragma once
 
 #include "hr_types.h"
+#include "../../include/hrcore_group.h"
 
 #include <cstddef>
 
@@ -138,6 +139,16 @@ void launchFetchTable(hipStream_t stream, const void *hostMapped, void *dst, siz
 void launchRaygen(const LaunchCfg &cfg, const SceneDev *S, const StepTable *tbl, const SegList &segs, const FrameDev &fr, Stats *stats);
 void launchResolve(const LaunchCfg &cfg, const FrameDev &fr, const PassBufList &bufs);
 void launchPackOwned(const LaunchCfg &cfg, const FrameDev &fr, const float *frame, float *packed, int unpack, float *full);
+// Context groups (hr_group.inl): the packed pixels of every member (rank m of world n, ownedPixel order) -> their places in the full
+// frame, ONE launch for all members.  Member m's slots are padded to whole workgroups: its workgroups are
+// [blockStart[m], blockStart[m + 1]) (blockStart[n] = the grid), so a workgroup belongs to one member.
+struct GatherList {
+    int32_t n;
+    uint32_t blockStart[HR_GROUP_MAX_MEMBERS + 1];
+    const float *packed[HR_GROUP_MAX_MEMBERS]; // device memory on the frame's device (null for a member that owns no tiles)
+};
+int gatherBlock(); // workgroup size of k_gather_members (slots per padded workgroup)
+void launchGatherMembers(const LaunchCfg &cfg, const FrameDev &fr, const GatherList &list, float *full);
 void launchDisplay(const LaunchCfg &cfg, const FrameDev &fr, const hr_display_params &P, int format, void *out);
 void launchTrace(const LaunchCfg &cfg, const SceneDev *S, const int *leafKeys, const Node32 *nodes32, const Tri *tris, StepTable *tbl, Stats *stats);
 void launchRaygenPackets(const LaunchCfg &cfg, const SceneDev *S, const Node4 *nodes, const Tri *tris, const StepTable *tbl, const SegList &segs,

@@ -3,6 +3,7 @@
 int hr_clear(hr_ctx *c)
 {
     ENTER(c);
+    if (c->grp) return groupClear(c);
     if (c->W <= 0) FAIL(c, HR_ERR_INVALID, "no frame");
     int rc = drainPipeline(c);
     if (rc) return rc;
@@ -732,6 +733,7 @@ static int drainPipeline(hr_ctx *c)
 int hr_render_pass(hr_ctx *c, const hr_pass_params *pp)
 {
     ENTER(c);
+    if (c->grp) return groupRenderPass(c, pp);
     if (!pp) FAIL(c, HR_ERR_INVALID, "null params");
     if (c->W <= 0) FAIL(c, HR_ERR_INVALID, "no frame");
     if (!c->committed) FAIL(c, HR_ERR_INVALID, "scene not committed");
@@ -804,6 +806,7 @@ int hr_render_pass(hr_ctx *c, const hr_pass_params *pp)
 int hr_frame_pass_batch(hr_ctx *c, int32_t max_ray_depth, int32_t *batch)
 {
     ENTER(c);
+    if (c->grp) return groupOne(c, 0, [&](hr_ctx *m) { return hr_frame_pass_batch(m, max_ray_depth, batch); });
     if (!batch || max_ray_depth < 0) FAIL(c, HR_ERR_INVALID, "bad arguments");
     if (c->W <= 0) FAIL(c, HR_ERR_INVALID, "no frame");
     hr_pass_params pp{};
@@ -815,6 +818,7 @@ int hr_frame_pass_batch(hr_ctx *c, int32_t max_ray_depth, int32_t *batch)
 int hr_flush(hr_ctx *c)
 {
     ENTER(c);
+    if (c->grp) return groupSync(c, false);
     const int rc = drainPipeline(c);
     return rc ? rc : overflowCheck(c); // (no wait here: what the kernels have reported so far)
 }
@@ -822,6 +826,7 @@ int hr_flush(hr_ctx *c)
 int hr_get_stats(hr_ctx *c, hr_pass_stats *out)
 {
     ENTER(c);
+    if (c->grp) return groupStats(c, out);
     if (!out) FAIL(c, HR_ERR_INVALID, "null output");
     {
         int rc = drainPipeline(c);
@@ -850,6 +855,7 @@ int hr_get_stats(hr_ctx *c, hr_pass_stats *out)
 int hr_get_kernel_times(hr_ctx *c, hr_kernel_times *out)
 {
     ENTER(c);
+    if (c->grp) return groupUnsupported(c, "hr_get_kernel_times");
     if (!out) FAIL(c, HR_ERR_INVALID, "null output");
     {
         int rc = drainPipeline(c);
@@ -872,6 +878,7 @@ int hr_get_kernel_times(hr_ctx *c, hr_kernel_times *out)
 int hr_get_step_log(hr_ctx *c, hr_step_record *out, int32_t capacity, int32_t *n_records)
 {
     ENTER(c);
+    if (c->grp) return groupUnsupported(c, "hr_get_step_log");
     if (!out || !n_records || capacity <= 0) FAIL(c, HR_ERR_INVALID, "bad arguments");
     {
         int rc = drainPipeline(c);

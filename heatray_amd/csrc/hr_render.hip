@@ -277,6 +277,37 @@ void launchPackOwned(const LaunchCfg &cfg, const FrameDev &fr, const float *fram
                        reinterpret_cast<float4 *>(packed), unpack, reinterpret_cast<float4 *>(full));
 }
 
+// Context groups: every member's packed tiles -> the full frame on the group's first device, in one launch.  The member of a workgroup
+// is found by comparing its index with the members' first workgroups — unrolled over constant indices, so the list stays in the
+// kernel-argument segment (scalar loads) instead of being copied to scratch for a dynamic index.  A wave reads 64 consecutive
+// 16-byte slots and writes one 8x8-pixel block (8 rows of 128 contiguous bytes), as k_pack_owned does the other way round.
+// Copies only: the assembled frame is the members' bits.
+__global__ __launch_bounds__(kBlock) void k_gather_members(FrameDev fr, GatherList list, float4 *__restrict__ full)
+{
+    const uint32_t b = blockIdx.x;
+    int m = 0;
+    uint32_t first = 0;
+    const float *src = list.packed[0];
+#pragma unroll
+    for (int k = 1; k < HR_GROUP_MAX_MEMBERS; ++k)
+        if (k < list.n && b >= list.blockStart[k]) m = k, first = list.blockStart[k], src = list.packed[k];
+    const int nTiles = fr.tilesX * fr.tilesY;
+    fr.rank = m, fr.world = list.n;
+    fr.nOwnedTiles = nTiles > m ? (nTiles - m + list.n - 1) / list.n : 0;
+    const uint32_t gid = (b - first) * kBlock + threadIdx.x;
+    int x = 0, y = 0;
+    if (!ownedPixel(fr, gid, x, y)) return; // past the member's slots (padding) or outside a cropped edge tile
+    full[(uint32_t)(y * fr.W + x)] = reinterpret_cast<const float4 *>(src)[gid];
+}
+
+int gatherBlock() { return kBlock; }
+
+void launchGatherMembers(const LaunchCfg &cfg, const FrameDev &fr, const GatherList &list, float *full)
+{
+    if (list.n <= 0 || list.n > HR_GROUP_MAX_MEMBERS || list.blockStart[list.n] == 0u) return;
+    hipLaunchKernelGGL(k_gather_members, dim3(list.blockStart[list.n]), dim3(kBlock), 0, cfg.stream, fr, list, reinterpret_cast<float4 *>(full));
+}
+
 // ------------------------------------------------------------------------------------------ display
 // displayGL.frag on the accumulation buffer: one thread per pixel, row-major (coalesced 16-byte reads, 4- or 16-byte writes)
 __global__ __launch_bounds__(kBlock) void k_display(FrameDev fr, hr_display_params P, int format, void *__restrict__ out)

@@ -26,6 +26,7 @@ static int stagedUpload(hr_ctx *c, char *dst, const char *src, size_t bytes)
 int hr_geom_add(hr_ctx *c, const hr_mesh_desc *d, hr_geom_id *out)
 {
     ENTER(c);
+    if (c->grp) return groupAllId(c, out, "hr_geom_add", [&](hr_ctx *m, int, int32_t *id) { return hr_geom_add(m, d, id); });
     if (!d || !d->positions || !d->normals || !d->indices || d->n_vertices <= 0 || d->n_indices < 0)
         FAIL(c, HR_ERR_INVALID, "mesh needs positions, normals, indices");
     if (d->mode != HR_TRIANGLES && d->mode != HR_TRIANGLE_STRIP) FAIL(c, HR_ERR_INVALID, "unsupported draw mode");
@@ -140,6 +141,7 @@ int hr_geom_add(hr_ctx *c, const hr_mesh_desc *d, hr_geom_id *out)
 int hr_geom_remove(hr_ctx *c, hr_geom_id id)
 {
     ENTER(c);
+    if (c->grp) return groupAll(c, [&](hr_ctx *m, int) { return hr_geom_remove(m, id); });
     if (id < 0 || id >= (int)c->geoms.size() || !c->geoms[id].alive) FAIL(c, HR_ERR_INVALID, "bad geom id");
     for (int k = 0; k < 2; ++k) // an upload of this mesh may still be in flight (nothing to wait for when the staging ring is idle)
         if (c->stageBusy[k] && hipEventQuery(c->stageEv[k]) != hipSuccess) HIP_TRY(c, hipEventSynchronize(c->stageEv[k]));
@@ -152,6 +154,7 @@ int hr_geom_remove(hr_ctx *c, hr_geom_id id)
 int hr_geom_set_transform(hr_ctx *c, hr_geom_id id, const float m[16])
 {
     ENTER(c);
+    if (c->grp) return groupAll(c, [&](hr_ctx *mc, int) { return hr_geom_set_transform(mc, id, m); });
     if (id < 0 || id >= (int)c->geoms.size() || !c->geoms[id].alive || !m) FAIL(c, HR_ERR_INVALID, "bad geom id");
     for (int k = 0; k < 16; ++k)
         if (!(std::fabs(m[k]) <= 3.0e37f)) FAIL(c, HR_ERR_INVALID, "world_from_entity must be finite");
@@ -163,6 +166,7 @@ int hr_geom_set_transform(hr_ctx *c, hr_geom_id id, const float m[16])
 int hr_scene_clear(hr_ctx *c)
 {
     ENTER(c);
+    if (c->grp) return groupAll(c, [](hr_ctx *m, int) { return hr_scene_clear(m); });
     for (int k = 0; k < 2; ++k)
         if (c->stageBusy[k] && hipEventQuery(c->stageEv[k]) != hipSuccess) HIP_TRY(c, hipEventSynchronize(c->stageEv[k]));
     c->meshReleaseAll();
@@ -353,6 +357,7 @@ struct CommitScratch {
 int hr_scene_commit(hr_ctx *c)
 {
     ENTER(c);
+    if (c->grp) return groupCommit(c);
     QUIESCE(c);
     // until this call succeeds there is no scene to render: a failed re-commit must not leave `committed` set over stale arrays
     c->committed = false, c->sceneDirty = true;
@@ -489,6 +494,7 @@ int hr_scene_commit(hr_ctx *c)
 int hr_scene_cache(hr_ctx *c, const char *path)
 {
     ENTER(c);
+    if (c->grp) return groupAll(c, [&](hr_ctx *m, int) { return hr_scene_cache(m, path); });
     c->cachePath = path ? path : "";
     return HR_OK;
 }
@@ -496,6 +502,7 @@ int hr_scene_cache(hr_ctx *c, const char *path)
 int hr_scene_get_info(hr_ctx *c, hr_scene_info *out)
 {
     ENTER(c);
+    if (c->grp) return groupOne(c, 0, [&](hr_ctx *m) { return hr_scene_get_info(m, out); });
     if (!c->committed || !out) FAIL(c, HR_ERR_INVALID, "scene not committed");
     *out = c->info;
     return HR_OK;
@@ -505,6 +512,7 @@ int hr_scene_get_info(hr_ctx *c, hr_scene_info *out)
 int hr_texture_create(hr_ctx *c, const hr_texture_desc *d, const void *pixels, hr_tex_id *out)
 {
     ENTER(c);
+    if (c->grp) return groupAllId(c, out, "hr_texture_create", [&](hr_ctx *m, int, int32_t *id) { return hr_texture_create(m, d, pixels, id); });
     if (!d || !pixels || d->width <= 0 || d->height <= 0 || (d->channels != 1 && d->channels != 3 && d->channels != 4))
         FAIL(c, HR_ERR_INVALID, "bad texture descriptor");
     const size_t n = (size_t)d->width * d->height * d->channels;
@@ -526,6 +534,7 @@ int hr_texture_create(hr_ctx *c, const hr_texture_desc *d, const void *pixels, h
 int hr_texture_destroy(hr_ctx *c, hr_tex_id id)
 {
     ENTER(c);
+    if (c->grp) return groupAll(c, [&](hr_ctx *m, int) { return hr_texture_destroy(m, id); });
     if (id < 0 || id >= (int)c->textures.size() || !c->textures[id].alive) FAIL(c, HR_ERR_INVALID, "bad texture id");
     QUIESCE(c);
     hipFree(c->textures[id].dpx), hipFree(c->textures[id].dmips);
@@ -538,6 +547,7 @@ int hr_texture_destroy(hr_ctx *c, hr_tex_id id)
 int hr_material_set(hr_ctx *c, int32_t id, const hr_material *m)
 {
     ENTER(c);
+    if (c->grp) return groupAll(c, [&](hr_ctx *m_, int) { return hr_material_set(m_, id, m); });
     if (id < 0 || id > (1 << 20) || !m) FAIL(c, HR_ERR_INVALID, "bad material id");
     if ((int)c->materials.size() <= id) {
         hr_material none{};
@@ -552,6 +562,7 @@ int hr_material_set(hr_ctx *c, int32_t id, const hr_material *m)
 int hr_lights_set(hr_ctx *c, const hr_lights *l)
 {
     ENTER(c);
+    if (c->grp) return groupAll(c, [&](hr_ctx *m, int) { return hr_lights_set(m, l); });
     if (!l || l->n_directional < 0 || l->n_directional > HR_MAX_DIRECTIONAL_LIGHTS || l->n_point < 0 || l->n_point > HR_MAX_POINT_LIGHTS ||
         l->n_spot < 0 || l->n_spot > HR_MAX_SPOT_LIGHTS)
         FAIL(c, HR_ERR_INVALID, "bad light block");
@@ -563,6 +574,7 @@ int hr_lights_set(hr_ctx *c, const hr_lights *l)
 int hr_interactive_blocks_set(hr_ctx *c, const int32_t *coords, int32_t nx, int32_t ny)
 {
     ENTER(c);
+    if (c->grp) return groupAll(c, [&](hr_ctx *m, int) { return hr_interactive_blocks_set(m, coords, nx, ny); });
     if (!coords) {
         c->blockNx = c->blockNy = 0;
     } else {
@@ -590,6 +602,7 @@ static int setTable(hr_ctx *c, float2 **dst, const float *src, size_t n)
 int hr_sequences_set(hr_ctx *c, const float *seq, const float *ap, int32_t nSeq, int32_t len)
 {
     ENTER(c);
+    if (c->grp) return groupAll(c, [&](hr_ctx *m, int) { return hr_sequences_set(m, seq, ap, nSeq, len); });
     if (!seq || !ap || nSeq <= 0 || nSeq > 255 || len <= 0) FAIL(c, HR_ERR_INVALID, "bad sequence table");
     int rc = setTable(c, &c->dSeq, seq, (size_t)nSeq * len);
     if (rc) return rc;
@@ -603,6 +616,7 @@ int hr_sequences_set(hr_ctx *c, const float *seq, const float *ap, int32_t nSeq,
 int hr_seq_offsets_set(hr_ctx *c, const float *off, int32_t n)
 {
     ENTER(c);
+    if (c->grp) return groupAll(c, [&](hr_ctx *m, int) { return hr_seq_offsets_set(m, off, n); });
     if (!off || n <= 0) FAIL(c, HR_ERR_INVALID, "bad offsets table");
     int rc = setTable(c, &c->dSeqOffsets, off, (size_t)n);
     if (rc) return rc;
@@ -689,6 +703,7 @@ static int tableToHost(hr_ctx *c, float2 *d, uint32_t count, float *out)
 int hr_qmc_generate(hr_ctx *c, int32_t mode, uint32_t seqIndex, uint32_t count, int32_t radial, float *out)
 {
     ENTER(c);
+    if (c->grp) return groupOne(c, 0, [&](hr_ctx *m) { return hr_qmc_generate(m, mode, seqIndex, count, radial, out); });
     if (!knownSampleMode(mode)) FAIL(c, HR_ERR_INVALID, "unknown sample mode");
     if (radial && mode != HR_SAMPLE_SOBOL) FAIL(c, HR_ERR_INVALID, "radial is defined for Sobol only");
     if (count == 0 || !out) FAIL(c, HR_ERR_INVALID, "bad count / output");
@@ -708,6 +723,7 @@ int hr_qmc_generate(hr_ctx *c, int32_t mode, uint32_t seqIndex, uint32_t count, 
 int hr_aperture_generate(hr_ctx *c, int32_t bokeh, uint32_t seqIndex, uint32_t count, float *out)
 {
     ENTER(c);
+    if (c->grp) return groupOne(c, 0, [&](hr_ctx *m) { return hr_aperture_generate(m, bokeh, seqIndex, count, out); });
     if (!knownBokeh(bokeh)) FAIL(c, HR_ERR_INVALID, "unknown bokeh shape");
     if (count == 0 || !out) FAIL(c, HR_ERR_INVALID, "bad count / output");
     float2 *d = nullptr;
@@ -726,6 +742,7 @@ int hr_aperture_generate(hr_ctx *c, int32_t bokeh, uint32_t seqIndex, uint32_t c
 int hr_sequences_generate(hr_ctx *c, int32_t sampleMode, int32_t bokeh, int32_t len)
 {
     ENTER(c);
+    if (c->grp) return groupAll(c, [&](hr_ctx *m, int) { return hr_sequences_generate(m, sampleMode, bokeh, len); });
     if (!knownSampleMode(sampleMode)) FAIL(c, HR_ERR_INVALID, "unknown sample mode");
     if (!knownBokeh(bokeh)) FAIL(c, HR_ERR_INVALID, "unknown bokeh shape");
     if (len <= 0) FAIL(c, HR_ERR_INVALID, "bad sequence length");
@@ -754,6 +771,7 @@ int hr_sequences_generate(hr_ctx *c, int32_t sampleMode, int32_t bokeh, int32_t 
 int hr_seq_offsets_generate(hr_ctx *c)
 {
     ENTER(c);
+    if (c->grp) return groupAll(c, [](hr_ctx *m, int) { return hr_seq_offsets_generate(m); });
     if (c->W <= 0) FAIL(c, HR_ERR_INVALID, "no frame");
     const size_t n = (size_t)c->W * c->H;
     int rc = setTable(c, &c->dSeqOffsets, nullptr, n);
@@ -768,6 +786,7 @@ int hr_seq_offsets_generate(hr_ctx *c)
 int hr_multiscatter_lut_generate(hr_ctx *c, float *out, hr_tex_id *outTex)
 {
     ENTER(c);
+    if (c->grp) return groupMultiscatter(c, out, outTex);
     float2 *seq = nullptr;
     float *lut = nullptr;
     HIP_TRY(c, hipMalloc(&seq, 4096 * sizeof(float2)));

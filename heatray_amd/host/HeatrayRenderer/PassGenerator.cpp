@@ -1,4 +1,5 @@
 #include "PassGenerator.h"
+#include "DeviceList.h"
 
 #include "Lights/EnvironmentLight.h"
 #include "Scene/Scene.h"
@@ -156,7 +157,30 @@ bool PassGenerator::runInitJob(const RLint renderWidth, const RLint renderHeight
         return false;
     }
     if (const char* mb = getenv("HEATRAY_MEMORY_BUDGET_MB")) desc.memory_budget = (uint64_t)strtoull(mb, nullptr, 10) << 20;
-    if (hr_ctx_create(&desc, &m_context) != HR_OK) {
+    // HEATRAY_DEVICES ("all" or a list such as 0,1,2,3): one frame split by pixel tiles over several devices, as a context group whose
+    // handle is the current context (include/hrcore_group.h).  A malformed list or a group that cannot be created fails init: never one
+    // device instead of the ones asked for.
+    if (const char* devices = getenv("HEATRAY_DEVICES")) {
+        std::vector<int32_t> ids;
+        std::string error;
+        if (!heatray::parseDeviceList(devices, ids, error)) {
+            fprintf(stderr, "PassGenerator: %s\n", error.c_str());
+            return false;
+        }
+        const int rc = hr_ctx_create_group(&desc, ids.empty() ? nullptr : ids.data(), (int32_t)ids.size(), &m_context);
+        if (rc != HR_OK) {
+            fprintf(stderr, "PassGenerator: HEATRAY_DEVICES=%s: creating the context group failed with status %d (no such device, or no usable HIP device)\n",
+                    devices, rc);
+            m_context = nullptr;
+            return false;
+        }
+        hr_group_info info;
+        if (!HRFunc(hr_group_get_info(m_context, &info))) return false;
+        std::string names;
+        for (int i = 0; i < info.n_members; ++i) names += (i ? "," : "") + std::to_string(info.device_ids[i]);
+        printf("PassGenerator: context group of %d members on devices %s\n", info.n_members, names.c_str());
+        fflush(stdout);
+    } else if (hr_ctx_create(&desc, &m_context) != HR_OK) {
         fprintf(stderr, "PassGenerator: no usable MI355X / HIP device (there is no CPU fallback)\n");
         return false;
     }
