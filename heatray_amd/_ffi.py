@@ -170,6 +170,15 @@ HR_GROUP_MAX_MEMBERS = 16
 GROUP_SYMBOLS = ["group_api_version", "ctx_create_group", "group_get_info", "group_member_stats"]
 
 
+# every symbol include/hrcore_aov.h declares (AOVs).  Resolved lazily, on the first AOV call: a library without them (the CPU oracle)
+# still makes an Engine, and its AOV calls raise EngineError
+HR_AOV_API_VERSION = 1
+HR_AOV_SURFACE, HR_AOV_MOMENTS = 1, 2
+HR_AOV_PLANE_ALBEDO, HR_AOV_PLANE_NORMAL_DEPTH, HR_AOV_PLANE_MOMENTS = 0, 1, 2
+AOV_PLANE_NAMES = ("albedo", "normal_depth", "moments")
+AOV_SYMBOLS = ["aov_api_version", "aov_enable", "aov_mask", "aov_readback", "aov_copy"]
+
+
 class GroupInfo(C.Structure):
     _fields_ = [("n_members", C.c_int32), ("device_ids", C.c_int32 * HR_GROUP_MAX_MEMBERS), ("owned_pixels", C.c_uint64 * HR_GROUP_MAX_MEMBERS)]
 
@@ -468,6 +477,50 @@ class Engine:
         self._call("readback_progressive", C.byref(p), C.byref(w), C.byref(h), C.byref(n))
         a = np.ctypeslib.as_array(p, shape=(h.value, w.value, 4))
         return (a.copy() if copy else a), int(n.value)
+
+    # -- AOVs (include/hrcore_aov.h)
+    def _aov_call(self, name, *args):
+        if not getattr(self, "_aov_checked", False):
+            missing = [s for s in AOV_SYMBOLS if not hasattr(self._lib, self._p + s)]
+            if missing:
+                raise EngineError(f"this library has no AOVs (lacks {[self._p + s for s in missing]})")
+            ver = getattr(self._lib, self._p + "aov_api_version")
+            ver.restype = C.c_uint32
+            if ver() != HR_AOV_API_VERSION:
+                raise EngineError(f"{self._p}aov_api_version() = {ver()}, this binding was written against {HR_AOV_API_VERSION}: rebuild the library")
+            self._aov_checked = True
+        self._call(name, *args)
+
+    def set_aovs(self, mask):
+        """Enable the AOV planes of `mask` (HR_AOV_SURFACE | HR_AOV_MOMENTS; 0 frees them).  Completes the passes in flight; a changed
+        mask starts the planes at zero, so they hold the passes requested after this call."""
+        self._aov_call("aov_enable", C.c_uint32(int(mask)))
+
+    def aov_mask(self):
+        m = C.c_uint32()
+        self._aov_call("aov_mask", C.byref(m))
+        return int(m.value)
+
+    def aov_plane(self, plane):
+        """(H x W x 4 float32 copy of one plane, passes summed into it); completes the enqueued passes first."""
+        p = f32p()
+        w, h, n = C.c_int32(), C.c_int32(), C.c_uint64()
+        self._aov_call("aov_readback", C.c_int32(plane), C.byref(p), C.byref(w), C.byref(h), C.byref(n))
+        return np.ctypeslib.as_array(p, shape=(h.value, w.value, 4)).copy(), int(n.value)
+
+    def aovs(self):
+        """The raw sums of every enabled plane: {"albedo", "normal_depth", "moments": H x W x 4 float32, "passes": n}
+        (include/hrcore_aov.h; heatray_amd.aov.resolve turns them into means and a variance)."""
+        mask = self.aov_mask()
+        out = {}
+        for plane, name in enumerate(AOV_PLANE_NAMES):
+            if mask & (HR_AOV_MOMENTS if plane == HR_AOV_PLANE_MOMENTS else HR_AOV_SURFACE):
+                out[name], out["passes"] = self.aov_plane(plane)
+        return out
+
+    def aov_to_device(self, plane, device_ptr, stream=None):
+        """Asynchronous copy of one plane (W x H float4) into device memory, e.g. a torch tensor; ordered like display_device."""
+        self._aov_call("aov_copy", C.c_int32(plane), C.c_void_p(int(device_ptr)), C.c_void_p(stream or 0))
 
     def debug_trace(self, origins, dirs, tmax=None, skip_prim=None, any_hit=False):
         o, d = _f32(origins).reshape(-1, 3), _f32(dirs).reshape(-1, 3)

@@ -129,11 +129,39 @@ static void slotBudget(hr_ctx *c)
     c->maxSlots = kMaxSlots;
     if (hipMemGetInfo(&freeB, &totalB) == hipSuccess) {
         const size_t fbBytes = (size_t)c->W * c->H * 4 * sizeof(float);
-        const size_t k = c->allLightsUsed ? 4 : 1;
+        const size_t k = (c->allLightsUsed ? 4 : 1) + c->aovFramesPerSlot();
         const size_t perSlot = fbBytes * k + sizeof(Counters);
         const size_t fit = (freeB / 2) / perSlot; // at most half of the free device memory for pass slots
         c->maxSlots = fit < 1 ? 1 : (fit > (size_t)kMaxSlots ? kMaxSlots : (int)fit);
     }
+}
+
+// AOVs (include/hrcore_aov.h): the frame's planes of the enabled mask at the frame's size, zeroed on the ctx stream
+static void aovFreePlanes(hr_ctx *c)
+{
+    for (float *&p : c->aovPlane) hipFree(p), p = nullptr;
+    if (c->aovPinned) hipHostFree(c->aovPinned);
+    c->aovPinned = nullptr, c->aovPinnedBytes = 0;
+}
+static void aovFree(hr_ctx *c)
+{
+    aovFreePlanes(c);
+    if (c->evAov) hipEventDestroy(c->evAov);
+    c->evAov = nullptr;
+}
+static int aovAllocPlanes(hr_ctx *c)
+{
+    aovFreePlanes(c);
+    c->aovZeroedAt = c->nextResolveOrder;
+    if (c->W <= 0) return HR_OK;
+    const size_t bytes = (size_t)c->W * c->H * 4 * sizeof(float);
+    const bool want[3] = {(c->aovMask & HR_AOV_SURFACE) != 0, (c->aovMask & HR_AOV_SURFACE) != 0, (c->aovMask & HR_AOV_MOMENTS) != 0};
+    for (int p = 0; p < 3; ++p) {
+        if (!want[p]) continue;
+        HIP_TRY(c, hipMalloc(&c->aovPlane[p], bytes));
+        HIP_TRY(c, hipMemsetAsync(c->aovPlane[p], 0, bytes, c->stream));
+    }
+    return HR_OK;
 }
 
 static void freeTree(hr_ctx *c)
@@ -313,6 +341,7 @@ int hr_ctx_destroy(hr_ctx *c)
     hipFree(c->fbInternal);
     if (c->pinned) hipHostFree(c->pinned);
     hipFree(c->dDisplay);
+    aovFree(c);
     c->meshReleaseAll();
     for (int k = 0; k < 2; ++k) {
         if (c->stage[k]) hipHostFree(c->stage[k]);
@@ -534,6 +563,10 @@ int hr_frame_resize(hr_ctx *c, int32_t w, int32_t h)
     f.nOwnedTiles = nTiles > c->rank ? (nTiles - c->rank + c->world - 1) / c->world : 0;
     // one path per owned pixel and pass: queue capacity = owned tiles x tile^2; pass slots are allocated on demand
     freeQueues(c);
+    {
+        const int rc = aovAllocPlanes(c);
+        if (rc) return rc;
+    }
     c->queueCapacity = (uint32_t)f.nOwnedTiles * (uint32_t)(c->tile * c->tile);
     // how many passes may be in flight: each slot holds two ray queues, an occlusion queue, hit records and a pass buffer
     slotBudget(c);
@@ -667,3 +700,6 @@ int hr_debug_trace(hr_ctx *c, int32_t n, const float *o, const float *d, const f
 
 // ------------------------------------------------------------------------------------------ context groups
 #include "hr_group.inl"
+
+// ------------------------------------------------------------------------------------------ AOVs
+#include "hr_aov.inl"

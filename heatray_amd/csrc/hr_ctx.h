@@ -121,6 +121,7 @@ struct hr_ctx {
         uint32_t sCapCur = 0;  // occlusion rays scur can hold
         float *passbuf = nullptr;
         float *passbufB = nullptr; // second partial sum (allLightsUsed): passbuf + W * H * 4, same allocation
+        float *aov = nullptr;      // HR_AOV_SURFACE: the pass's AOV record (two float4 per pixel) behind the partial sums, same allocation
         Counters *ctr = nullptr;
     };
     PassSlot slots[kMaxSlots];
@@ -427,10 +428,22 @@ struct hr_ctx {
     float *fb() const { return fbExternal ? fbExternal : fbInternal; }
     // tuning knobs (defaults measured on MI355X; HR_TUNE="tri=4,refill=8,blocks=6,depth=12,batch=2,groups=2" overrides for experiments)
     int tuneTri = 2, tuneRefill = 16, tuneBlocks = 5, tuneShadeBlocks = 4, tuneDepth = kMaxSlots, tuneBatch = 0, tuneFetchMax = 64, tuneFetchMin = 64, tuneStaticDeal = 256, tuneFetchPrimary = 128, tuneFetchGate = 8, tuneHeads = 5, tuneSlowMs = 4;
+    // AOVs (include/hrcore_aov.h): the frame's planes, summed by k_resolve_aov in pass order beside the frame.  With HR_AOV_SURFACE every
+    // pass slot also holds the pass's AOV record (PassSlot::aov) and the shading kernel variant with MODE & 4 writes it.
+    uint32_t aovMask = 0;
+    float *aovPlane[3] = {nullptr, nullptr, nullptr}; // W x H float4 each (HR_AOV_PLANE_*), null when not enabled
+    float *aovPinned = nullptr;                       // hr_aov_readback's host buffer
+    size_t aovPinnedBytes = 0;
+    unsigned long long aovZeroedAt = 0;               // value of nextResolveOrder when the planes were last zeroed
+    hipEvent_t evAov = nullptr;                       // orders hr_aov_copy on a foreign stream against the resolves
+    size_t aovFramesPerSlot() const { return (aovMask & HR_AOV_SURFACE) ? 2 : 0; }
     // Context group (include/hrcore_group.h): non-null when this handle is a group.  Its own fields then describe the ASSEMBLED frame on the
     // group's first device (W, H, frame, fbInternal, the read-back buffers) and `stream` is the assembly stream; no pass pipeline runs on it.
     GroupState *grp = nullptr;
-    LaunchCfg cfg(hipStream_t st) const { return LaunchCfg{st, numCUs, tuneBlocks, tuneShadeBlocks, collectStats, textureLodUsed, allLightsUsed, hasGlass, tunePacketSwizzle}; }
+    LaunchCfg cfg(hipStream_t st) const
+    {
+        return LaunchCfg{st, numCUs, tuneBlocks, tuneShadeBlocks, collectStats, textureLodUsed, allLightsUsed, hasGlass, tunePacketSwizzle, (aovMask & HR_AOV_SURFACE) != 0};
+    }
 };
 
 #define FAIL(ctx, code, msg)  \

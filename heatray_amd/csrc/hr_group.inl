@@ -185,6 +185,7 @@ static int groupDestroy(hr_ctx *c)
     if (c->pinned) hipHostFree(c->pinned);
     hipFree(c->dDisplay);
     if (c->pinnedDisplay) hipHostFree(c->pinnedDisplay);
+    aovFree(c);
     delete g;
     delete c;
     return HR_OK;
@@ -238,7 +239,7 @@ static int groupResize(hr_ctx *c, int32_t w, int32_t h)
     f.tilesX = (w + c->tile - 1) / c->tile, f.tilesY = (h + c->tile - 1) / c->tile;
     f.nOwnedTiles = f.tilesX * f.tilesY;
     f.fb = c->fbInternal;
-    return HR_OK;
+    return aovAllocPlanes(c); // (the group's AOV planes, assembled like the frame)
 }
 
 // Every member packs the passes it has resolved (drain: after completing all it has been given), members on other devices copy their

@@ -3,6 +3,7 @@
 
 #include "hr_types.h"
 #include "../../include/hrcore_group.h"
+#include "../../include/hrcore_aov.h"
 
 #include <cstddef>
 
@@ -34,6 +35,7 @@ struct LaunchCfg {
     bool allLights;  // some pass has asked for HR_ESTIMATOR_ALL_LIGHTS: the shading kernel that can emit two occlusion rays per vertex
     bool hasGlass;   // some material of the scene is glass: the glass shading kernel is launched too
     int packetSwizzle = 0; // k_raygen_packets deals whole 32x32 tiles to the XCDs instead of consecutive 16-pixel patches (HR_TUNE pswz)
+    bool aovSurface = false; // HR_AOV_SURFACE is enabled: launch the shading kernel that records the first visible surface (include/hrcore_aov.h)
 };
 
 // One in-flight pass as seen by the kernels of one macro step.
@@ -62,6 +64,7 @@ struct SegDev {
     uint32_t qinCap;  // rays qin can hold
     uint32_t sInCap;  // occlusion rays sqIn can hold
     uint32_t sOutCap; // occlusion rays sqOut can hold
+    float *aov;       // HR_AOV_SURFACE: the pass's AOV record, two float4 per pixel (albedo + hit, normal + depth; full-frame indexing), or null
 };
 
 #ifndef HR_MAX_SEGS
@@ -138,6 +141,13 @@ void launchZeroCounters(const LaunchCfg &cfg, const CounterList &list);
 void launchFetchTable(hipStream_t stream, const void *hostMapped, void *dst, size_t bytes);
 void launchRaygen(const LaunchCfg &cfg, const SceneDev *S, const StepTable *tbl, const SegList &segs, const FrameDev &fr, Stats *stats);
 void launchResolve(const LaunchCfg &cfg, const FrameDev &fr, const PassBufList &bufs);
+// AOVs (include/hrcore_aov.h): the frame's planes (null when not enabled) and each pass's AOV planes (null without HR_AOV_SURFACE), in
+// the order of PassBufList.  The resolve that adds the passes to the frame folds them into the planes and zeroes the passes' planes.
+struct AovList {
+    float *albedo, *normalDepth, *moments;
+    float *pass[kMaxBatch];
+};
+void launchResolveAov(const LaunchCfg &cfg, const FrameDev &fr, const PassBufList &bufs, const AovList &aov);
 void launchPackOwned(const LaunchCfg &cfg, const FrameDev &fr, const float *frame, float *packed, int unpack, float *full);
 // Context groups (hr_group.inl): the packed pixels of every member (rank m of world n, ownedPixel order) -> their places in the full
 // frame, ONE launch for all members.  Member m's slots are padded to whole workgroups: its workgroups are

@@ -13,7 +13,9 @@ int hr_clear(hr_ctx *c)
     }
     HIP_TRY(c, hipMemsetAsync(c->fb(), 0, (size_t)c->W * c->H * 4 * sizeof(float), c->stream));
     HIP_TRY(c, hipMemsetAsync(c->dStats, 0, sizeof(Stats) * kStatSlots, c->stream));
-    c->resolvedAtClear = c->nextResolveOrder;
+    for (float *plane : c->aovPlane)
+        if (plane) HIP_TRY(c, hipMemsetAsync(plane, 0, (size_t)c->W * c->H * 4 * sizeof(float), c->stream));
+    c->resolvedAtClear = c->aovZeroedAt = c->nextResolveOrder;
     c->snapshotEpoch++;
     if (getenv("HR_DEBUG_PIPE")) fprintf(stderr, "hr_clear %p: ray-memory growths so far %llu, waits %llu (%.2f ms)\n", (void *)c, c->dbgGrowths, c->dbgWaits, (double)c->dbgWaitNs * 1e-6);
     c->drainTimes();
@@ -21,11 +23,13 @@ int hr_clear(hr_ctx *c)
     return HR_OK;
 }
 
-static int allocSlot(hr_ctx *c, hr_ctx::PassSlot &ps)
+static int allocSlot(hr_ctx *c, hr_ctx::PassSlot &ps, hipStream_t st)
 {
     const size_t fbBytes = (size_t)c->W * c->H * 4 * sizeof(float);
-    // (with HR_ESTIMATOR_ALL_LIGHTS the sample's further partial sums lie right behind the first: k_trace indexes one buffer)
-    const hipError_t e = hipMalloc(&ps.passbuf, fbBytes * (c->allLightsUsed ? 4 : 1));
+    const size_t sums = c->allLightsUsed ? 4 : 1;
+    // (with HR_ESTIMATOR_ALL_LIGHTS the sample's further partial sums lie right behind the first: k_trace indexes one buffer; the AOV record
+    // of HR_AOV_SURFACE behind them)
+    const hipError_t e = hipMalloc(&ps.passbuf, fbBytes * (sums + c->aovFramesPerSlot()));
     if (e != hipSuccess) { // say what ran out: a pass slot is the unit the pipeline's memory grows in
         size_t freeB = 0, totalB = 0;
         hipMemGetInfo(&freeB, &totalB);
@@ -34,6 +38,11 @@ static int allocSlot(hr_ctx *c, hr_ctx::PassSlot &ps)
         return HR_ERR_DEVICE;
     }
     if (c->allLightsUsed) ps.passbufB = ps.passbuf + (size_t)c->W * c->H * 4;
+    if (c->aovFramesPerSlot()) { // zeroed once here (complete before any stream uses the slot); from then on the resolve that reads a pass's record zeroes it
+        ps.aov = ps.passbuf + sums * (size_t)c->W * c->H * 4;
+        HIP_TRY(c, hipMemsetAsync(ps.aov, 0, fbBytes * c->aovFramesPerSlot(), st));
+        HIP_TRY(c, hipStreamSynchronize(st));
+    }
     ps.ctr = c->dCounters + (&ps - c->slots);
     HIP_TRY(c, hipEventCreateWithFlags(&ps.evFinal, hipEventDisableTiming));
     HIP_TRY(c, hipEventCreateWithFlags(&ps.evResolved, hipEventDisableTiming));
@@ -147,7 +156,14 @@ static int resolveReady(hr_ctx *c)
             if (!seen) HIP_TRY(c, hipStreamWaitEvent(c->stream, ready[k]->finalEv, 0));
         }
         c->timeBegin(HR_KERNEL_RESOLVE, c->stream);
-        launchResolve(cfg, fr, bufs);
+        if (c->aovMask) {
+            AovList aov{};
+            aov.albedo = c->aovPlane[HR_AOV_PLANE_ALBEDO], aov.normalDepth = c->aovPlane[HR_AOV_PLANE_NORMAL_DEPTH], aov.moments = c->aovPlane[HR_AOV_PLANE_MOMENTS];
+            for (int k = 0; k < bufs.n; ++k) aov.pass[k] = ready[k]->aov;
+            launchResolveAov(cfg, fr, bufs, aov);
+        } else {
+            launchResolve(cfg, fr, bufs);
+        }
         c->timeEnd(c->stream);
         HIP_TRY(c, hipEventRecord(ready[bufs.n - 1]->evResolved, c->stream));
         for (int k = 0; k < bufs.n; ++k) {
@@ -230,7 +246,7 @@ static int macroStep(hr_ctx *c, int g, int nInject)
         if (slot < 0) FAIL(c, HR_ERR_INVALID, "internal: no free pass slot");
         hr_ctx::PassSlot &ps = c->slots[slot];
         if (!ps.allocated) {
-            int rc = allocSlot(c, ps);
+            int rc = allocSlot(c, ps, G.stream);
             if (rc) return rc;
         }
         if (ps.everResolved) { // the pass buffer is free again once the launch that resolved it has run
@@ -420,6 +436,7 @@ static int macroStep(hr_ctx *c, int g, int nInject)
         }
         sg.passbuf = ps.passbuf;
         sg.passbufB = ps.pp.estimator == HR_ESTIMATOR_ALL_LIGHTS ? ps.passbufB : nullptr;
+        sg.aov = ps.aov;
         // The per-stage counters are a ring: a chain of pass-through rays (stacked single-sided sheets seen from behind, alpha holes:
         // physicallyBased.rlsl:70-108 re-emits without a depth bound) can outlive any fixed number of stages, so from stage
         // kMaxBounceSlots - 1 on the entries this step appends to are cleared first (their previous use lies a whole ring back).
@@ -659,7 +676,7 @@ static bool packetsInUse(const hr_ctx *c) { return c->tunePackets == 1 || (c->tu
 static double budgetBytesPerPass(const hr_ctx *c, int stages)
 {
     const double P = (double)(c->queueCapacity ? c->queueCapacity : 1u), kS = c->allLightsUsed ? 4.0 : 1.0;
-    const double fb = (double)c->W * c->H * 16.0 * (c->allLightsUsed ? 4.0 : 1.0);
+    const double fb = (double)c->W * c->H * 16.0 * ((c->allLightsUsed ? 4.0 : 1.0) + (double)c->aovFramesPerSlot());
     double arena = 0.0, scratch = 0.0;
     for (int st = 0; st + 1 < stages && st < kMaxBounceSlots; ++st) { // (the last stage traces occlusion rays only)
         arena += c->stageSeen[st] ? 1.1 * c->stageArenaSeen[st] : P * (64.0 + 48.0 * kS);
@@ -789,7 +806,7 @@ int hr_render_pass(hr_ctx *c, const hr_pass_params *pp)
         if (want > slotLimit(c)) want = slotLimit(c);
         for (int i = 0; i < kMaxSlots && c->nSlotsAllocated < want; ++i)
             if (!c->slots[i].allocated) {
-                rc = allocSlot(c, c->slots[i]);
+                rc = allocSlot(c, c->slots[i], c->stream);
                 if (rc) return rc;
             }
     }

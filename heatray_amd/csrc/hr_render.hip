@@ -112,12 +112,15 @@ HRD uint32_t packMeta(const Ray &r)
     return (uint32_t)(r.sequenceID & 0xFF) | ((uint32_t)(r.depth & 0xFFFF) << 8) | ((uint32_t)r.missKind << 24) | ((uint32_t)r.missIdx << 27);
 }
 
-HRD void storeRay(const RayQueue &q, uint32_t slot, const Ray &r, uint32_t pixel, uint32_t srcPrim)
+// Bits 30-31 of the meta word are free (every reader masks its fields): bit 30 is kMetaAovFirst, set by the shading kernels of HR_AOV_SURFACE
+// on a pass-through continuation of a path that has not met its first visible surface yet (a camera ray is one by its depth 0)
+static const uint32_t kMetaAovFirst = 1u << 30;
+HRD void storeRay(const RayQueue &q, uint32_t slot, const Ray &r, uint32_t pixel, uint32_t srcPrim, uint32_t metaBits = 0u)
 {
     G(q.A)[slot] = make_float4(r.o.x, r.o.y, r.o.z, r.maxT);
     G(q.B)[slot] = make_float4(r.d.x, r.d.y, r.d.z, r.extraT);
     G(q.C)[slot] = make_float4(r.weight.x, r.weight.y, r.weight.z, __uint_as_float(pixel));
-    G(q.D)[slot] = make_int4((int)packMeta(r), r.sequenceIndexOffset, (int)srcPrim, (int)packCone(r.coneW, r.coneG));
+    G(q.D)[slot] = make_int4((int)(packMeta(r) | metaBits), r.sequenceIndexOffset, (int)srcPrim, (int)packCone(r.coneW, r.coneG));
 }
 
 // pixel of thread `gid` in this context's tile shard: tiles in round-robin order, 8x8-pixel blocks inside
@@ -250,6 +253,44 @@ __global__ __launch_bounds__(kBlock) void k_resolve(FrameDev fr, PassBufList buf
         a.x = a.x + s.x, a.y = a.y + s.y, a.z = a.z + s.z, a.w = a.w + s.w;
     }
     reinterpret_cast<float4 *>(fr.fb)[pixel] = a;
+}
+
+// The same with AOVs enabled (include/hrcore_aov.h): every pass is also folded into the frame's AOV planes, in the same order, and its
+// own AOV planes are zeroed for the slot's next pass (so ray generation never clears them).  k_resolve stays the kernel without AOVs.
+__global__ __launch_bounds__(kBlock) void k_resolve_aov(FrameDev fr, PassBufList bufs, AovList aov)
+{
+    int x = 0, y = 0;
+    if (!ownedPixel(fr, blockIdx.x * kBlock + threadIdx.x, x, y)) return;
+    const uint32_t pixel = (uint32_t)(y * fr.W + x);
+    float4 a = reinterpret_cast<float4 *>(fr.fb)[pixel];
+    float4 m = aov.moments ? reinterpret_cast<float4 *>(aov.moments)[pixel] : make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+    float4 al = aov.albedo ? reinterpret_cast<float4 *>(aov.albedo)[pixel] : make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+    float4 nd = aov.normalDepth ? reinterpret_cast<float4 *>(aov.normalDepth)[pixel] : make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+    for (int k = 0; k < bufs.n; ++k) {
+        float4 s = reinterpret_cast<const float4 *>(bufs.buf[k])[pixel];
+        if (bufs.bufB[k]) {
+            const size_t pixelsB = (size_t)(bufs.bufB[k] - bufs.buf[k]) >> 2;
+            for (int j = 1; j <= 3; ++j) {
+                const float4 t = reinterpret_cast<const float4 *>(bufs.buf[k])[pixel + j * pixelsB];
+                s.x = s.x + t.x, s.y = s.y + t.y, s.z = s.z + t.z;
+            }
+        }
+        a.x = a.x + s.x, a.y = a.y + s.y, a.z = a.z + s.z, a.w = a.w + s.w;
+        const float sx = s.x * s.x, sy = s.y * s.y, sz = s.z * s.z; // (-ffp-contract=off: rounded, then added)
+        m.x = m.x + sx, m.y = m.y + sy, m.z = m.z + sz, m.w = m.w + s.w;
+        if (aov.pass[k]) { // (a pass's planes are interleaved: albedo and normal-depth of a pixel are 32 consecutive bytes)
+            float4 *p = reinterpret_cast<float4 *>(aov.pass[k]) + 2 * (size_t)pixel;
+            const float4 pa = p[0], pn = p[1];
+            al.x = al.x + pa.x, al.y = al.y + pa.y, al.z = al.z + pa.z, al.w = al.w + pa.w;
+            nd.x = nd.x + pn.x, nd.y = nd.y + pn.y, nd.z = nd.z + pn.z, nd.w = nd.w + pn.w;
+            p[0] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+            p[1] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+        }
+    }
+    reinterpret_cast<float4 *>(fr.fb)[pixel] = a;
+    if (aov.moments) reinterpret_cast<float4 *>(aov.moments)[pixel] = m;
+    if (aov.albedo) reinterpret_cast<float4 *>(aov.albedo)[pixel] = al;
+    if (aov.normalDepth) reinterpret_cast<float4 *>(aov.normalDepth)[pixel] = nd;
 }
 
 // ----------------------------------------------------------------------------------- shard exchange
@@ -1364,7 +1405,7 @@ __global__ __launch_bounds__(kShadeBlock, HR_HIT_MINBLOCKS) void k_shade_hit(con
         return listed < tbl->seg[k].hitCap ? listed : tbl->seg[k].hitCap;
     });
     const uint32_t total = start[nSeg];
-    constexpr bool LOD = (MODE & 1) != 0, ALL = (MODE & 2) != 0;
+    constexpr bool LOD = (MODE & 1) != 0, ALL = (MODE & 2) != 0, AOV = (MODE & 4) != 0;
     uint32_t nShaded = 0, nAccum = 0;
     for (uint32_t base = blockIdx.x * kShadeBlock; base < total; base += gridDim.x * kShadeBlock) {
         const uint32_t i = base + threadIdx.x;
@@ -1374,6 +1415,7 @@ __global__ __launch_bounds__(kShadeBlock, HR_HIT_MINBLOCKS) void k_shade_hit(con
         ExtraRay nee, extra[3]; // (occlusion rays in their compact form: direction, range, the value their light's shader adds; they start at the hit point)
         nee.valid = next.valid = extra[0].valid = extra[1].valid = extra[2].valid = false;
         uint32_t pixel = 0, prim = 0xFFFFFFFFu;
+        uint32_t nextMeta = 0u; // HR_AOV_SURFACE: kMetaAovFirst when `next` is a pass-through continuation of a path still before its first surface
         v3 hitP(0.0f);
         if (live) {
             const SegDev &sg = tbl->seg[sI];
@@ -1394,6 +1436,10 @@ __global__ __launch_bounds__(kShadeBlock, HR_HIT_MINBLOCKS) void k_shade_hit(con
             in.coneW = in.coneG = 0.0f;
             if (LOD) unpackCone((uint32_t)dm.w, in.coneW, in.coneG);
             ShaderT<MODE> sh(S, sg.pp, G(sg.passbuf) + (size_t)pixel * 4);
+            if constexpr (AOV) {
+                sh.aov.px = sg.aov ? G(sg.aov) + (size_t)pixel * 8 : nullptr;
+                sh.aov.first = in.depth == 0 || (meta & kMetaAovFirst) != 0u;
+            }
             prim = h.prim & 0x7FFFFFFFu;
             uint32_t mid;
             const typename ShaderT<MODE>::Surface sf = sh.surface(in, prim, (h.prim >> 31) != 0u, h.t, h.u, h.v, mid);
@@ -1406,6 +1452,7 @@ __global__ __launch_bounds__(kShadeBlock, HR_HIT_MINBLOCKS) void k_shade_hit(con
                 sh.physicallyBased(in, sf, M, nee, next, extra[0], extra[1], extra[2]);
             hitP = sf.P; // (where the occlusion rays start)
             nAccum += sh.nAccum;
+            if constexpr (AOV) nextMeta = (sh.aov.first && sh.aov.through) ? kMetaAovFirst : 0u;
         }
         // the emitted rays leave through compacted appends to the pass's queues
         const uint32_t last = (total - base < (uint32_t)kShadeBlock ? total - base : (uint32_t)kShadeBlock) - 1u;
@@ -1438,7 +1485,7 @@ __global__ __launch_bounds__(kShadeBlock, HR_HIT_MINBLOCKS) void k_shade_hit(con
             }
             const bool wantQ = live && next.valid;
             const uint32_t qSlot = blockReserve(wantQ, sg.qCountOut, scratch);
-            if (wantQ && qSlot < sg.hitCap) storeRay(sg.qout, qSlot, next, pixel, prim);
+            if (wantQ && qSlot < sg.hitCap) storeRay(sg.qout, qSlot, next, pixel, prim, nextMeta);
             if (wantQ && qSlot >= sg.hitCap) queueOverflow(tbl, OVF_CLOSEST_OUT, (uint32_t)sLo, qSlot + 1u);
         } else {
             unsigned long long todo = __ballot(live && (nee.valid || next.valid || (ALL && (extra[0].valid || extra[1].valid || extra[2].valid))));
@@ -1471,7 +1518,7 @@ __global__ __launch_bounds__(kShadeBlock, HR_HIT_MINBLOCKS) void k_shade_hit(con
                 }
                 const bool wantQ = mine && next.valid;
                 const uint32_t qSlot = waveReserve(wantQ, sg.qCountOut);
-                if (wantQ && qSlot < sg.hitCap) storeRay(sg.qout, qSlot, next, pixel, prim);
+                if (wantQ && qSlot < sg.hitCap) storeRay(sg.qout, qSlot, next, pixel, prim, nextMeta);
                 if (wantQ && qSlot >= sg.hitCap) queueOverflow(tbl, OVF_CLOSEST_OUT, (uint32_t)s, qSlot + 1u);
             }
         }
@@ -1530,6 +1577,13 @@ void launchResolve(const LaunchCfg &cfg, const FrameDev &fr, const PassBufList &
     hipLaunchKernelGGL(k_resolve, dim3((threads + kBlock - 1) / kBlock), dim3(kBlock), 0, cfg.stream, fr, bufs);
 }
 
+void launchResolveAov(const LaunchCfg &cfg, const FrameDev &fr, const PassBufList &bufs, const AovList &aov)
+{
+    const int threads = ownedThreads(fr);
+    if (threads <= 0 || bufs.n <= 0) return;
+    hipLaunchKernelGGL(k_resolve_aov, dim3((threads + kBlock - 1) / kBlock), dim3(kBlock), 0, cfg.stream, fr, bufs, aov);
+}
+
 void launchTrace(const LaunchCfg &cfg, const SceneDev *S, const int *leafKeys, const Node32 *nodes32, const Tri *tris, StepTable *tbl, Stats *stats)
 {
     const int grid = cfg.numCUs * cfg.traceBlocksPerCU * (kBlock / kTraceBlock); // traceBlocksPerCU counts 256-thread workgroups
@@ -1584,14 +1638,19 @@ template <int MODE> static void launchShadeHit(const LaunchCfg &cfg, int grid, c
 void launchShade(const LaunchCfg &cfg, const SceneDev *S, const StepTable *tbl, Stats *stats)
 {
     const int grid = cfg.numCUs * cfg.shadeBlocksPerCU;
-    // four instantiations: bit 0 = HR_TEXTURE_LOD_CONE, bit 1 = HR_ESTIMATOR_ALL_LIGHTS compiled in; the plain one runs until a pass asks for more
-    const int mode = (cfg.textureLod ? 1 : 0) | (cfg.allLights ? 2 : 0);
+    // eight instantiations: bit 0 = HR_TEXTURE_LOD_CONE, bit 1 = HR_ESTIMATOR_ALL_LIGHTS, bit 2 = HR_AOV_SURFACE compiled in; the plain one
+    // runs until a pass asks for more (AOVs: while they are enabled)
+    const int mode = (cfg.textureLod ? 1 : 0) | (cfg.allLights ? 2 : 0) | (cfg.aovSurface ? 4 : 0);
     hipLaunchKernelGGL(k_shade_sort, dim3(cfg.numCUs * 8), dim3(kSortBlock), 0, cfg.stream, S, tbl, stats);
     switch (mode) {
     case 0: launchShadeHit<0>(cfg, grid, S, tbl, stats); break;
     case 1: launchShadeHit<1>(cfg, grid, S, tbl, stats); break;
     case 2: launchShadeHit<2>(cfg, grid, S, tbl, stats); break;
-    default: launchShadeHit<3>(cfg, grid, S, tbl, stats); break;
+    case 3: launchShadeHit<3>(cfg, grid, S, tbl, stats); break;
+    case 4: launchShadeHit<4>(cfg, grid, S, tbl, stats); break;
+    case 5: launchShadeHit<5>(cfg, grid, S, tbl, stats); break;
+    case 6: launchShadeHit<6>(cfg, grid, S, tbl, stats); break;
+    default: launchShadeHit<7>(cfg, grid, S, tbl, stats); break;
     }
 }
 

@@ -40,16 +40,27 @@ struct ExtraRay {
     bool valid;
 };
 
+// HR_AOV_SURFACE (include/hrcore_aov.h): where a path records its first visible surface.  Empty unless the variant has AOVs compiled in.
+template <bool ON> struct AovState {
+};
+template <> struct AovState<true> {
+    HR_GLOBAL float *px = nullptr; // the pass's AOV record of the path's pixel: albedo + hit, normal + depth (null: not recorded in this pass)
+    bool first = false;            // the ray being shaded is the camera ray or a pass-through continuation of it
+    bool through = false;          // the shader made a pass-through continuation (it carries `first` on)
+};
+
 // LOD: compiled with the ray-cone texture lookups of HR_TEXTURE_LOD_CONE.  The shading kernel exists in both variants; the one
 // without is what runs until a pass asks for the mode (its code and register allocation are those of the level-0 sampler alone).
 template <int MODE> struct ShaderT {
     static constexpr bool LOD = (MODE & 1) != 0; // HR_TEXTURE_LOD_CONE compiled in
     static constexpr bool ALL = (MODE & 2) != 0; // HR_ESTIMATOR_ALL_LIGHTS compiled in (a second occlusion ray per vertex)
+    static constexpr bool AOV = (MODE & 4) != 0; // HR_AOV_SURFACE compiled in (the first visible surface is recorded)
     const SceneDev &S;
     const hr_pass_params &pp;
     HR_GLOBAL float *px; // RGBA of the pixel this path belongs to (single owner: plain read-modify-write)
     uint32_t nAccum;
     float lodBase; // HR_TEXTURE_LOD_CONE: log2(texels of a unit-uv-square texture under the cone's footprint); level 0 when <= 0
+    AovState<AOV> aov;
 
     HRD ShaderT(const SceneDev &s, const hr_pass_params &p, HR_GLOBAL float *pixel) : S(s), pp(p), px(pixel), nAccum(0), lodBase(-1e30f) {}
 
@@ -104,6 +115,24 @@ template <int MODE> struct ShaderT {
         px[3] = px[3] + a;
     }
     HRD void performAccumulate(v3 color) { accumulate3(accumulateValue(color)); }
+
+    // The first visible surface (include/hrcore_aov.h), right before the visualizer switch: (baseColor, 1) and (N, camera-space depth)
+    // into the pass's planes — plain stores, the pixel has one path per pass.  Depth: along the camera's viewing axis (-z of view_matrix).
+    HRD void recordSurface(v3 baseColor, v3 N, v3 P)
+    {
+        if constexpr (AOV) {
+            if (!aov.first || !aov.px) return;
+            const float *m = pp.view_matrix;
+            const float depth = dot(P - v3(m[12], m[13], m[14]), -normalize(v3(m[8], m[9], m[10])));
+            reinterpret_cast<HR_GLOBAL float4 *>(aov.px)[0] = make_float4(baseColor.x, baseColor.y, baseColor.z, 1.0f);
+            reinterpret_cast<HR_GLOBAL float4 *>(aov.px)[1] = make_float4(N.x, N.y, N.z, depth);
+        }
+    }
+    // a pass-through continuation (alpha-masked texel, back face of a single-sided material): the surface behind it may be the first
+    HRD void passThrough()
+    {
+        if constexpr (AOV) aov.through = true;
+    }
 
     HRD v4 tex(int id, v2 uv) const
     {
@@ -727,6 +756,7 @@ template <int MODE> struct ShaderT {
         if (F & HR_MF_ALPHA_MASK) { // :70-91 (occlusion rays are resolved inside the any-hit traversal)
             if (alpha < 1.0f) {
                 next = createRay(in, sf.P);
+                passThrough();
                 return;
             }
         }
@@ -735,6 +765,7 @@ template <int MODE> struct ShaderT {
             if (!sf.frontFacing) N = -N;
         } else if (!sf.frontFacing) {
             next = createRay(in, sf.P);
+            passThrough();
             return;
         }
         v3 clearCoatN = N;
@@ -771,6 +802,7 @@ template <int MODE> struct ShaderT {
             v4 s = tex(M.emissive_texture, sf.uv);
             emissive = v3(s.x, s.y, s.z);
         }
+        recordSurface(baseColor, N, sf.P);
         if (pp.enable_visualizer == 1) { // :158-203
             switch (pp.visualizer_mode) {
             case HR_VIS_GEOMETRIC_NORMALS: accumulate4((sf.normal + v3(1.0f)) * 0.5f, 1.0f); break;
@@ -1088,6 +1120,7 @@ template <int MODE> struct ShaderT {
             roughness = roughness * s.y;
             roughnessAlpha = roughness * roughness;
         }
+        recordSurface(baseColor, N, sf.P);
         if (pp.enable_visualizer == 1) { // :179-210
             switch (pp.visualizer_mode) {
             case HR_VIS_GEOMETRIC_NORMALS: accumulate4((sf.normal + v3(1.0f)) * 0.5f, 1.0f); break;
