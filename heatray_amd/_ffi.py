@@ -179,6 +179,19 @@ AOV_PLANE_NAMES = ("albedo", "normal_depth", "moments")
 AOV_SYMBOLS = ["aov_api_version", "aov_enable", "aov_mask", "aov_readback", "aov_copy"]
 
 
+# every symbol include/hrcore_denoise.h declares (the denoiser over the AOV planes).  Resolved lazily like the AOV symbols
+HR_DENOISE_API_VERSION = 1
+HR_DENOISE_MAX_ITERATIONS, HR_DENOISE_MAX_NORMAL_POWER = 8, 16
+HR_DENOISE_KERNEL_AUTO, HR_DENOISE_KERNEL_PLAIN, HR_DENOISE_KERNEL_TILED = 0, 1, 2
+DENOISE_SYMBOLS = ["denoise_api_version", "denoise_default_params", "denoise", "denoise_readback", "denoise_display"]
+
+
+class DenoiseParams(C.Structure):
+    """hr_denoise_params"""
+    _fields_ = [("iterations", C.c_int32), ("normal_power", C.c_int32), ("sigma_l", C.c_float), ("sigma_z", C.c_float),
+                ("kernel", C.c_int32), ("reserved", C.c_uint32 * 3)]
+
+
 class GroupInfo(C.Structure):
     _fields_ = [("n_members", C.c_int32), ("device_ids", C.c_int32 * HR_GROUP_MAX_MEMBERS), ("owned_pixels", C.c_uint64 * HR_GROUP_MAX_MEMBERS)]
 
@@ -521,6 +534,38 @@ class Engine:
     def aov_to_device(self, plane, device_ptr, stream=None):
         """Asynchronous copy of one plane (W x H float4) into device memory, e.g. a torch tensor; ordered like display_device."""
         self._aov_call("aov_copy", C.c_int32(plane), C.c_void_p(int(device_ptr)), C.c_void_p(stream or 0))
+
+    # -- denoiser (include/hrcore_denoise.h)
+    def _denoise_call(self, name, *args):
+        if not getattr(self, "_denoise_checked", False):
+            missing = [s for s in DENOISE_SYMBOLS if not hasattr(self._lib, self._p + s)]
+            if missing:
+                raise EngineError(f"this library has no denoiser (lacks {[self._p + s for s in missing]})")
+            ver = getattr(self._lib, self._p + "denoise_api_version")
+            ver.restype = C.c_uint32
+            if ver() != HR_DENOISE_API_VERSION:
+                raise EngineError(f"{self._p}denoise_api_version() = {ver()}, this binding was written against {HR_DENOISE_API_VERSION}: rebuild the library")
+            self._denoise_checked = True
+        self._call(name, *args)
+
+    def denoise(self, params=None, with_passes=False):
+        """The denoised frame (H x W x 4 float32: rgb = mean colour, a = 1) of the passes rendered so far; needs both AOV masks enabled
+        before the frame's first pass.  params: a DenoiseParams (heatray_amd.denoise.default_params()), None = the defaults."""
+        p = f32p()
+        w, h, n = C.c_int32(), C.c_int32(), C.c_uint32()
+        self._denoise_call("denoise_readback", C.byref(params) if params is not None else None, C.byref(p), C.byref(w), C.byref(h), C.byref(n))
+        img = np.ctypeslib.as_array(p, shape=(h.value, w.value, 4)).copy()
+        return (img, int(n.value)) if with_passes else img
+
+    def denoise_to_device(self, device_ptr, params=None, stream=None):
+        """Asynchronous: the denoised frame (W x H float4) into device memory, e.g. a torch tensor; ordered like aov_to_device."""
+        self._denoise_call("denoise", C.byref(params) if params is not None else None, C.c_void_p(int(device_ptr)), C.c_void_p(stream or 0), None)
+
+    def denoise_display(self, device_ptr, display=None, fmt=HR_DISPLAY_RGBA8, params=None):
+        """Asynchronous display resolve of the denoised frame into device memory (like display_device)."""
+        display = display if display is not None else display_params()
+        self._denoise_call("denoise_display", C.byref(params) if params is not None else None, C.byref(display), C.c_int32(fmt),
+                           C.c_void_p(int(device_ptr)), None)
 
     def debug_trace(self, origins, dirs, tmax=None, skip_prim=None, any_hit=False):
         o, d = _f32(origins).reshape(-1, 3), _f32(dirs).reshape(-1, 3)

@@ -9,6 +9,7 @@
 //   hr_scene.inl      geometry ingest, commit (build / refit / tree cache), textures, materials, lights, sample tables
 //   hr_pipeline.inl   ray memory, the macro step, batching and the packet selector, hr_render_pass, the step log
 //   hr_group.inl      context groups (include/hrcore_group.h): member threads, the assembly of the members' tiles
+//   hr_aov.inl        the AOV planes (include/hrcore_aov.h);  hr_denoise.inl  the denoiser over them (include/hrcore_denoise.h)
 // (one translation unit: the .inl files are sections of this one, included below)
 #include "hr_ctx.h"
 
@@ -140,6 +141,9 @@ static void slotBudget(hr_ctx *c)
 static void aovFreePlanes(hr_ctx *c)
 {
     for (float *&p : c->aovPlane) hipFree(p), p = nullptr;
+    hipFree(c->dnWork), hipFree(c->dnOut); // (the denoiser's buffers live and die with the planes it reads)
+    if (c->dnPinned) hipHostFree(c->dnPinned);
+    c->dnWork = c->dnOut = c->dnPinned = nullptr, c->dnPinnedBytes = 0;
     if (c->aovPinned) hipHostFree(c->aovPinned);
     c->aovPinned = nullptr, c->aovPinnedBytes = 0;
 }
@@ -550,6 +554,7 @@ int hr_frame_resize(hr_ctx *c, int32_t w, int32_t h)
     const size_t fbBytes = (size_t)w * h * 4 * sizeof(float);
     HIP_TRY(c, hipMalloc(&c->fbInternal, fbBytes));
     HIP_TRY(c, hipMemsetAsync(c->fbInternal, 0, fbBytes, c->stream));
+    c->frameZeroedAt = c->nextResolveOrder;
     if (c->pinnedBytes < fbBytes) {
         if (c->pinned) hipHostFree(c->pinned);
         c->pinned = nullptr, c->pinnedBytes = 0;
@@ -703,3 +708,6 @@ int hr_debug_trace(hr_ctx *c, int32_t n, const float *o, const float *d, const f
 
 // ------------------------------------------------------------------------------------------ AOVs
 #include "hr_aov.inl"
+
+// ------------------------------------------------------------------------------------------ denoiser
+#include "hr_denoise.inl"

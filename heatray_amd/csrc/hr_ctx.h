@@ -436,6 +436,12 @@ struct hr_ctx {
     size_t aovPinnedBytes = 0;
     unsigned long long aovZeroedAt = 0;               // value of nextResolveOrder when the planes were last zeroed
     hipEvent_t evAov = nullptr;                       // orders hr_aov_copy on a foreign stream against the resolves
+    // Denoiser (include/hrcore_denoise.h): working planes and result image, allocated by the first call, freed with the AOV planes
+    unsigned long long frameZeroedAt = 0; // value of nextResolveOrder when the frame was last zeroed (hr_clear, hr_frame_resize): the planes hold the frame's passes when aovZeroedAt equals it
+    float *dnWork = nullptr;    // kDenoiseBytesPerPixel x W x H, cut into DenoiseBufs
+    float *dnOut = nullptr;     // the result when it does not go straight to the caller's memory (W x H float4)
+    float *dnPinned = nullptr;  // hr_denoise_readback's host buffer
+    size_t dnPinnedBytes = 0;
     size_t aovFramesPerSlot() const { return (aovMask & HR_AOV_SURFACE) ? 2 : 0; }
     // Context group (include/hrcore_group.h): non-null when this handle is a group.  Its own fields then describe the ASSEMBLED frame on the
     // group's first device (W, H, frame, fbInternal, the read-back buffers) and `stream` is the assembly stream; no pass pipeline runs on it.

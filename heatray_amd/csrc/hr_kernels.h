@@ -4,6 +4,7 @@
 #include "hr_types.h"
 #include "../../include/hrcore_group.h"
 #include "../../include/hrcore_aov.h"
+#include "../../include/hrcore_denoise.h"
 
 #include <cstddef>
 
@@ -171,6 +172,19 @@ void launchShade(const LaunchCfg &cfg, const SceneDev *S, const StepTable *tbl, 
 void launchDebugTrace(const LaunchCfg &cfg, const SceneDev *S, int n, const float *o, const float *d, const float *tmax, const int *skip,
                       int anyHit, hr_hit *out);
 size_t hitRecordSize();
+
+// ---- hr_denoise.hip (include/hrcore_denoise.h)
+// the working planes of the denoiser, W x H each: cv = demodulated colour + variance (ping-pong), nd = unit normal + depth,
+// ac = effective albedo + coverage (float4 each), grad = depth gradient (float)
+struct DenoiseBufs {
+    float *cv[2], *nd, *ac, *grad;
+};
+static const size_t kDenoiseBytesPerPixel = 4 * 16 + 4;
+void launchDenoisePrepare(hipStream_t st, int W, int H, const float *frame, const float *albedo, const float *normalDepth, const float *moments, const DenoiseBufs &b);
+// one iteration from cv[src] to cv[src ^ 1] or, with finalOut, to the remodulated image there; tiled: the LDS kernel where it exists for the step
+bool denoiseTiledHasStep(int step);
+void launchDenoiseAtrous(hipStream_t st, int W, int H, const DenoiseBufs &b, int src, int step, const hr_denoise_params &p, bool tiled, float *finalOut);
+void launchDenoiseFinish(hipStream_t st, int W, int H, const DenoiseBufs &b, float *out); // (no iteration: cv[0] remodulated)
 
 // ---- hr_build.hip
 // Per-geometry descriptor for the assemble kernel; all pointers are device pointers.  Attributes are addressed with a stride

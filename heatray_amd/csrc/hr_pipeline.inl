@@ -15,7 +15,7 @@ int hr_clear(hr_ctx *c)
     HIP_TRY(c, hipMemsetAsync(c->dStats, 0, sizeof(Stats) * kStatSlots, c->stream));
     for (float *plane : c->aovPlane)
         if (plane) HIP_TRY(c, hipMemsetAsync(plane, 0, (size_t)c->W * c->H * 4 * sizeof(float), c->stream));
-    c->resolvedAtClear = c->aovZeroedAt = c->nextResolveOrder;
+    c->resolvedAtClear = c->aovZeroedAt = c->frameZeroedAt = c->nextResolveOrder;
     c->snapshotEpoch++;
     if (getenv("HR_DEBUG_PIPE")) fprintf(stderr, "hr_clear %p: ray-memory growths so far %llu, waits %llu (%.2f ms)\n", (void *)c, c->dbgGrowths, c->dbgWaits, (double)c->dbgWaitNs * 1e-6);
     c->drainTimes();
