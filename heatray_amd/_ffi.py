@@ -192,6 +192,25 @@ class DenoiseParams(C.Structure):
                 ("kernel", C.c_int32), ("reserved", C.c_uint32 * 3)]
 
 
+# every symbol include/hrcore_adaptive.h declares (the sample mask and the error estimate that builds it).  Resolved lazily like the AOV symbols
+HR_ADAPTIVE_API_VERSION = 1
+HR_ADAPTIVE_MIN_SAMPLES_LOWEST, HR_ADAPTIVE_MIN_SAMPLES_HIGHEST, HR_ADAPTIVE_MAX_RADIUS = 2, 65536, 4
+ADAPTIVE_SYMBOLS = ["adaptive_api_version", "sample_mask_set", "sample_mask_get", "adaptive_default_params", "adaptive_update", "adaptive_error_copy", "adaptive_error_readback"]
+
+
+class AdaptiveParams(C.Structure):
+    """hr_adaptive_params"""
+    _fields_ = [("threshold", C.c_float), ("floor", C.c_float), ("min_samples", C.c_int32), ("radius", C.c_int32), ("reserved", C.c_uint32 * 4)]
+
+
+class AdaptiveResult(C.Structure):
+    """hr_adaptive_result"""
+    _fields_ = [("unconverged_pixels", C.c_uint64), ("active_pixels", C.c_uint64), ("max_error", C.c_float), ("passes", C.c_uint32)]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
 class GroupInfo(C.Structure):
     _fields_ = [("n_members", C.c_int32), ("device_ids", C.c_int32 * HR_GROUP_MAX_MEMBERS), ("owned_pixels", C.c_uint64 * HR_GROUP_MAX_MEMBERS)]
 
@@ -566,6 +585,56 @@ class Engine:
         display = display if display is not None else display_params()
         self._denoise_call("denoise_display", C.byref(params) if params is not None else None, C.byref(display), C.c_int32(fmt),
                            C.c_void_p(int(device_ptr)), None)
+
+    # -- adaptive sampling (include/hrcore_adaptive.h)
+    def _adaptive_call(self, name, *args):
+        if not getattr(self, "_adaptive_checked", False):
+            missing = [s for s in ADAPTIVE_SYMBOLS if not hasattr(self._lib, self._p + s)]
+            if missing:
+                raise EngineError(f"this library has no adaptive sampling (lacks {[self._p + s for s in missing]})")
+            ver = getattr(self._lib, self._p + "adaptive_api_version")
+            ver.restype = C.c_uint32
+            if ver() != HR_ADAPTIVE_API_VERSION:
+                raise EngineError(f"{self._p}adaptive_api_version() = {ver()}, this binding was written against {HR_ADAPTIVE_API_VERSION}: rebuild the library")
+            self._adaptive_checked = True
+        self._call(name, *args)
+
+    def set_sample_mask(self, mask):
+        """Install a sample mask (H x W, row 0 = bottom like the frame, non-zero = the pixel is sampled by the passes requested from now
+        on), or remove it with None.  Completes the enqueued passes first; clear() and resize() remove the mask too."""
+        if mask is None:
+            self._adaptive_call("sample_mask_set", None)
+            return
+        m = np.asarray(mask)
+        m = np.ascontiguousarray(m if m.dtype == np.uint8 else m != 0, dtype=np.uint8)  # (bytes go as they are: any non-zero value counts)
+        if m.shape != (self.height, self.width):
+            raise ValueError(f"sample mask of shape {m.shape} for a frame of {(self.height, self.width)}")
+        self._adaptive_call("sample_mask_set", m.ctypes.data_as(C.POINTER(C.c_uint8)))
+
+    def sample_mask(self):
+        """(the mask in force as H x W uint8 of 0 / 1, whether one is installed); all ones when there is none."""
+        out = np.empty((self.height, self.width), dtype=np.uint8)
+        inst = C.c_int32()
+        self._adaptive_call("sample_mask_get", out.ctypes.data_as(C.POINTER(C.c_uint8)), C.byref(inst))
+        return out, bool(inst.value)
+
+    def adaptive_update(self, params=None, install=True):
+        """Estimate every pixel's error from the frame and the MOMENTS plane (set_aovs(HR_AOV_MOMENTS) before the first pass), build the
+        sample mask from it and, with install, put it in force.  params: an AdaptiveParams (heatray_amd.adaptive.default_params()),
+        None = the defaults.  Returns the AdaptiveResult."""
+        r = AdaptiveResult()
+        self._adaptive_call("adaptive_update", C.byref(params) if params is not None else None, C.c_int32(int(bool(install))), C.byref(r))
+        return r
+
+    def adaptive_error_to_device(self, device_ptr, stream=None):
+        """Asynchronous copy of the last adaptive_update's error map (W x H floats) into device memory; ordered like aov_to_device."""
+        self._adaptive_call("adaptive_error_copy", C.c_void_p(int(device_ptr)), C.c_void_p(stream or 0))
+
+    def adaptive_error(self):
+        """The error map of the last adaptive_update as H x W float32 (+inf: fewer than min_samples samples)."""
+        out = np.empty((self.height, self.width), dtype=np.float32)
+        self._adaptive_call("adaptive_error_readback", _ptr(out))
+        return out
 
     def debug_trace(self, origins, dirs, tmax=None, skip_prim=None, any_hit=False):
         o, d = _f32(origins).reshape(-1, 3), _f32(dirs).reshape(-1, 3)

@@ -1,0 +1,230 @@
+// hr_adaptive.inl — a section of hr_core.hip (included at its end): the entry points of include/hrcore_adaptive.h.  The kernels are in
+// hr_adaptive.hip; cameraLane (hr_render.hip) reads the mask through FrameDev::mask.
+//
+// Ordering.  The mask words are rewritten in place on the context's stream after drainPipeline: every enqueued pass has been given its
+// resolve there by then, and a resolve waits for its pass's last stage, so the write comes after every ray generation that read the
+// old words; drainPipeline also makes each pipeline group's next step wait for the context's stream (needUserSync), so the next ray
+// generation comes after the write.  The calls below do wait for the stream — the caller's bytes are pageable host memory, an update's
+// result goes back to the host — but the mask's ordering against the passes does not rest on that.
+
+static int adaptiveCheckParams(hr_ctx *c, const hr_adaptive_params *in, hr_adaptive_params *p)
+{
+    if (in)
+        *p = *in;
+    else
+        hr_adaptive_default_params(p);
+    if (!std::isfinite(p->threshold) || !(p->threshold > 0.0f)) FAIL(c, HR_ERR_INVALID, "adaptive: threshold must be finite and greater than 0");
+    if (!std::isfinite(p->floor) || !(p->floor > 0.0f)) FAIL(c, HR_ERR_INVALID, "adaptive: floor must be finite and greater than 0");
+    if (p->min_samples < HR_ADAPTIVE_MIN_SAMPLES_LOWEST || p->min_samples > HR_ADAPTIVE_MIN_SAMPLES_HIGHEST)
+        FAIL(c, HR_ERR_INVALID, "adaptive: min_samples = " + std::to_string(p->min_samples) + " is outside " + std::to_string(HR_ADAPTIVE_MIN_SAMPLES_LOWEST) + " .. " +
+                                    std::to_string(HR_ADAPTIVE_MIN_SAMPLES_HIGHEST));
+    if (p->radius < 0 || p->radius > HR_ADAPTIVE_MAX_RADIUS)
+        FAIL(c, HR_ERR_INVALID, "adaptive: radius = " + std::to_string(p->radius) + " is outside 0 .. " + std::to_string(HR_ADAPTIVE_MAX_RADIUS));
+    return HR_OK;
+}
+
+// MOMENTS on, and zeroed when the frame was: the plane holds the frame's passes
+static int adaptiveCheckPlane(hr_ctx *c)
+{
+    if (!(c->aovMask & HR_AOV_MOMENTS))
+        FAIL(c, HR_ERR_INVALID, "adaptive sampling needs the sample moments: hr_aov_enable(HR_AOV_MOMENTS) before the frame's first pass (enabled mask: " +
+                                    std::to_string(c->aovMask) + ")");
+    if (c->aovZeroedAt != c->frameZeroedAt)
+        FAIL(c, HR_ERR_INVALID, "adaptive: the MOMENTS plane was enabled after the frame's first pass and does not hold the frame's passes: hr_clear, or hr_aov_enable before rendering");
+    return HR_OK;
+}
+
+static int sampleMaskEnsure(hr_ctx *c, bool bytesToo)
+{
+    if (!c->smWords) HIP_TRY(c, hipMalloc((void **)&c->smWords, sampleMaskWords(c->W, c->H) * 4));
+    if (bytesToo && !c->smBytes) HIP_TRY(c, hipMalloc((void **)&c->smBytes, (size_t)c->W * c->H));
+    return HR_OK;
+}
+
+// a plain context: the byte mask (host memory) -> its words, installed; null removes the mask
+static int sampleMaskSetPlain(hr_ctx *c, const uint8_t *mask)
+{
+    if (c->W <= 0) FAIL(c, HR_ERR_INVALID, "no frame");
+    int rc = drainPipeline(c);
+    if (rc) return rc;
+    if (!mask) {
+        c->frame.mask = nullptr;
+        return HR_OK;
+    }
+    rc = sampleMaskEnsure(c, true);
+    if (rc) return rc;
+    HIP_TRY(c, hipMemcpyAsync(c->smBytes, mask, (size_t)c->W * c->H, hipMemcpyHostToDevice, c->stream));
+    launchMaskPack(c->stream, c->W, c->H, c->smBytes, c->smWords);
+    HIP_TRY(c, hipGetLastError());
+    HIP_TRY(c, hipStreamSynchronize(c->stream)); // (the caller's bytes are pageable host memory: read before the call returns)
+    c->frame.mask = c->smWords;
+    return HR_OK;
+}
+
+// a context group: the words on the group's first device (complete: its stream was synchronised) -> every member, installed there
+static int groupSampleMaskDistribute(hr_ctx *c)
+{
+    const uint32_t *src = c->smWords;
+    const int dev0 = c->device;
+    const size_t bytes = sampleMaskWords(c->W, c->H) * 4;
+    return groupAll(c, [=](hr_ctx *m, int) {
+        int rc = drainPipeline(m);
+        if (rc == HR_OK) rc = sampleMaskEnsure(m, false);
+        if (rc) return rc;
+        HIP_TRY(m, hipMemcpyPeerAsync(m->smWords, m->device, src, dev0, bytes, m->stream));
+        HIP_TRY(m, hipStreamSynchronize(m->stream)); // (the source is the group's buffer, which its next call may rewrite)
+        m->frame.mask = m->smWords;
+        return HR_OK;
+    });
+}
+
+static int groupSampleMaskSet(hr_ctx *c, const uint8_t *mask)
+{
+    if (c->W <= 0) FAIL(c, HR_ERR_INVALID, "no frame");
+    if (!mask) {
+        const int rc = groupAll(c, [](hr_ctx *m, int) { return sampleMaskSetPlain(m, nullptr); });
+        if (rc) return rc;
+        c->frame.mask = nullptr;
+        return HR_OK;
+    }
+    int rc = sampleMaskEnsure(c, true);
+    if (rc) return rc;
+    HIP_TRY(c, hipMemcpyAsync(c->smBytes, mask, (size_t)c->W * c->H, hipMemcpyHostToDevice, c->stream));
+    launchMaskPack(c->stream, c->W, c->H, c->smBytes, c->smWords);
+    HIP_TRY(c, hipGetLastError());
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    rc = groupSampleMaskDistribute(c);
+    if (rc) return rc;
+    c->frame.mask = c->smWords;
+    return HR_OK;
+}
+
+extern "C" {
+
+uint32_t hr_adaptive_api_version(void) { return HR_ADAPTIVE_API_VERSION; }
+
+void hr_adaptive_default_params(hr_adaptive_params *p)
+{
+    if (!p) return;
+    *p = hr_adaptive_params{};
+    p->threshold = 0.02f, p->floor = 0.05f, p->min_samples = 16, p->radius = 2;
+}
+
+int hr_sample_mask_set(hr_ctx *c, const uint8_t *mask)
+{
+    ENTER(c);
+    return c->grp ? groupSampleMaskSet(c, mask) : sampleMaskSetPlain(c, mask);
+}
+
+int hr_sample_mask_get(hr_ctx *c, uint8_t *out, int32_t *installed)
+{
+    ENTER(c);
+    if (!out) FAIL(c, HR_ERR_INVALID, "null output");
+    if (c->W <= 0) FAIL(c, HR_ERR_INVALID, "no frame");
+    if (installed) *installed = c->frame.mask ? 1 : 0;
+    const size_t px = (size_t)c->W * c->H;
+    if (!c->frame.mask) {
+        std::memset(out, 1, px);
+        return HR_OK;
+    }
+    const int rc = sampleMaskEnsure(c, true);
+    if (rc) return rc;
+    launchMaskUnpack(c->stream, c->W, c->H, c->frame.mask, c->smBytes); // (a group's handle holds the copy its members were sent)
+    HIP_TRY(c, hipGetLastError());
+    HIP_TRY(c, hipMemcpyAsync(out, c->smBytes, px, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    return HR_OK;
+}
+
+int hr_adaptive_update(hr_ctx *c, const hr_adaptive_params *params, int32_t install, hr_adaptive_result *out)
+{
+    ENTER(c);
+    hr_adaptive_params p;
+    int rc = adaptiveCheckParams(c, params, &p);
+    if (rc) return rc;
+    if (c->W <= 0) FAIL(c, HR_ERR_INVALID, "no frame");
+    uint32_t n = 0;
+    const float *frame = nullptr;
+    if (c->grp) {
+        rc = adaptiveCheckPlane(c); // (the group's own mask: hr_aov_enable on the handle)
+        if (rc == HR_OK) rc = groupAll(c, [](hr_ctx *m, int) { return adaptiveCheckPlane(m); });
+        if (rc == HR_OK) rc = groupAssemble(c, true, &n, nullptr);
+        if (rc == HR_OK) rc = groupAovAssemble(c, HR_AOV_PLANE_MOMENTS, nullptr);
+        if (rc) return rc;
+        frame = c->fbInternal;
+    } else {
+        if (c->world > 1)
+            FAIL(c, HR_ERR_INVALID, "adaptive: a tile-sharded context (world > 1) holds only its own tiles and the mask's dilation reads across them: use a context group, which assembles the frame");
+        rc = adaptiveCheckPlane(c);
+        if (rc == HR_OK) rc = drainPipeline(c);
+        if (rc == HR_OK) rc = overflowCheck(c);
+        if (rc) return rc;
+        n = (uint32_t)(c->nextResolveOrder - c->frameZeroedAt);
+        frame = c->fb();
+    }
+    const size_t px = (size_t)c->W * c->H, maskBytes = sampleMaskWords(c->W, c->H) * 4;
+    if (!c->adError) HIP_TRY(c, hipMalloc((void **)&c->adError, px * 4));
+    if (!c->adWords) HIP_TRY(c, hipMalloc((void **)&c->adWords, maskBytes));
+    if (!c->adResult) HIP_TRY(c, hipMalloc((void **)&c->adResult, kAdaptiveResultWords * 4));
+    if (!c->adResultHost) HIP_TRY(c, hipHostMalloc((void **)&c->adResultHost, kAdaptiveResultWords * 4, hipHostMallocDefault));
+    if (install) {
+        rc = sampleMaskEnsure(c, false);
+        if (rc) return rc;
+    }
+    HIP_TRY(c, hipMemsetAsync(c->adResult, 0, kAdaptiveResultWords * 4, c->stream));
+    launchAdaptiveError(c->stream, c->W, c->H, frame, c->aovPlane[HR_AOV_PLANE_MOMENTS], p, c->adError);
+    launchAdaptiveMask(c->stream, c->W, c->H, c->adError, p, c->adWords, c->adResult);
+    HIP_TRY(c, hipGetLastError());
+    c->adErrorValid = true;
+    if (install) HIP_TRY(c, hipMemcpyAsync(c->smWords, c->adWords, maskBytes, hipMemcpyDeviceToDevice, c->stream));
+    HIP_TRY(c, hipMemcpyAsync(c->adResultHost, c->adResult, kAdaptiveResultWords * 4, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    if (install) {
+        if (c->grp) {
+            rc = groupSampleMaskDistribute(c);
+            if (rc) return rc;
+        }
+        c->frame.mask = c->smWords;
+    }
+    if (out) {
+        *out = hr_adaptive_result{};
+        out->unconverged_pixels = c->adResultHost[0], out->active_pixels = c->adResultHost[1];
+        std::memcpy(&out->max_error, &c->adResultHost[2], 4);
+        out->passes = n;
+    }
+    return HR_OK;
+}
+
+int hr_adaptive_error_copy(hr_ctx *c, void *device_out, void *stream)
+{
+    ENTER(c);
+    if (!device_out) FAIL(c, HR_ERR_INVALID, "null output");
+    if (c->W <= 0) FAIL(c, HR_ERR_INVALID, "no frame");
+    if (!c->adErrorValid) FAIL(c, HR_ERR_INVALID, "adaptive: no error map: hr_adaptive_update has not run since the frame was last resized");
+    const size_t bytes = (size_t)c->W * c->H * sizeof(float);
+    hipStream_t st = stream ? (hipStream_t)stream : c->stream;
+    if (st != c->stream) {
+        if (!c->evAov) HIP_TRY(c, hipEventCreateWithFlags(&c->evAov, hipEventDisableTiming));
+        HIP_TRY(c, hipEventRecord(c->evAov, c->stream));
+        HIP_TRY(c, hipStreamWaitEvent(st, c->evAov, 0));
+    }
+    HIP_TRY(c, hipMemcpyAsync(device_out, c->adError, bytes, hipMemcpyDeviceToDevice, st));
+    if (st != c->stream) { // the next update rewrites the map: behind the copy
+        HIP_TRY(c, hipEventRecord(c->evAov, st));
+        HIP_TRY(c, hipStreamWaitEvent(c->stream, c->evAov, 0));
+    }
+    return HR_OK;
+}
+
+int hr_adaptive_error_readback(hr_ctx *c, float *host_out)
+{
+    ENTER(c);
+    if (!host_out) FAIL(c, HR_ERR_INVALID, "null output");
+    if (c->W <= 0) FAIL(c, HR_ERR_INVALID, "no frame");
+    if (!c->adErrorValid) FAIL(c, HR_ERR_INVALID, "adaptive: no error map: hr_adaptive_update has not run since the frame was last resized");
+    HIP_TRY(c, hipMemcpyAsync(host_out, c->adError, (size_t)c->W * c->H * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    return HR_OK;
+}
+
+} // extern "C"

@@ -10,6 +10,7 @@
 //   hr_pipeline.inl   ray memory, the macro step, batching and the packet selector, hr_render_pass, the step log
 //   hr_group.inl      context groups (include/hrcore_group.h): member threads, the assembly of the members' tiles
 //   hr_aov.inl        the AOV planes (include/hrcore_aov.h);  hr_denoise.inl  the denoiser over them (include/hrcore_denoise.h)
+//   hr_adaptive.inl   the sample mask and the error estimate that builds it (include/hrcore_adaptive.h)
 // (one translation unit: the .inl files are sections of this one, included below)
 #include "hr_ctx.h"
 
@@ -166,6 +167,16 @@ static int aovAllocPlanes(hr_ctx *c)
         HIP_TRY(c, hipMemsetAsync(c->aovPlane[p], 0, bytes, c->stream));
     }
     return HR_OK;
+}
+
+// Adaptive sampling (include/hrcore_adaptive.h): the mask and the update's buffers live and die with the frame's size
+static void adaptiveFree(hr_ctx *c)
+{
+    hipFree(c->smWords), hipFree(c->smBytes), hipFree(c->adError), hipFree(c->adWords), hipFree(c->adResult);
+    if (c->adResultHost) hipHostFree(c->adResultHost);
+    c->smWords = c->adWords = c->adResult = c->adResultHost = nullptr, c->smBytes = nullptr, c->adError = nullptr;
+    c->adErrorValid = false;
+    c->frame.mask = nullptr;
 }
 
 static void freeTree(hr_ctx *c)
@@ -346,6 +357,7 @@ int hr_ctx_destroy(hr_ctx *c)
     if (c->pinned) hipHostFree(c->pinned);
     hipFree(c->dDisplay);
     aovFree(c);
+    adaptiveFree(c);
     c->meshReleaseAll();
     for (int k = 0; k < 2; ++k) {
         if (c->stage[k]) hipHostFree(c->stage[k]);
@@ -551,6 +563,7 @@ int hr_frame_resize(hr_ctx *c, int32_t w, int32_t h)
     hipFree(c->fbInternal);
     c->fbInternal = nullptr;
     c->fbExternal = nullptr;
+    adaptiveFree(c); // (the sample mask goes with the frame it was made for)
     const size_t fbBytes = (size_t)w * h * 4 * sizeof(float);
     HIP_TRY(c, hipMalloc(&c->fbInternal, fbBytes));
     HIP_TRY(c, hipMemsetAsync(c->fbInternal, 0, fbBytes, c->stream));
@@ -711,3 +724,6 @@ int hr_debug_trace(hr_ctx *c, int32_t n, const float *o, const float *d, const f
 
 // ------------------------------------------------------------------------------------------ denoiser
 #include "hr_denoise.inl"
+
+// ------------------------------------------------------------------------------------------ adaptive sampling
+#include "hr_adaptive.inl"

@@ -442,6 +442,15 @@ struct hr_ctx {
     float *dnOut = nullptr;     // the result when it does not go straight to the caller's memory (W x H float4)
     float *dnPinned = nullptr;  // hr_denoise_readback's host buffer
     size_t dnPinnedBytes = 0;
+    // Adaptive sampling (include/hrcore_adaptive.h).  frame.mask is smWords while a mask is installed, null otherwise.  The buffers are made
+    // by the first call that needs them and go with the frame (adaptiveFree: hr_frame_resize, hr_ctx_destroy).
+    uint32_t *smWords = nullptr;  // the installed mask's words (sampleMaskWords)
+    uint8_t *smBytes = nullptr;   // W x H bytes: staging of the byte form (hr_sample_mask_set / _get)
+    float *adError = nullptr;     // W x H floats: the error map of the last hr_adaptive_update
+    uint32_t *adWords = nullptr;  // the mask that update built (copied to smWords when it is installed)
+    uint32_t *adResult = nullptr; // kAdaptiveResultWords device words ...
+    uint32_t *adResultHost = nullptr; // ... and their pinned host copy
+    bool adErrorValid = false;    // adError holds an update's map at this frame size
     size_t aovFramesPerSlot() const { return (aovMask & HR_AOV_SURFACE) ? 2 : 0; }
     // Context group (include/hrcore_group.h): non-null when this handle is a group.  Its own fields then describe the ASSEMBLED frame on the
     // group's first device (W, H, frame, fbInternal, the read-back buffers) and `stream` is the assembly stream; no pass pipeline runs on it.

@@ -186,6 +186,7 @@ static int groupDestroy(hr_ctx *c)
     hipFree(c->dDisplay);
     if (c->pinnedDisplay) hipHostFree(c->pinnedDisplay);
     aovFree(c);
+    adaptiveFree(c);
     delete g;
     delete c;
     return HR_OK;
@@ -225,6 +226,7 @@ static int groupResize(hr_ctx *c, int32_t w, int32_t h)
     freeLagged(c->progFrame), freeLagged(c->progDisplay);
     hipFree(c->fbInternal);
     c->fbInternal = nullptr;
+    adaptiveFree(c); // (the group's copy of the sample mask; the members' went with their frames)
     const size_t fbBytes = (size_t)w * h * 4 * sizeof(float);
     HIP_TRY(c, hipMalloc(&c->fbInternal, fbBytes));
     HIP_TRY(c, hipMemsetAsync(c->fbInternal, 0, fbBytes, c->stream));
@@ -430,6 +432,7 @@ static int groupClear(hr_ctx *c)
     const int rc = groupAll(c, [](hr_ctx *m, int) { return hr_clear(m); });
     if (rc) return rc;
     HIP_TRY(c, hipMemsetAsync(c->fbInternal, 0, (size_t)c->W * c->H * 4 * sizeof(float), c->stream));
+    c->frame.mask = nullptr; // (hr_clear has removed the members' sample masks)
     c->snapshotEpoch++;
     return HR_OK;
 }

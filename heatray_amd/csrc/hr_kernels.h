@@ -5,6 +5,7 @@
 #include "../../include/hrcore_group.h"
 #include "../../include/hrcore_aov.h"
 #include "../../include/hrcore_denoise.h"
+#include "../../include/hrcore_adaptive.h"
 
 #include <cstddef>
 
@@ -14,6 +15,7 @@ struct FrameDev {
     float *fb; // RGBA32F accumulation buffer, row 0 = bottom
     int32_t W, H;
     int32_t rank, world, tile, tilesX, tilesY, nOwnedTiles;
+    const uint32_t *mask; // the sample mask in force (include/hrcore_adaptive.h): row-major words, (W + 31) / 32 per row, bit (x & 31) of word (x >> 5) = pixel x; null: every pixel is sampled
 };
 
 struct HitRec; // hr_trace.h
@@ -185,6 +187,15 @@ void launchDenoisePrepare(hipStream_t st, int W, int H, const float *frame, cons
 bool denoiseTiledHasStep(int step);
 void launchDenoiseAtrous(hipStream_t st, int W, int H, const DenoiseBufs &b, int src, int step, const hr_denoise_params &p, bool tiled, float *finalOut);
 void launchDenoiseFinish(hipStream_t st, int W, int H, const DenoiseBufs &b, float *out); // (no iteration: cv[0] remodulated)
+
+// ---- hr_adaptive.hip (include/hrcore_adaptive.h)
+size_t sampleMaskWords(int W, int H); // 32-bit words of a frame's sample mask (FrameDev::mask)
+void launchAdaptiveError(hipStream_t st, int W, int H, const float *frame, const float *moments, const hr_adaptive_params &p, float *err);
+// err -> the mask words and result = {unconverged pixels, active pixels, bits of the largest finite error, unused} (four words, zeroed by the caller)
+static const size_t kAdaptiveResultWords = 4;
+void launchAdaptiveMask(hipStream_t st, int W, int H, const float *err, const hr_adaptive_params &p, uint32_t *words, uint32_t *result);
+void launchMaskPack(hipStream_t st, int W, int H, const uint8_t *bytes, uint32_t *words);   // W x H bytes (non-zero = sampled) -> words
+void launchMaskUnpack(hipStream_t st, int W, int H, const uint32_t *words, uint8_t *bytes); // words -> W x H bytes, 0 / 1
 
 // ---- hr_build.hip
 // Per-geometry descriptor for the assemble kernel; all pointers are device pointers.  Attributes are addressed with a stride

@@ -16,6 +16,7 @@ int hr_clear(hr_ctx *c)
     for (float *plane : c->aovPlane)
         if (plane) HIP_TRY(c, hipMemsetAsync(plane, 0, (size_t)c->W * c->H * 4 * sizeof(float), c->stream));
     c->resolvedAtClear = c->aovZeroedAt = c->frameZeroedAt = c->nextResolveOrder;
+    c->frame.mask = nullptr; // (include/hrcore_adaptive.h: a new frame starts without a sample mask)
     c->snapshotEpoch++;
     if (getenv("HR_DEBUG_PIPE")) fprintf(stderr, "hr_clear %p: ray-memory growths so far %llu, waits %llu (%.2f ms)\n", (void *)c, c->dbgGrowths, c->dbgWaits, (double)c->dbgWaitNs * 1e-6);
     c->drainTimes();

@@ -152,7 +152,7 @@ HRD bool ownedPixel(const FrameDev &fr, uint32_t gid, int &x, int &y)
 struct CameraLane {
     Ray r;
     uint32_t pixel;
-    bool active;  // the pixel is sampled this pass
+    bool active;  // the pixel is sampled this pass: in the frame, its bit of the sample mask set (where one is installed), and the pass's own choice (interactive mode's blocks)
     bool enqueue; // ... and its ray has to be traced
     uint32_t nAcc;
 };
@@ -161,6 +161,7 @@ HRD void cameraLane(const SceneDev &S, const hr_pass_params &pp, const SegDev &s
     c.pixel = (uint32_t)(y * fr.W + x);
     c.r.valid = false;
     c.active = inFrame;
+    if (fr.mask && inFrame) c.active = ((G(fr.mask)[y * ((fr.W + 31) >> 5) + (x >> 5)] >> (x & 31)) & 1u) != 0u; // the sample mask (include/hrcore_adaptive.h)
     if (c.active) c.active = generatePrimary(S, pp, fr.W, fr.H, x, y, c.r);
     if (inFrame) G(reinterpret_cast<float4 *>(seg.passbuf))[c.pixel] = make_float4(0.0f, 0.0f, 0.0f, c.active ? 1.0f : 0.0f);
     if (inFrame && seg.passbufB) { // HR_ESTIMATOR_ALL_LIGHTS: three more partial sums behind the first

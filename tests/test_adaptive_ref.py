@@ -1,0 +1,225 @@
+"""The arithmetic of adaptive sampling without a GPU: heatray_amd/csrc/hr_adaptive.h compiled for the CPU (tests/host/adaptive_cpu.cpp)
+against its numpy restatement heatray_amd.adaptive.reference_error / reference_mask, bit for bit, on random and on hand-made inputs whose
+answers are known (include/hrcore_adaptive.h is the contract).  tests/test_gpu_adaptive.py holds the device to the same reference."""
+import os
+import subprocess
+
+import numpy as np
+import pytest
+
+from heatray_amd import adaptive
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+F = np.float32
+
+
+def params(threshold=0.02, floor=0.05, min_samples=16, radius=2):
+    p = adaptive.default_params()
+    p.threshold, p.floor, p.min_samples, p.radius = threshold, floor, min_samples, radius
+    return p
+
+
+@pytest.fixture(scope="module")
+def cpu(tmp_path_factory):
+    d = tmp_path_factory.mktemp("adaptive_cpu")
+    exe = d / "adaptive_cpu"
+    # -ffp-contract=off like the library: the header's float lines must mean the same on both sides
+    subprocess.check_call(["g++", "-std=c++17", "-O1", "-ffp-contract=off", "-Wall", "-I" + os.path.join(ROOT, "heatray_amd", "csrc"),
+                           os.path.join(ROOT, "tests", "host", "adaptive_cpu.cpp"), "-o", str(exe)])
+
+    def run(frame, moments, p):
+        H, W = frame.shape[:2]
+        with open(d / "in.bin", "wb") as f:
+            f.write(np.array([W, H, p.min_samples, p.radius], np.int32).tobytes())
+            f.write(np.array([p.threshold, p.floor], F).tobytes())
+            f.write(np.ascontiguousarray(frame, F).tobytes())
+            f.write(np.ascontiguousarray(moments, F).tobytes())
+        out = subprocess.run([str(exe), str(d / "in.bin"), str(d / "out.bin")], capture_output=True, text=True)
+        assert out.returncode == 0 and "adaptive cpu: ok" in out.stdout, (out.returncode, out.stderr)
+        raw = open(d / "out.bin", "rb").read()
+        n = W * H
+        err = np.frombuffer(raw[:4 * n], F).reshape(H, W)
+        mask = np.frombuffer(raw[4 * n:5 * n], np.uint8).reshape(H, W)
+        unc, act = np.frombuffer(raw[5 * n:5 * n + 16], np.uint64)
+        mx = np.frombuffer(raw[5 * n + 16:5 * n + 20], F)[0]
+        return err, mask, {"unconverged_pixels": int(unc), "active_pixels": int(act), "max_error": float(mx)}
+    return run
+
+
+def synthetic(W, H, seed, max_n=40, holes=True):
+    """A frame and its MOMENTS as a renderer with a per-pixel sample count would leave them: per pixel n samples around a mean, a
+    constant strip (variance exactly 0), a dark strip (luminance below the floor), pixels without samples."""
+    rng = np.random.default_rng(seed)
+    n = rng.integers(0 if holes else 1, max_n + 1, (H, W))
+    frame, mom = np.zeros((H, W, 4), F), np.zeros((H, W, 4), F)
+    y, x = np.mgrid[0:H, 0:W]
+    mean = (F(0.02) + F(1.5) * rng.random((H, W, 3))).astype(F)
+    mean[:, : max(1, W // 6)] *= F(0.01)                       # dark: lum(c) below the floor
+    sigma = (rng.random((H, W, 1)) ** 3).astype(F)              # most pixels quiet, some noisy
+    sigma[y % 7 == 0] = 0                                       # rows of identical samples
+    for k in range(max_n):
+        s = np.abs(mean * (F(1) + sigma * rng.standard_normal((H, W, 3)).astype(F))).astype(F)
+        on = (k < n)[..., None]
+        frame[..., :3] += np.where(on, s, F(0))
+        frame[..., 3] += on[..., 0]
+        mom[..., :3] += np.where(on, s * s, F(0))
+        mom[..., 3] += on[..., 0]
+    return frame, mom
+
+
+def _same_bits(got, want, what):
+    g, w = np.ascontiguousarray(got), np.ascontiguousarray(want)
+    assert g.shape == w.shape and g.dtype == w.dtype, what
+    if g.tobytes() != w.tobytes():
+        bad = np.argwhere(g.view(np.uint32 if g.dtype == F else g.dtype) != w.view(np.uint32 if w.dtype == F else w.dtype))
+        raise AssertionError(f"{what}: {len(bad)} pixels differ, first at (y, x) = {tuple(bad[0])}: {g[tuple(bad[0])]} against {w[tuple(bad[0])]}")
+
+
+def _check(cpu, frame, mom, p, what):
+    err = adaptive.reference_error(frame, mom, p)
+    mask = adaptive.reference_mask(err, p)
+    res = adaptive.reference_result(err, p)
+    cerr, cmask, cres = cpu(frame, mom, p)
+    _same_bits(cerr, err, what + ": error map")
+    _same_bits(cmask, mask, what + ": mask")
+    assert cres["unconverged_pixels"] == res["unconverged_pixels"] and cres["active_pixels"] == res["active_pixels"], (what, cres, res)
+    assert F(cres["max_error"]).tobytes() == F(res["max_error"]).tobytes(), (what, cres, res)
+    return err, mask, res
+
+
+CASES = [
+    # (W, H, seed, threshold, floor, min_samples, radius)
+    (67, 41, 1, 0.02, 0.05, 16, 2),
+    (67, 41, 2, 0.2, 0.05, 16, 2),
+    (131, 19, 3, 0.05, 0.5, 2, 1),
+    (1, 1, 4, 0.02, 0.05, 16, 4),
+    (5, 300, 5, 0.1, 0.01, 30, 3),
+    (64, 16, 6, 0.02, 0.05, 16, 4),
+] + [(70, 37, 10 + r, 0.15, 0.05, 8, r) for r in range(5)]  # every radius at a size that is no multiple of the 64 x 16 tile
+
+
+@pytest.mark.parametrize("case", CASES, ids=lambda c: "-".join(str(v) for v in c))
+def test_cpu_header_equals_numpy_reference_bit_for_bit(cpu, case):
+    W, H, seed, thr, floor, ms, radius = case
+    frame, mom = synthetic(W, H, seed)
+    p = params(thr, floor, ms, radius)
+    err, mask, res = _check(cpu, frame, mom, p, f"case {case}")
+    if W * H > 100:  # the inputs exercise both answers
+        assert 0 < res["unconverged_pixels"] < W * H, res
+
+
+def _pixel(n, samples):
+    """the frame and MOMENTS value of one pixel that has seen `samples` (n of them, rgb each)"""
+    s = np.asarray(samples, F).reshape(n, 3) if n else np.zeros((0, 3), F)
+    f, m = np.zeros(4, F), np.zeros(4, F)
+    for v in s:
+        f[:3] += v
+        f[3] += F(1)
+        m[:3] += v * v
+        m[3] += F(1)
+    return f, m
+
+
+def test_sample_count_boundaries(cpu):
+    ms = 16
+    noisy = lambda n: [(0.5 + 0.4 * (-1) ** k, 0.5, 0.5 - 0.3 * (-1) ** k) for k in range(n)]
+    px = [_pixel(0, []), _pixel(1, noisy(1)), _pixel(ms - 1, noisy(ms - 1)), _pixel(ms, noisy(ms)), _pixel(ms + 1, noisy(ms + 1))]
+    frame = np.stack([f for f, _ in px])[None]
+    mom = np.stack([m for _, m in px])[None]
+    p = params(min_samples=ms, radius=0)
+    err, mask, res = _check(cpu, frame, mom, p, "sample counts")
+    assert np.isposinf(err[0, :3]).all()                     # n = 0, n = 1, n = min_samples - 1: never converged
+    assert np.isfinite(err[0, 3:]).all() and (err[0, 3:] > 0).all()
+    assert mask[0, :3].tolist() == [1, 1, 1]
+    assert res["max_error"] == float(err[0, 3:].max())
+    # by hand, in float32, for n = min_samples
+    f, m = px[3]
+    n = f[3]
+    c = f[:3] / n
+    e = np.maximum(m[:3] - (n * c) * c, F(0))
+    vc = (e / (n - F(1))) / n
+    v = (F(0.2126) * vc[0] + F(0.7152) * vc[1]) + F(0.0722) * vc[2]
+    l = (F(0.2126) * c[0] + F(0.7152) * c[1]) + F(0.0722) * c[2]
+    assert err[0, 3].tobytes() == (np.sqrt(v) / max(l, F(0.05))).astype(F).tobytes()
+
+
+def test_zero_variance_is_exactly_zero_and_converged(cpu):
+    H, W = 9, 13
+    frame, mom = np.zeros((H, W, 4), F), np.zeros((H, W, 4), F)
+    for _ in range(32):  # 32 identical samples of 0.75 0.5 0.25: every sum is exact
+        frame += F([0.75, 0.5, 0.25, 1.0])
+        mom += F([0.5625, 0.25, 0.0625, 1.0])
+    p = params()
+    err, mask, res = _check(cpu, frame, mom, p, "zero variance")
+    assert (err == 0).all() and not mask.any()
+    assert res == {"unconverged_pixels": 0, "active_pixels": 0, "max_error": 0.0, "passes": 0}
+
+
+def test_negative_e_is_clamped(cpu):
+    frame = np.tile(F([16.0, 16.0, 16.0, 16.0]), (3, 4, 1))     # mean 1
+    mom = np.tile(F([8.0, 8.0, 8.0, 16.0]), (3, 4, 1))          # MOMENTS below n c^2: e = -8 -> 0
+    err, mask, _ = _check(cpu, frame, mom, params(), "negative e")
+    assert (err == 0).all() and not mask.any()
+
+
+def test_luminance_below_the_floor_is_an_absolute_error(cpu):
+    n = 16
+    dark = [(0.001 * (1 + (k & 1)), 0.001, 0.001) for k in range(n)]
+    f, m = _pixel(n, dark)
+    frame, mom = f[None, None], m[None, None]
+    for floor in (0.05, 0.5):
+        p = params(floor=floor, radius=0)
+        err, _, _ = _check(cpu, frame, mom, p, f"floor {floor}")
+        c = f[:3] / f[3]
+        lum = (F(0.2126) * c[0] + F(0.7152) * c[1]) + F(0.0722) * c[2]
+        assert lum < floor
+    e_small = adaptive.reference_error(frame, mom, params(floor=0.05))[0, 0]
+    e_big = adaptive.reference_error(frame, mom, params(floor=0.5))[0, 0]
+    assert e_small > 0 and abs(e_small / e_big - 10.0) < 1e-5   # divided by the floor, not by the luminance
+
+
+def test_radius_zero_leaves_the_unconverged_map(cpu):
+    frame, mom = synthetic(45, 30, 21)
+    p = params(threshold=0.1, radius=0)
+    err, mask, res = _check(cpu, frame, mom, p, "radius 0")
+    assert (mask.astype(bool) == adaptive.unconverged(err, p)).all()
+    assert res["active_pixels"] == res["unconverged_pixels"]
+
+
+@pytest.mark.parametrize("radius", range(5))
+@pytest.mark.parametrize("corner", [(0, 0), (0, 1), (1, 0), (1, 1)])
+def test_one_unconverged_pixel_in_a_corner_sets_the_clipped_square(cpu, radius, corner):
+    H, W = 23, 77
+    frame, mom = np.zeros((H, W, 4), F), np.zeros((H, W, 4), F)
+    for _ in range(16):
+        frame += F([0.5, 0.5, 0.5, 1.0])
+        mom += F([0.25, 0.25, 0.25, 1.0])
+    y, x = corner[0] * (H - 1), corner[1] * (W - 1)
+    mom[y, x, :3] = F(40.0)  # that pixel alone has a variance
+    p = params(radius=radius)
+    err, mask, res = _check(cpu, frame, mom, p, f"corner {corner} radius {radius}")
+    want = np.zeros((H, W), np.uint8)
+    want[max(0, y - radius):y + radius + 1, max(0, x - radius):x + radius + 1] = 1
+    assert (mask == want).all()
+    assert res["unconverged_pixels"] == 1 and res["active_pixels"] == (radius + 1) ** 2
+
+
+def test_nan_and_inf_frames_do_not_count_as_unconverged_or_as_the_maximum(cpu):
+    frame, mom = synthetic(20, 10, 31, holes=False)
+    frame[..., 3] = np.maximum(frame[..., 3], F(16))
+    frame[2, 3, :3] = F(np.inf)
+    mom[2, 3, :3] = F(np.inf)
+    frame[4, 5, 0] = F(np.nan)
+    err, mask, res = _check(cpu, frame, mom, params(radius=0), "nan / inf")
+    # inf: e = inf - inf * inf is NaN, which the clamp turns into 0, over a luminance of inf: the error is 0.  NaN: the luminance is NaN
+    # and fmax_ hands it through: the error is NaN, which is not greater than any threshold
+    assert err[2, 3] == 0 and np.isnan(err[4, 5])
+    assert mask[2, 3] == 0 and mask[4, 5] == 0
+    assert np.isfinite(res["max_error"])
+
+
+def test_default_params_are_the_documented_ones():
+    from heatray_amd import convergence
+    p = adaptive.default_params()
+    assert (p.threshold, p.floor, p.min_samples, p.radius) == (F(0.02), F(0.05), 16, 2)
+    assert F(p.threshold) == F(convergence.THRESHOLD)
