@@ -211,6 +211,26 @@ class AdaptiveResult(C.Structure):
         return {k: getattr(self, k) for k, _ in self._fields_}
 
 
+# every symbol include/hrcore_history.h declares (history reprojection across a camera change).  Resolved lazily like the AOV symbols
+HR_HISTORY_API_VERSION = 1
+HR_HISTORY_MAX_HISTORY_LOWEST, HR_HISTORY_MAX_HISTORY_HIGHEST = 1, 65536
+HISTORY_SYMBOLS = ["history_api_version", "history_default_params", "history_capture", "history_merge", "history_drop", "history_info", "history_readback"]
+
+
+class HistoryParams(C.Structure):
+    """hr_history_params"""
+    _fields_ = [("max_history", C.c_int32), ("normal_cos", C.c_float), ("plane_tol", C.c_float), ("min_weight", C.c_float), ("reserved", C.c_uint32 * 4)]
+
+
+class HistoryResult(C.Structure):
+    """hr_history_result"""
+    _fields_ = [("reused_pixels", C.c_uint64), ("rejected_pixels", C.c_uint64), ("history_samples", C.c_uint64), ("history_passes", C.c_uint32),
+                ("passes", C.c_uint32)]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
 class GroupInfo(C.Structure):
     _fields_ = [("n_members", C.c_int32), ("device_ids", C.c_int32 * HR_GROUP_MAX_MEMBERS), ("owned_pixels", C.c_uint64 * HR_GROUP_MAX_MEMBERS)]
 
@@ -634,6 +654,47 @@ class Engine:
         """The error map of the last adaptive_update as H x W float32 (+inf: fewer than min_samples samples)."""
         out = np.empty((self.height, self.width), dtype=np.float32)
         self._adaptive_call("adaptive_error_readback", _ptr(out))
+        return out
+
+    # -- history reprojection (include/hrcore_history.h)
+    def _history_call(self, name, *args):
+        if not getattr(self, "_history_checked", False):
+            missing = [s for s in HISTORY_SYMBOLS if not hasattr(self._lib, self._p + s)]
+            if missing:
+                raise EngineError(f"this library has no history reprojection (lacks {[self._p + s for s in missing]})")
+            ver = getattr(self._lib, self._p + "history_api_version")
+            ver.restype = C.c_uint32
+            if ver() != HR_HISTORY_API_VERSION:
+                raise EngineError(f"{self._p}history_api_version() = {ver()}, this binding was written against {HR_HISTORY_API_VERSION}: rebuild the library")
+            self._history_checked = True
+        self._call(name, *args)
+
+    def history_capture(self, pass_params):
+        """Turn the frame and the three AOV planes (set_aovs(HR_AOV_SURFACE | HR_AOV_MOMENTS) before the first pass) into the history, as
+        seen by the camera of `pass_params` (view_matrix, fov_tan, aspect_ratio).  The history survives clear()."""
+        self._history_call("history_capture", C.byref(pass_params))
+
+    def history_merge(self, pass_params, params=None):
+        """Add the captured history to the frame and the planes of the view being rendered with `pass_params`; once per clear().  params: a
+        HistoryParams (heatray_amd.history.default_params()), None = the defaults.  Returns the HistoryResult as a dict."""
+        r = HistoryResult()
+        self._history_call("history_merge", C.byref(pass_params), C.byref(params) if params is not None else None, C.byref(r))
+        return r.as_dict()
+
+    def history_drop(self):
+        self._history_call("history_drop")
+
+    def history_info(self):
+        """(is there a captured history, the complete passes of the frame it was captured from)"""
+        have, n = C.c_int32(), C.c_uint32()
+        self._history_call("history_info", C.byref(have), C.byref(n))
+        return bool(have.value), int(n.value)
+
+    def history(self):
+        """The captured history as 3 x H x W x 4 float32: H0 (mean colour, samples), H1 (mean second moment, coverage), H2 (unit normal,
+        mean depth; +inf: sky)."""
+        out = np.empty((3, self.height, self.width, 4), dtype=np.float32)
+        self._history_call("history_readback", _ptr(out))
         return out
 
     def debug_trace(self, origins, dirs, tmax=None, skip_prim=None, any_hit=False):

@@ -11,6 +11,7 @@
 //   hr_group.inl      context groups (include/hrcore_group.h): member threads, the assembly of the members' tiles
 //   hr_aov.inl        the AOV planes (include/hrcore_aov.h);  hr_denoise.inl  the denoiser over them (include/hrcore_denoise.h)
 //   hr_adaptive.inl   the sample mask and the error estimate that builds it (include/hrcore_adaptive.h)
+//   hr_history.inl    history reprojection across a camera change (include/hrcore_history.h)
 // (one translation unit: the .inl files are sections of this one, included below)
 #include "hr_ctx.h"
 
@@ -177,6 +178,15 @@ static void adaptiveFree(hr_ctx *c)
     c->smWords = c->adWords = c->adResult = c->adResultHost = nullptr, c->smBytes = nullptr, c->adError = nullptr;
     c->adErrorValid = false;
     c->frame.mask = nullptr;
+}
+
+// History reprojection (include/hrcore_history.h): the history goes with the frame's size, not with its contents
+static void historyFree(hr_ctx *c)
+{
+    hipFree(c->hsHist), hipFree(c->hsResult);
+    if (c->hsResultHost) hipHostFree(c->hsResultHost);
+    c->hsHist = nullptr, c->hsResult = c->hsResultHost = nullptr;
+    c->hsCaptured = c->hsMerged = false, c->hsPasses = 0;
 }
 
 static void freeTree(hr_ctx *c)
@@ -358,6 +368,7 @@ int hr_ctx_destroy(hr_ctx *c)
     hipFree(c->dDisplay);
     aovFree(c);
     adaptiveFree(c);
+    historyFree(c);
     c->meshReleaseAll();
     for (int k = 0; k < 2; ++k) {
         if (c->stage[k]) hipHostFree(c->stage[k]);
@@ -564,6 +575,7 @@ int hr_frame_resize(hr_ctx *c, int32_t w, int32_t h)
     c->fbInternal = nullptr;
     c->fbExternal = nullptr;
     adaptiveFree(c); // (the sample mask goes with the frame it was made for)
+    historyFree(c);  // (... and so does a captured history)
     const size_t fbBytes = (size_t)w * h * 4 * sizeof(float);
     HIP_TRY(c, hipMalloc(&c->fbInternal, fbBytes));
     HIP_TRY(c, hipMemsetAsync(c->fbInternal, 0, fbBytes, c->stream));
@@ -727,3 +739,6 @@ int hr_debug_trace(hr_ctx *c, int32_t n, const float *o, const float *d, const f
 
 // ------------------------------------------------------------------------------------------ adaptive sampling
 #include "hr_adaptive.inl"
+
+// ------------------------------------------------------------------------------------------ history reprojection
+#include "hr_history.inl"

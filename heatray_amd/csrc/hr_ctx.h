@@ -451,6 +451,14 @@ struct hr_ctx {
     uint32_t *adResult = nullptr; // kAdaptiveResultWords device words ...
     uint32_t *adResultHost = nullptr; // ... and their pinned host copy
     bool adErrorValid = false;    // adError holds an update's map at this frame size
+    // History reprojection (include/hrcore_history.h).  The history survives hr_clear; it goes with the frame's size (historyFree:
+    // hr_frame_resize, hr_history_drop, hr_ctx_destroy).
+    float *hsHist = nullptr;          // kHistoryBytesPerPixel x W x H: H0, H1, H2
+    bool hsCaptured = false;          // hsHist holds a capture
+    uint32_t hsPasses = 0;            // complete passes of the frame it was captured from
+    float hsView[16] = {0}, hsFovTan = 0.0f, hsAspect = 0.0f; // ... and its camera
+    bool hsMerged = false;            // the history has been merged into the frame since its last hr_clear
+    unsigned long long *hsResult = nullptr, *hsResultHost = nullptr; // kHistoryResultWords device words and their pinned host copy
     size_t aovFramesPerSlot() const { return (aovMask & HR_AOV_SURFACE) ? 2 : 0; }
     // Context group (include/hrcore_group.h): non-null when this handle is a group.  Its own fields then describe the ASSEMBLED frame on the
     // group's first device (W, H, frame, fbInternal, the read-back buffers) and `stream` is the assembly stream; no pass pipeline runs on it.

@@ -1,0 +1,84 @@
+// hr_history.hip — the kernels of history reprojection (include/hrcore_history.h is the contract, hr_history.h the per-pixel arithmetic,
+// hr_history.inl the entry points).  A translation unit of its own: nothing here touches the register budgets of hr_render.hip.
+//
+// The history lives on the device as three planes of W x H float4 one after the other: H0, H1, H2.
+//
+//   k_history_capture  one lane per pixel: the frame's and the three planes' float4 in (64 B, coalesced), three float4 out (48 B): a
+//                      streaming kernel
+//   k_history_merge    one lane per pixel, a wave = an 8 x 8 block of pixels, a workgroup four of them side by side (32 x 8): a row of a
+//                      wave's own pixels is one 128-byte line per plane, and the wave's four-tap footprints (which a camera change
+//                      moves together) overlap in a handful of lines.  Own pixel 4 x 16 B in and, where history was taken over,
+//                      4 x 16 B out; 12 gathered float4 of history, every load issued before the first decision.  The counters: the
+//                      wave's ballots and a shuffle sum of the samples taken over, reduced in LDS, one integer atomic per workgroup and
+//                      counter: the result does not depend on the order workgroups finish in.
+// No scratch, no float atomics.
+#include "hr_math.h"
+#include "hr_history.h"
+#include "hr_kernels.h"
+
+namespace hr {
+
+static constexpr int kHsTileW = 32, kHsTileH = 8; // pixels of a workgroup of k_history_merge: four waves of 8 x 8
+
+struct HsGlobal {
+    const dn4 *p0, *p1, *p2;
+    HRD dn4 h0(int i) const { return G(p0)[i]; }
+    HRD dn4 h1(int i) const { return G(p1)[i]; }
+    HRD dn4 h2(int i) const { return G(p2)[i]; }
+};
+
+__global__ __launch_bounds__(256) void k_history_capture(int n, const dn4 *__restrict__ frame, const dn4 *__restrict__ albedo, const dn4 *__restrict__ normalDepth,
+                                                         const dn4 *__restrict__ moments, dn4 *__restrict__ hist)
+{
+    const int i = (int)(blockIdx.x * 256u + threadIdx.x);
+    if (i >= n) return;
+    dn4 H0, H1, H2;
+    hsCapture(G(frame)[i], G(albedo)[i], G(normalDepth)[i], G(moments)[i], H0, H1, H2);
+    G(hist)[i] = H0, G(hist)[(size_t)n + i] = H1, G(hist)[2 * (size_t)n + i] = H2;
+}
+
+// result: {reused pixels, rejected pixels, samples taken over}, zeroed by the caller
+__global__ __launch_bounds__(256) void k_history_merge(int W, int H, HsCam cam, HsParams P, const dn4 *__restrict__ hist, dn4 *__restrict__ frame, dn4 *__restrict__ albedo,
+                                                       dn4 *__restrict__ normalDepth, dn4 *__restrict__ moments, unsigned long long *__restrict__ result)
+{
+    __shared__ uint32_t sRed[3];
+    if (threadIdx.x < 3u) sRed[threadIdx.x] = 0u;
+    __syncthreads();
+    const uint32_t tilesX = (uint32_t)(W + kHsTileW - 1) / (uint32_t)kHsTileW; // (a one-dimensional grid: no bound on the image's height)
+    const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
+    const int x = (int)(blockIdx.x % tilesX) * kHsTileW + (int)(wave * 8u + (lane & 7u));
+    const int y = (int)(blockIdx.x / tilesX) * kHsTileH + (int)(lane >> 3);
+    const bool in = x < W && y < H;
+    const int i = in ? y * W + x : 0; // (a lane outside the image reads pixel 0 and writes nothing)
+    const size_t n = (size_t)W * (size_t)H;
+    dn4 F = G(frame)[i], A = G(albedo)[i], Gn = G(normalDepth)[i], M = G(moments)[i];
+    const HsGlobal src{hist, hist + n, hist + 2 * n};
+    float nh = 0.0f;
+    const int st = hsMerge(src, cam, P, in ? x : 0, in ? y : 0, W, H, F, A, Gn, M, &nh);
+    const bool reused = in && st == HS_REUSED, rejected = in && st == HS_REJECTED;
+    if (reused) G(frame)[i] = F, G(albedo)[i] = A, G(normalDepth)[i] = Gn, G(moments)[i] = M;
+    uint32_t samples = reused ? hsCount(nh) : 0u; // (at most 65536 per pixel: a workgroup's sum fits 32 bits)
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) samples += (uint32_t)__shfl_xor((int)samples, o);
+    const uint32_t nReused = (uint32_t)__popcll(__ballot(reused)), nRejected = (uint32_t)__popcll(__ballot(rejected));
+    if (lane == 0u) atomicAdd(&sRed[0], nReused), atomicAdd(&sRed[1], nRejected), atomicAdd(&sRed[2], samples);
+    __syncthreads();
+    if (threadIdx.x < 3u && sRed[threadIdx.x]) atomicAdd(&result[threadIdx.x], (unsigned long long)sRed[threadIdx.x]);
+}
+
+void launchHistoryCapture(hipStream_t st, int W, int H, const float *frame, const float *albedo, const float *normalDepth, const float *moments, float *hist)
+{
+    const int n = W * H;
+    hipLaunchKernelGGL(k_history_capture, dim3((n + 255) / 256), dim3(256), 0, st, n, reinterpret_cast<const dn4 *>(frame), reinterpret_cast<const dn4 *>(albedo),
+                       reinterpret_cast<const dn4 *>(normalDepth), reinterpret_cast<const dn4 *>(moments), reinterpret_cast<dn4 *>(hist));
+}
+
+void launchHistoryMerge(hipStream_t st, int W, int H, const HsCam &cam, const HsParams &P, const float *hist, float *frame, float *albedo, float *normalDepth, float *moments,
+                        unsigned long long *result)
+{
+    const dim3 grid(((W + kHsTileW - 1) / kHsTileW) * ((H + kHsTileH - 1) / kHsTileH));
+    hipLaunchKernelGGL(k_history_merge, grid, dim3(256), 0, st, W, H, cam, P, reinterpret_cast<const dn4 *>(hist), reinterpret_cast<dn4 *>(frame),
+                       reinterpret_cast<dn4 *>(albedo), reinterpret_cast<dn4 *>(normalDepth), reinterpret_cast<dn4 *>(moments), result);
+}
+
+} // namespace hr

@@ -1,0 +1,147 @@
+// hr_history.inl — a section of hr_core.hip (included at its end): the entry points of include/hrcore_history.h.  The kernels are in
+// hr_history.hip, the per-pixel arithmetic and the two cameras' arithmetic (hsCameras) in hr_history.h.
+//
+// Ordering.  Both kernels run on the context's stream after drainPipeline: every enqueued pass has been given its resolve there by then,
+// so a capture reads and a merge rewrites a frame and planes that hold exactly the passes requested so far; drainPipeline also makes
+// each pipeline group's next step wait for the context's stream (needUserSync), and the next resolve is enqueued behind the merge on
+// that same stream.  A merge waits for the stream because its result goes back to the host.
+#include "hr_history.h"
+
+static int historyCheckParams(hr_ctx *c, const hr_history_params *in, hr_history_params *p)
+{
+    if (in)
+        *p = *in;
+    else
+        hr_history_default_params(p);
+    if (p->max_history < HR_HISTORY_MAX_HISTORY_LOWEST || p->max_history > HR_HISTORY_MAX_HISTORY_HIGHEST)
+        FAIL(c, HR_ERR_INVALID, "history: max_history = " + std::to_string(p->max_history) + " is outside " + std::to_string(HR_HISTORY_MAX_HISTORY_LOWEST) + " .. " +
+                                    std::to_string(HR_HISTORY_MAX_HISTORY_HIGHEST));
+    if (!std::isfinite(p->normal_cos) || p->normal_cos < -1.0f || p->normal_cos > 1.0f) FAIL(c, HR_ERR_INVALID, "history: normal_cos must lie in -1 .. 1");
+    if (!std::isfinite(p->plane_tol) || !(p->plane_tol > 0.0f)) FAIL(c, HR_ERR_INVALID, "history: plane_tol must be finite and greater than 0");
+    if (!std::isfinite(p->min_weight) || !(p->min_weight > 0.0f) || p->min_weight > 1.0f) FAIL(c, HR_ERR_INVALID, "history: min_weight must be greater than 0 and at most 1");
+    return HR_OK;
+}
+
+static int historyCheckCamera(hr_ctx *c, const hr_pass_params *cam)
+{
+    if (!cam) FAIL(c, HR_ERR_INVALID, "history: null camera");
+    bool finite = std::isfinite(cam->fov_tan) && std::isfinite(cam->aspect_ratio);
+    for (float v : cam->view_matrix) finite = finite && std::isfinite(v);
+    if (!finite) FAIL(c, HR_ERR_INVALID, "history: the camera (view_matrix, fov_tan, aspect_ratio) is not finite");
+    return HR_OK;
+}
+
+// what capture and merge both ask of the context; *passes = the complete passes in its frame
+static int historyCheckFrame(hr_ctx *c, const char *what, uint32_t *passes)
+{
+    if (c->grp) FAIL(c, HR_ERR_INVALID, std::string(what) + ": a context group is not supported (the gather reads across the members' tiles): capture and merge on a plain context");
+    if (c->world > 1)
+        FAIL(c, HR_ERR_INVALID, std::string(what) + ": a tile-sharded context (world > 1) holds only its own tiles and the gather reads across them");
+    if (c->W <= 0) FAIL(c, HR_ERR_INVALID, "no frame");
+    const uint32_t both = HR_AOV_SURFACE | HR_AOV_MOMENTS;
+    if ((c->aovMask & both) != both)
+        FAIL(c, HR_ERR_INVALID, std::string(what) + " needs the AOV planes: hr_aov_enable(HR_AOV_SURFACE | HR_AOV_MOMENTS) before the frame's first pass (enabled mask: " +
+                                    std::to_string(c->aovMask) + ")");
+    if (c->aovZeroedAt != c->frameZeroedAt)
+        FAIL(c, HR_ERR_INVALID, std::string(what) + ": the AOV planes were enabled after the frame's first pass and do not hold the frame's passes: hr_clear, or hr_aov_enable before rendering");
+    int rc = drainPipeline(c);
+    if (rc == HR_OK) rc = overflowCheck(c);
+    if (rc) return rc;
+    *passes = (uint32_t)(c->nextResolveOrder - c->frameZeroedAt);
+    if (*passes == 0) FAIL(c, HR_ERR_INVALID, std::string(what) + ": the frame is empty (0 passes)");
+    return HR_OK;
+}
+
+extern "C" {
+
+uint32_t hr_history_api_version(void) { return HR_HISTORY_API_VERSION; }
+
+void hr_history_default_params(hr_history_params *p)
+{
+    if (!p) return;
+    *p = hr_history_params{};
+    p->max_history = 32, p->normal_cos = 0.9f, p->plane_tol = 0.02f, p->min_weight = 0.25f;
+}
+
+int hr_history_capture(hr_ctx *c, const hr_pass_params *camera)
+{
+    ENTER(c);
+    int rc = historyCheckCamera(c, camera);
+    if (rc) return rc;
+    uint32_t n = 0;
+    rc = historyCheckFrame(c, "history capture", &n);
+    if (rc) return rc;
+    if (!c->hsHist) HIP_TRY(c, hipMalloc((void **)&c->hsHist, (size_t)c->W * c->H * kHistoryBytesPerPixel));
+    c->hsCaptured = false;
+    launchHistoryCapture(c->stream, c->W, c->H, c->fb(), c->aovPlane[HR_AOV_PLANE_ALBEDO], c->aovPlane[HR_AOV_PLANE_NORMAL_DEPTH], c->aovPlane[HR_AOV_PLANE_MOMENTS], c->hsHist);
+    HIP_TRY(c, hipGetLastError());
+    std::memcpy(c->hsView, camera->view_matrix, sizeof(c->hsView));
+    c->hsFovTan = camera->fov_tan, c->hsAspect = camera->aspect_ratio;
+    c->hsPasses = n, c->hsCaptured = true;
+    return HR_OK;
+}
+
+int hr_history_merge(hr_ctx *c, const hr_pass_params *camera, const hr_history_params *params, hr_history_result *out)
+{
+    ENTER(c);
+    hr_history_params p;
+    int rc = historyCheckParams(c, params, &p);
+    if (rc == HR_OK) rc = historyCheckCamera(c, camera);
+    if (rc) return rc;
+    uint32_t n = 0;
+    rc = historyCheckFrame(c, "history merge", &n);
+    if (rc) return rc;
+    if (!c->hsCaptured) FAIL(c, HR_ERR_INVALID, "history merge: no captured history (hr_history_capture; hr_frame_resize and hr_history_drop remove it)");
+    if (c->hsMerged) FAIL(c, HR_ERR_INVALID, "history merge: the history has already been merged into this frame (one merge per hr_clear: a second would count it twice)");
+    if (!c->hsResult) HIP_TRY(c, hipMalloc((void **)&c->hsResult, kHistoryResultWords * 8));
+    if (!c->hsResultHost) HIP_TRY(c, hipHostMalloc((void **)&c->hsResultHost, kHistoryResultWords * 8, hipHostMallocDefault));
+    const HsCam cam = hsCameras(c->hsView, c->hsAspect, c->hsFovTan, camera->view_matrix, camera->aspect_ratio, camera->fov_tan);
+    const HsParams P{(float)p.max_history, p.normal_cos, p.plane_tol, p.min_weight};
+    HIP_TRY(c, hipMemsetAsync(c->hsResult, 0, kHistoryResultWords * 8, c->stream));
+    launchHistoryMerge(c->stream, c->W, c->H, cam, P, c->hsHist, c->fb(), c->aovPlane[HR_AOV_PLANE_ALBEDO], c->aovPlane[HR_AOV_PLANE_NORMAL_DEPTH],
+                       c->aovPlane[HR_AOV_PLANE_MOMENTS], c->hsResult);
+    HIP_TRY(c, hipGetLastError());
+    c->hsMerged = true;
+    c->snapshotEpoch++; // (progressive snapshots taken before the merge are not handed out any more)
+    HIP_TRY(c, hipMemcpyAsync(c->hsResultHost, c->hsResult, kHistoryResultWords * 8, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    if (out) {
+        *out = hr_history_result{};
+        out->reused_pixels = c->hsResultHost[0], out->rejected_pixels = c->hsResultHost[1], out->history_samples = c->hsResultHost[2];
+        out->history_passes = c->hsPasses, out->passes = n;
+    }
+    return HR_OK;
+}
+
+int hr_history_drop(hr_ctx *c)
+{
+    ENTER(c);
+    if (c->grp) return HR_OK; // (a group never holds one)
+    const int rc = c->hsHist ? quiesce(c) : HR_OK;
+    if (rc) return rc;
+    const bool merged = c->hsMerged; // (the frame has still been merged into: dropping the history does not allow a second merge of a new one)
+    historyFree(c);
+    c->hsMerged = merged;
+    return HR_OK;
+}
+
+int hr_history_info(hr_ctx *c, int32_t *captured, uint32_t *passes)
+{
+    ENTER(c);
+    const bool have = !c->grp && c->hsCaptured;
+    if (captured) *captured = have ? 1 : 0;
+    if (passes) *passes = have ? c->hsPasses : 0u;
+    return HR_OK;
+}
+
+int hr_history_readback(hr_ctx *c, float *host_out)
+{
+    ENTER(c);
+    if (!host_out) FAIL(c, HR_ERR_INVALID, "null output");
+    if (c->grp || !c->hsCaptured) FAIL(c, HR_ERR_INVALID, "history: no captured history");
+    HIP_TRY(c, hipMemcpyAsync(host_out, c->hsHist, (size_t)c->W * c->H * kHistoryBytesPerPixel, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    return HR_OK;
+}
+
+} // extern "C"

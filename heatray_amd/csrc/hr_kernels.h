@@ -6,6 +6,7 @@
 #include "../../include/hrcore_aov.h"
 #include "../../include/hrcore_denoise.h"
 #include "../../include/hrcore_adaptive.h"
+#include "../../include/hrcore_history.h"
 
 #include <cstddef>
 
@@ -196,6 +197,16 @@ static const size_t kAdaptiveResultWords = 4;
 void launchAdaptiveMask(hipStream_t st, int W, int H, const float *err, const hr_adaptive_params &p, uint32_t *words, uint32_t *result);
 void launchMaskPack(hipStream_t st, int W, int H, const uint8_t *bytes, uint32_t *words);   // W x H bytes (non-zero = sampled) -> words
 void launchMaskUnpack(hipStream_t st, int W, int H, const uint32_t *words, uint8_t *bytes); // words -> W x H bytes, 0 / 1
+
+// ---- hr_history.hip (include/hrcore_history.h)
+struct HsCam;    // hr_history.h: the two cameras of a merge
+struct HsParams; // ... and its parameters as the kernel takes them
+static const size_t kHistoryBytesPerPixel = 3 * 16; // H0, H1, H2: three planes of W x H float4 one after the other
+void launchHistoryCapture(hipStream_t st, int W, int H, const float *frame, const float *albedo, const float *normalDepth, const float *moments, float *hist);
+// the history -> the frame and the planes of the view being rendered; result = {reused pixels, rejected pixels, samples taken over}, zeroed by the caller
+static const size_t kHistoryResultWords = 3;
+void launchHistoryMerge(hipStream_t st, int W, int H, const HsCam &cam, const HsParams &P, const float *hist, float *frame, float *albedo, float *normalDepth, float *moments,
+                        unsigned long long *result);
 
 // ---- hr_build.hip
 // Per-geometry descriptor for the assemble kernel; all pointers are device pointers.  Attributes are addressed with a stride

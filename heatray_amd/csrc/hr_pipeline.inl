@@ -17,6 +17,7 @@ int hr_clear(hr_ctx *c)
         if (plane) HIP_TRY(c, hipMemsetAsync(plane, 0, (size_t)c->W * c->H * 4 * sizeof(float), c->stream));
     c->resolvedAtClear = c->aovZeroedAt = c->frameZeroedAt = c->nextResolveOrder;
     c->frame.mask = nullptr; // (include/hrcore_adaptive.h: a new frame starts without a sample mask)
+    c->hsMerged = false;     // (include/hrcore_history.h: ... and may take over a captured history once)
     c->snapshotEpoch++;
     if (getenv("HR_DEBUG_PIPE")) fprintf(stderr, "hr_clear %p: ray-memory growths so far %llu, waits %llu (%.2f ms)\n", (void *)c, c->dbgGrowths, c->dbgWaits, (double)c->dbgWaitNs * 1e-6);
     c->drainTimes();

@@ -1,0 +1,341 @@
+"""The arithmetic of history reprojection without a GPU: heatray_amd/csrc/hr_history.h compiled for the CPU (tests/host/history_cpu.cpp)
+against its numpy restatement heatray_amd.history.reference_capture / reference_merge, bit for bit, every pixel, on synthetic frames,
+planes and cameras; and properties of the reference itself on constructed inputs whose answers are known (include/hrcore_history.h is
+the contract).  tests/test_gpu_history.py holds the device to the same reference."""
+import ctypes as C
+import math
+import os
+import subprocess
+
+import numpy as np
+import pytest
+
+from heatray_amd import _ffi as ffi
+from heatray_amd import history, scenes
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+F = np.float32
+U = 2.0 ** -24  # unit roundoff of binary32
+
+
+def camera(view=None, fov=0.24, aspect=None, W=1, H=1):
+    """A PassParams that holds a camera: view = camera -> world as m[row, col]"""
+    p = ffi.PassParams()
+    m = np.eye(4) if view is None else np.asarray(view, np.float64)
+    p.view_matrix = (C.c_float * 16)(*m.astype(F).T.reshape(-1))
+    p.fov_tan = fov
+    p.aspect_ratio = aspect if aspect is not None else W / H
+    return p
+
+
+def rot_y(a):
+    c, s = math.cos(a), math.sin(a)
+    return np.array([[c, 0, s, 0], [0, 1, 0, 0], [-s, 0, c, 0], [0, 0, 0, 1.0]])
+
+
+def rot_x(a):
+    c, s = math.cos(a), math.sin(a)
+    return np.array([[1, 0, 0, 0], [0, c, -s, 0], [0, s, c, 0], [0, 0, 0, 1.0]])
+
+
+def translate(x, y, z):
+    m = np.eye(4)
+    m[:3, 3] = (x, y, z)
+    return m
+
+
+def params(max_history=32, normal_cos=0.9, plane_tol=0.02, min_weight=0.25):
+    p = history.default_params()
+    p.max_history, p.normal_cos, p.plane_tol, p.min_weight = max_history, normal_cos, plane_tol, min_weight
+    return p
+
+
+@pytest.fixture(scope="module")
+def cpu(tmp_path_factory):
+    d = tmp_path_factory.mktemp("history_cpu")
+    exe = d / "history_cpu"
+    # -ffp-contract=off like the library: the header's float lines must mean the same on both sides
+    subprocess.check_call(["g++", "-std=c++17", "-O1", "-ffp-contract=off", "-Wall", "-I" + os.path.join(ROOT, "heatray_amd", "csrc"),
+                           os.path.join(ROOT, "tests", "host", "history_cpu.cpp"), "-o", str(exe)])
+
+    def cam_floats(pp):
+        return np.array(list(pp.view_matrix) + [pp.aspect_ratio, pp.fov_tan], F)
+
+    def run(old, old_cam, new, new_cam, p):
+        H, W = old[0].shape[:2]
+        with open(d / "in.bin", "wb") as f:
+            f.write(np.array([W, H, p.max_history, 0], np.int32).tobytes())
+            f.write(np.array([p.normal_cos, p.plane_tol, p.min_weight, 0], F).tobytes())
+            f.write(cam_floats(old_cam).tobytes())
+            f.write(cam_floats(new_cam).tobytes())
+            for frame, planes in (old, new):
+                f.write(np.ascontiguousarray(frame, F).tobytes())
+                for k in history.PLANES:
+                    f.write(np.ascontiguousarray(planes[k], F).tobytes())
+        out = subprocess.run([str(exe), str(d / "in.bin"), str(d / "out.bin")], capture_output=True, text=True)
+        assert out.returncode == 0 and "history cpu: ok" in out.stdout, (out.returncode, out.stderr)
+        raw = np.fromfile(d / "out.bin", np.uint8)
+        n = W * H * 16
+        hist = raw[:3 * n].view(F).reshape(3, H, W, 4)
+        planes = [raw[(3 + k) * n:(4 + k) * n].view(F).reshape(H, W, 4) for k in range(4)]
+        res = raw[7 * n:7 * n + 24].view(np.uint64)
+        return hist, planes[0], dict(zip(history.PLANES, planes[1:])), {"reused_pixels": int(res[0]), "rejected_pixels": int(res[1]), "history_samples": int(res[2])}
+    return run
+
+
+def _same_bits(got, want, what):
+    g, w = np.ascontiguousarray(got), np.ascontiguousarray(want)
+    assert g.shape == w.shape and g.dtype == w.dtype, what
+    if g.tobytes() != w.tobytes():
+        bad = np.argwhere(g.view(np.uint32) != w.view(np.uint32))
+        raise AssertionError(f"{what}: {len(bad)} values differ, first at {tuple(bad[0])}: {g[tuple(bad[0])]} against {w[tuple(bad[0])]}")
+
+
+def _check(cpu, old, old_cam, new, new_cam, p, what):
+    """the CPU build of the header against the numpy reference, bit for bit; returns the reference's answer"""
+    hist = history.reference_capture(*old)
+    frame, planes, res = history.reference_merge(hist, old_cam, new[0], new[1], new_cam, p)
+    chist, cframe, cplanes, cres = cpu(old, old_cam, new, new_cam, p)
+    _same_bits(chist, hist, what + ": history")
+    _same_bits(cframe, frame, what + ": frame")
+    for k in history.PLANES:
+        _same_bits(cplanes[k], planes[k], f"{what}: {k}")
+    assert cres == {k: res[k] for k in cres}, (what, cres, res)
+    # what holds for every merge
+    _same_bits(frame[..., 3], planes["moments"][..., 3], what + ": F.a against M.a")
+    assert (frame[..., 3] == np.floor(frame[..., 3])).all(), what
+    empty = ~(new[0][..., 3] > 0)
+    _same_bits(frame[empty], new[0][empty], what + ": a pixel with n = 0 is untouched (frame)")
+    for k in history.PLANES:
+        _same_bits(planes[k][empty], new[1][k][empty], f"{what}: a pixel with n = 0 is untouched ({k})")
+    assert res["reused_pixels"] + res["rejected_pixels"] == int((new[0][..., 3] > 0).sum()), what
+    return hist, frame, planes, res
+
+
+def _uniform(rng, shape):
+    """SplitMix64 content -> float32 in [0, 1)"""
+    n = int(np.prod(shape))
+    return ((rng.u64(n) >> np.uint64(40)).astype(np.float64) / float(1 << 24)).astype(F).reshape(shape)
+
+
+def plane_view(W, H, cam, seed, depth=6.0, max_n=40, holes=True, sky=True, noise=True):
+    """A frame and its planes as a renderer would leave them in front of the world plane z = -depth (normal 0 0 1), seen with `cam`:
+    per-pixel sample counts (some 0), coverage between 0 and 1 (sky patches, half-covered pixels), normals and depths disturbed at some
+    pixels (what the tap tests must reject), colours and moments from SplitMix64."""
+    rng = scenes.SplitMix64(seed)
+    v = np.array(list(cam.view_matrix), np.float64).reshape(4, 4).T
+    y, x = np.mgrid[0:H, 0:W]
+    cx = (2 * (x + 0.5) / W - 1) * cam.aspect_ratio * cam.fov_tan
+    cy = (2 * (y + 0.5) / H - 1) * cam.fov_tan
+    d = cx[..., None] * v[:3, 0] + cy[..., None] * v[:3, 1] - v[:3, 2]
+    with np.errstate(all="ignore"):
+        s = (-depth - v[2, 3]) / d[..., 2]
+    hit = np.isfinite(s) & (s > 0)
+    u = _uniform(rng, (8, H, W))
+    n = np.floor(u[0] * (max_n + 1)) if holes else np.full((H, W), float(max_n))
+    if holes:
+        n[u[1] < 0.05] = 0
+    cov = np.where(hit, 1.0, 0.0)
+    if sky:
+        blocks = _uniform(rng, ((H + 7) // 8, (W + 7) // 8))[y // 8, x // 8]
+        cov = np.where(blocks < 0.2, 0.0, cov)                         # sky patches
+        cov = np.where((u[2] < 0.1) & hit, np.round(u[3] * 4) / 4, cov)  # partly covered pixels: 0, 1/4 .. 1
+    hits = np.floor(n * cov)
+    normal = np.zeros((H, W, 3))
+    normal[..., 2] = 1.0
+    dep = np.where(hit, s, 0.0)
+    if noise:
+        turn = u[4] < 0.1
+        ang = u[5] * 1.2
+        normal[turn] = np.stack([np.sin(ang), np.zeros_like(ang), np.cos(ang)], -1)[turn]
+        dep = np.where(u[6] < 0.1, dep * (1 + 0.2 * (u[7] - 0.5)), dep)
+    col = _uniform(rng, (H, W, 3)) * F(1.5) + F(0.02)
+    frame, planes = np.zeros((H, W, 4), F), {k: np.zeros((H, W, 4), F) for k in history.PLANES}
+    frame[..., :3], frame[..., 3] = col * n[..., None], n
+    planes["moments"][..., :3], planes["moments"][..., 3] = (col * col * F(1.3)) * n[..., None], n
+    planes["albedo"][..., :3], planes["albedo"][..., 3] = _uniform(rng, (H, W, 3)) * hits[..., None], hits
+    planes["normal_depth"][..., :3], planes["normal_depth"][..., 3] = normal * hits[..., None], dep * hits
+    return frame, planes
+
+
+MOVES = {
+    "none": lambda: (np.eye(4), 0.24),
+    "yaw": lambda: (rot_y(0.05), 0.24),
+    "orbit": lambda: (translate(0, 0, -6) @ rot_y(0.3) @ translate(0, 0, 6), 0.24),
+    "pitch_shift": lambda: (translate(0.3, -0.2, 0.1) @ rot_x(-0.07), 0.24),
+    "dolly": lambda: (translate(0, 0, -0.6), 0.24),
+    "zoom": lambda: (np.eye(4), 0.31),
+    "behind": lambda: (rot_y(math.pi), 0.24),
+}
+CASES = [(67, 41, "none", 1), (67, 41, "yaw", 2), (67, 41, "orbit", 3), (131, 19, "pitch_shift", 4), (5, 300, "dolly", 5), (64, 16, "zoom", 6),
+         (1, 1, "none", 7), (33, 33, "behind", 8), (96, 54, "orbit", 9)]
+
+
+@pytest.mark.parametrize("case", CASES, ids=lambda c: "-".join(str(v) for v in c))
+def test_cpu_header_equals_numpy_reference_bit_for_bit(cpu, case):
+    W, H, move, seed = case
+    base = translate(0.1, 0.2, 0.3) @ rot_y(0.2) @ rot_x(-0.1)  # (no identity matrices: every product of R and t rounds)
+    m, fov_new = MOVES[move]()
+    old_cam = camera(base, 0.24, W=W, H=H)
+    new_cam = camera(base @ m, fov_new, W=W, H=H)
+    old = plane_view(W, H, old_cam, seed)
+    new = plane_view(W, H, new_cam, seed + 100)
+    _, _, _, res = _check(cpu, old, old_cam, new, new_cam, params(), f"case {case}")
+    sampled = int((new[0][..., 3] > 0).sum())
+    if W * H > 1000 and move != "behind":  # the inputs exercise both answers
+        assert 0 < res["reused_pixels"] < sampled and res["rejected_pixels"] > 0, res
+    if move == "behind":
+        assert res["reused_pixels"] == 0 and res["rejected_pixels"] == sampled
+
+
+@pytest.mark.parametrize("p", [params(max_history=1), params(max_history=65536), params(normal_cos=-1.0), params(normal_cos=1.0), params(plane_tol=1e-30),
+                               params(plane_tol=1e30), params(min_weight=1e-30), params(min_weight=1.0)],
+                         ids=["max1", "max65536", "cos-1", "cos1", "tol-tiny", "tol-huge", "minw-tiny", "minw1"])
+def test_parameters_at_both_ends_of_their_ranges(cpu, p):
+    W, H = 67, 41
+    old_cam = camera(rot_y(0.2), 0.24, W=W, H=H)
+    new_cam = camera(rot_y(0.2) @ translate(0.2, 0.0, 0.0) @ rot_y(0.04), 0.24, W=W, H=H)
+    old, new = plane_view(W, H, old_cam, 21, max_n=100000 if p.max_history > 32 else 40), plane_view(W, H, new_cam, 22)
+    _, frame, _, res = _check(cpu, old, old_cam, new, new_cam, p, "ends")
+    nh = res["nh"]
+    assert nh.max() <= p.max_history and (nh == np.floor(nh)).all()
+    if p.max_history == 1:
+        assert set(np.unique(nh)) == {0.0, 1.0} and res["history_samples"] == res["reused_pixels"]
+    if p.max_history == 65536:
+        assert nh.max() > 32
+    ref = history.reference_merge(history.reference_capture(*old), old_cam, new[0], new[1], new_cam, params())[2]
+    if p.normal_cos == -1.0 or p.plane_tol > 1 or p.min_weight < 0.25:   # a wider test never loses a pixel
+        assert res["reused_pixels"] >= ref["reused_pixels"]
+    if p.normal_cos == 1.0 or p.plane_tol < 1e-3 or p.min_weight == 1.0:  # a tighter one never gains one
+        assert res["reused_pixels"] <= ref["reused_pixels"]
+
+
+def flat(W, H, n, colour=(0.5, 0.25, 0.125), depth=6.0, cov=1.0, normal=(0.0, 0.0, 1.0)):
+    """n samples of one colour everywhere on a surface of one depth and normal (cov = 0: sky)"""
+    frame, planes = np.zeros((H, W, 4), F), {k: np.zeros((H, W, 4), F) for k in history.PLANES}
+    c = np.asarray(colour, F)
+    frame[..., :3], frame[..., 3] = c * F(n), n
+    planes["moments"][..., :3], planes["moments"][..., 3] = (c * c) * F(n), n
+    hits = F(n * cov)
+    planes["albedo"][..., :3], planes["albedo"][..., 3] = F(0.5) * hits, hits
+    planes["normal_depth"][..., :3], planes["normal_depth"][..., 3] = np.asarray(normal, F) * hits, F(depth) * hits
+    return frame, planes
+
+
+def test_a_constant_history_comes_back_as_that_constant(cpu):
+    """h = (sum w_k C) / (sum w_k) over at most four taps, all weights positive.  Roundings: one per product w_k C, three for the sums of
+    the four products (the first sum, 0 + x, is exact), three for the sum of the weights, one for the division: eight, each of relative
+    size at most u = 2^-24 and none cancelling because every term has one sign — so |h - C| <= 8 u |C| to first order; asserted with 9 u
+    for the second-order terms.  The moment likewise.  Made readable from the output by a history of 64 samples against max_history 32
+    (nh = 32 exactly: fmin_ picks the cap) merged into a frame whose colour sums are 0: F.rgb = 0 + h * 32, exact."""
+    W, H = 67, 41
+    C3 = np.array([0.7310586, 0.2689414, 1.6180340], F)
+    old_cam = camera(rot_y(0.3), 0.24, W=W, H=H)
+    new_cam = camera(rot_y(0.3) @ translate(0.15, -0.1, 0.2) @ rot_y(0.03) @ rot_x(0.02), 0.26, W=W, H=H)
+    old = flat(W, H, 64, colour=C3)
+    old[1]["moments"][..., :3] = (C3 * F(3.0)) * F(64)
+    new = plane_view(W, H, new_cam, 5, depth=6.0, holes=False, sky=False, noise=False)
+    old = (old[0], {**old[1], "normal_depth": plane_view(W, H, old_cam, 6, depth=6.0, max_n=64, holes=False, sky=False, noise=False)[1]["normal_depth"]})
+    new[0][..., :3] = 0
+    new[1]["moments"][..., :3] = 0
+    _, frame, planes, res = _check(cpu, old, old_cam, new, new_cam, params(), "constant")
+    reused = res["nh"] > 0
+    assert reused.sum() > 0.5 * W * H and (res["nh"][reused] == 32).all()
+    h = frame[..., :3][reused].astype(np.float64) / 32.0
+    m2 = planes["moments"][..., :3][reused].astype(np.float64) / 32.0
+    assert (np.abs(h - C3.astype(np.float64)) <= 9 * U * C3.astype(np.float64)).all()
+    assert (np.abs(m2 - 3.0 * C3.astype(np.float64)) <= 9 * U * 3.0 * C3.astype(np.float64) + 2 * U * 3.0 * C3.astype(np.float64)).all()  # (C * 3 and * 64 round once more in the input)
+
+
+@pytest.mark.parametrize("n_old, max_history, want", [(64, 32, 32), (16, 32, 16), (100, 32, 32), (1, 1, 1), (32, 32, 32)])
+def test_the_same_camera_reuses_every_sampled_pixel(cpu, n_old, max_history, want):
+    """nh = floor(min(sum(w n) / sum(w), max_history)).  With one sample count n over the image the quotient is n exactly when n is a
+    power of two (every product and sum just scales the weights' own), and at least max_history in any case when n is well above it."""
+    W, H = 67, 41
+    cam = camera(translate(0.5, 1.0, 2.0) @ rot_y(0.4) @ rot_x(-0.2), 0.24, W=W, H=H)
+    old = plane_view(W, H, cam, 31, max_n=n_old, holes=False, sky=False, noise=False)
+    new = plane_view(W, H, cam, 32, max_n=3, holes=True, sky=False, noise=False)
+    for k in ("albedo", "normal_depth"):  # a band of sky in both views
+        old[1][k][:, 10:20] = 0
+        new[1][k][:, 10:20] = 0
+    _, frame, _, res = _check(cpu, old, cam, new, cam, params(max_history=max_history), "same camera")
+    sampled = new[0][..., 3] > 0
+    assert res["rejected_pixels"] == 0 and res["reused_pixels"] == int(sampled.sum()) > 0.5 * W * H
+    assert (res["nh"][sampled] == want).all()
+    assert (frame[..., 3][sampled] == new[0][..., 3][sampled] + F(want)).all()
+
+
+def test_a_sideways_shift_by_whole_pixels_shifts_the_history(cpu):
+    W, H, k, depth, fov = 64, 24, 5, 6.0, 0.25
+    aspect = W / H
+    step = 2 * aspect * fov * depth / W  # the width of a pixel on the plane
+    old_cam, new_cam = camera(np.eye(4), fov, W=W, H=H), camera(translate(k * step, 0, 0), fov, W=W, H=H)
+    col = _uniform(scenes.SplitMix64(3), (W, 3))  # a colour per column
+    old = flat(W, H, 32)
+    old[0][..., :3] = col[None] * F(32)
+    new = flat(W, H, 1, colour=(0, 0, 0))
+    _, frame, _, res = _check(cpu, old, old_cam, new, new_cam, params(), "shift")
+    nh = res["nh"]
+    assert (nh[:, :W - k] == 32).all() and (nh[:, W - k:] == 0).all()  # the k columns that entered the view have no history
+    assert res["rejected_pixels"] == k * H
+    # column x shows what column x + k showed; the projection's rounding lets in less than 1e-4 of a neighbouring column
+    got = frame[:, :W - k, :3].astype(np.float64) / 32.0
+    assert np.abs(got - col[None, k:].astype(np.float64)).max() < 1e-3
+
+
+def test_what_a_nearer_surface_uncovered_is_rejected(cpu):
+    W, H, k, depth, fov = 64, 16, 4, 10.0, 0.25
+    step = 2 * (W / H) * fov * depth / W
+    old_cam, new_cam = camera(np.eye(4), fov, W=W, H=H), camera(translate(k * step, 0, 0), fov, W=W, H=H)
+    old = flat(W, H, 32, depth=depth)
+    old[1]["normal_depth"][:, 20:30, 3] = F(5.0) * F(32)  # a nearer strip in the old view; the new view sees the far plane everywhere
+    new = flat(W, H, 1, depth=depth)
+    _, _, _, res = _check(cpu, old, old_cam, new, new_cam, params(), "two depths")
+    want = np.full((H, W), 32, F)
+    want[:, 20 - k:30 - k] = 0  # the pixels whose point lies where the old view saw the strip
+    want[:, W - k:] = 0
+    assert (res["nh"] == want).all()
+    # ... and with a plane test wide enough to let the strip through they take its history
+    wide = history.reference_merge(history.reference_capture(*old), old_cam, new[0], new[1], new_cam, params(plane_tol=1.0))[2]["nh"]
+    assert (wide[:, 20 - k:30 - k] == 32).all()
+
+
+def test_a_normal_turned_past_normal_cos_is_rejected(cpu):
+    W, H = 32, 8
+    cam = camera(rot_y(0.1), 0.24, W=W, H=H)
+    old = plane_view(W, H, cam, 1, max_n=32, holes=False, sky=False, noise=False)
+    new = plane_view(W, H, cam, 2, max_n=1, holes=False, sky=False, noise=False)
+    for x, cosine in ((3, 0.85), (4, 0.95), (5, 0.0), (6, -1.0)):
+        new[1]["normal_depth"][:, x, :3] = F([math.sqrt(1 - cosine * cosine), 0.0, cosine])
+    _, _, _, res = _check(cpu, old, cam, new, cam, params(normal_cos=0.9), "normal")
+    assert (res["nh"][:, [3, 5, 6]] == 0).all() and (res["nh"][:, 4] == 32).all() and (res["nh"][:, 7:] == 32).all()
+
+
+def test_sky_and_surface_never_exchange_history(cpu):
+    W, H = 32, 8
+    cam = camera(rot_y(0.1), 0.24, W=W, H=H)
+    old = plane_view(W, H, cam, 1, max_n=32, holes=False, sky=False, noise=False)
+    new = plane_view(W, H, cam, 2, max_n=1, holes=False, sky=False, noise=False)
+    for k in ("albedo", "normal_depth"):
+        old[1][k][:, 8:16] = 0   # sky in the old view ...
+        new[1][k][:, 12:20] = 0  # ... and in the new one
+    _, _, _, res = _check(cpu, old, cam, new, cam, params(), "classes")
+    nh = res["nh"]
+    assert (nh[:, 1:7] == 32).all() and (nh[:, 9:11] == 0).all() and (nh[:, 13:15] == 32).all() and (nh[:, 17:19] == 0).all() and (nh[:, 21:] == 32).all()
+
+
+@pytest.mark.parametrize("sky", [False, True])
+def test_behind_the_old_camera_and_outside_the_old_image(cpu, sky):
+    W, H = 40, 30
+    base = rot_x(0.1)
+    old_cam = camera(base, 0.24, W=W, H=H)
+    old, new = flat(W, H, 32, cov=0.0 if sky else 1.0), flat(W, H, 2, cov=0.0 if sky else 1.0)
+    for what, m in (("behind", rot_y(math.pi)), ("outside", rot_y(math.pi / 2)), ("outside, near", rot_y(1.2 * 2 * math.atan(0.24 * W / H)))):
+        _, frame, _, res = _check(cpu, old, old_cam, new, camera(base @ m, 0.24, W=W, H=H), params(), what)
+        assert res["reused_pixels"] == 0 and res["rejected_pixels"] == W * H, what
+        _same_bits(frame, new[0], what + ": nothing changed")
+
+
+def test_default_params_are_the_documented_ones():
+    p = history.default_params()
+    assert (p.max_history, p.normal_cos, p.plane_tol, p.min_weight) == (32, F(0.9), F(0.02), F(0.25)) and list(p.reserved) == [0, 0, 0, 0]
