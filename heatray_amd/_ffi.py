@@ -231,6 +231,29 @@ class HistoryResult(C.Structure):
         return {k: getattr(self, k) for k, _ in self._fields_}
 
 
+# every symbol include/hrcore_reproject.h declares (the progressive history merge and the preview of unsampled pixels).  Resolved lazily
+# like the AOV symbols
+HR_REPROJECT_API_VERSION = 1
+REPROJECT_SYMBOLS = ["reproject_api_version", "reproject_merge", "reproject_examined_get", "reproject_preview", "reproject_preview_readback"]
+
+
+class ReprojectResult(C.Structure):
+    """hr_reproject_result"""
+    _fields_ = [("reused_pixels", C.c_uint64), ("rejected_pixels", C.c_uint64), ("history_samples", C.c_uint64), ("pending_pixels", C.c_uint64),
+                ("examined_pixels", C.c_uint64), ("history_passes", C.c_uint32), ("passes", C.c_uint32)]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
+class ReprojectPreviewResult(C.Structure):
+    """hr_reproject_preview_result"""
+    _fields_ = [("own_pixels", C.c_uint64), ("previewed_pixels", C.c_uint64), ("empty_pixels", C.c_uint64)]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
 class GroupInfo(C.Structure):
     _fields_ = [("n_members", C.c_int32), ("device_ids", C.c_int32 * HR_GROUP_MAX_MEMBERS), ("owned_pixels", C.c_uint64 * HR_GROUP_MAX_MEMBERS)]
 
@@ -696,6 +719,47 @@ class Engine:
         out = np.empty((3, self.height, self.width, 4), dtype=np.float32)
         self._history_call("history_readback", _ptr(out))
         return out
+
+    # -- progressive merge and preview (include/hrcore_reproject.h)
+    def _reproject_call(self, name, *args):
+        if not getattr(self, "_reproject_checked", False):
+            missing = [s for s in REPROJECT_SYMBOLS if not hasattr(self._lib, self._p + s)]
+            if missing:
+                raise EngineError(f"this library has no progressive history merge (lacks {[self._p + s for s in missing]})")
+            ver = getattr(self._lib, self._p + "reproject_api_version")
+            ver.restype = C.c_uint32
+            if ver() != HR_REPROJECT_API_VERSION:
+                raise EngineError(f"{self._p}reproject_api_version() = {ver()}, this binding was written against {HR_REPROJECT_API_VERSION}: rebuild the library")
+            self._reproject_checked = True
+        self._call(name, *args)
+
+    def reproject_merge(self, pass_params, params=None):
+        """history_merge's progressive form: the sampled pixels no earlier call has examined since clear() take over their history; any
+        number of calls per clear().  params: a HistoryParams, None = the defaults.  Returns the ReprojectResult as a dict."""
+        r = ReprojectResult()
+        self._reproject_call("reproject_merge", C.byref(pass_params), C.byref(params) if params is not None else None, C.byref(r))
+        return r.as_dict()
+
+    def reproject_examined(self):
+        """The examined bits as H x W bool (row 0 = bottom like the frame)."""
+        out = np.empty((self.height, self.width), dtype=np.uint8)
+        self._reproject_call("reproject_examined_get", out.ctypes.data_as(C.POINTER(C.c_uint8)))
+        return out.astype(bool)
+
+    def reproject_preview(self, pass_params, params=None):
+        """(H x W x 4 float32, the ReprojectPreviewResult as a dict): every sampled pixel's own mean and, in the pixels without a sample,
+        the history behind a neighbour's guide (alpha 1) or 0 0 0 0.  Changes nothing."""
+        p = f32p()
+        w, h = C.c_int32(), C.c_int32()
+        r = ReprojectPreviewResult()
+        self._reproject_call("reproject_preview_readback", C.byref(pass_params), C.byref(params) if params is not None else None, C.byref(p), C.byref(w), C.byref(h),
+                             C.byref(r))
+        return np.ctypeslib.as_array(p, shape=(h.value, w.value, 4)).copy(), r.as_dict()
+
+    def reproject_preview_to_device(self, device_ptr, pass_params, params=None, stream=None):
+        """Asynchronous: the preview (W x H float4) into device memory, e.g. a torch tensor; ordered like denoise_to_device."""
+        self._reproject_call("reproject_preview", C.byref(pass_params), C.byref(params) if params is not None else None, C.c_void_p(int(device_ptr)),
+                             C.c_void_p(stream or 0), None)
 
     def debug_trace(self, origins, dirs, tmax=None, skip_prim=None, any_hit=False):
         o, d = _f32(origins).reshape(-1, 3), _f32(dirs).reshape(-1, 3)

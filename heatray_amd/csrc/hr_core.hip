@@ -12,6 +12,7 @@
 //   hr_aov.inl        the AOV planes (include/hrcore_aov.h);  hr_denoise.inl  the denoiser over them (include/hrcore_denoise.h)
 //   hr_adaptive.inl   the sample mask and the error estimate that builds it (include/hrcore_adaptive.h)
 //   hr_history.inl    history reprojection across a camera change (include/hrcore_history.h)
+//   hr_reproject.inl  its progressive form and the preview of unsampled pixels (include/hrcore_reproject.h)
 // (one translation unit: the .inl files are sections of this one, included below)
 #include "hr_ctx.h"
 
@@ -187,6 +188,16 @@ static void historyFree(hr_ctx *c)
     if (c->hsResultHost) hipHostFree(c->hsResultHost);
     c->hsHist = nullptr, c->hsResult = c->hsResultHost = nullptr;
     c->hsCaptured = c->hsMerged = false, c->hsPasses = 0;
+}
+
+// Progressive merge and preview (include/hrcore_reproject.h): the examined bits and the preview's buffers go with the frame's size
+static void reprojectFree(hr_ctx *c)
+{
+    hipFree(c->rpExamined), hipFree(c->rpResult), hipFree(c->rpOut);
+    if (c->rpResultHost) hipHostFree(c->rpResultHost);
+    if (c->rpPinned) hipHostFree(c->rpPinned);
+    c->rpExamined = c->rpResult = c->rpResultHost = nullptr, c->rpOut = c->rpPinned = nullptr, c->rpPinnedBytes = 0;
+    c->rpStale = true, c->rpMerged = false;
 }
 
 static void freeTree(hr_ctx *c)
@@ -369,6 +380,7 @@ int hr_ctx_destroy(hr_ctx *c)
     aovFree(c);
     adaptiveFree(c);
     historyFree(c);
+    reprojectFree(c);
     c->meshReleaseAll();
     for (int k = 0; k < 2; ++k) {
         if (c->stage[k]) hipHostFree(c->stage[k]);
@@ -576,6 +588,7 @@ int hr_frame_resize(hr_ctx *c, int32_t w, int32_t h)
     c->fbExternal = nullptr;
     adaptiveFree(c); // (the sample mask goes with the frame it was made for)
     historyFree(c);  // (... and so does a captured history)
+    reprojectFree(c); // (... and the examined bits of the progressive merge)
     const size_t fbBytes = (size_t)w * h * 4 * sizeof(float);
     HIP_TRY(c, hipMalloc(&c->fbInternal, fbBytes));
     HIP_TRY(c, hipMemsetAsync(c->fbInternal, 0, fbBytes, c->stream));
@@ -742,3 +755,6 @@ int hr_debug_trace(hr_ctx *c, int32_t n, const float *o, const float *d, const f
 
 // ------------------------------------------------------------------------------------------ history reprojection
 #include "hr_history.inl"
+
+// ------------------------------------------------------------------------------------------ progressive merge and preview
+#include "hr_reproject.inl"

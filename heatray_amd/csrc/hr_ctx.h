@@ -459,6 +459,15 @@ struct hr_ctx {
     float hsView[16] = {0}, hsFovTan = 0.0f, hsAspect = 0.0f; // ... and its camera
     bool hsMerged = false;            // the history has been merged into the frame since its last hr_clear
     unsigned long long *hsResult = nullptr, *hsResultHost = nullptr; // kHistoryResultWords device words and their pinned host copy
+    // Progressive merge and preview (include/hrcore_reproject.h).  Everything here goes with the frame's size (reprojectFree: hr_frame_resize,
+    // hr_ctx_destroy); hr_clear marks the examined bits stale and the next hr_reproject_merge zeroes them.
+    unsigned long long *rpExamined = nullptr; // rpExaminedWords(W, H) words: one per 8 x 8 block of pixels
+    bool rpStale = true;                      // the bits belong to an earlier frame (or were never zeroed): all pixels count as not examined
+    bool rpMerged = false;                    // hr_reproject_merge has merged into the frame since its last hr_clear (hsMerged is set with it)
+    unsigned long long *rpResult = nullptr, *rpResultHost = nullptr; // kReprojectResultWords device words and their pinned host copy
+    float *rpOut = nullptr;                   // the preview when it does not go straight to the caller's memory (W x H float4)
+    float *rpPinned = nullptr;                // hr_reproject_preview_readback's host buffer
+    size_t rpPinnedBytes = 0;
     size_t aovFramesPerSlot() const { return (aovMask & HR_AOV_SURFACE) ? 2 : 0; }
     // Context group (include/hrcore_group.h): non-null when this handle is a group.  Its own fields then describe the ASSEMBLED frame on the
     // group's first device (W, H, frame, fbInternal, the read-back buffers) and `stream` is the assembly stream; no pass pipeline runs on it.

@@ -7,6 +7,7 @@
 #include "../../include/hrcore_denoise.h"
 #include "../../include/hrcore_adaptive.h"
 #include "../../include/hrcore_history.h"
+#include "../../include/hrcore_reproject.h"
 
 #include <cstddef>
 
@@ -207,6 +208,17 @@ void launchHistoryCapture(hipStream_t st, int W, int H, const float *frame, cons
 static const size_t kHistoryResultWords = 3;
 void launchHistoryMerge(hipStream_t st, int W, int H, const HsCam &cam, const HsParams &P, const float *hist, float *frame, float *albedo, float *normalDepth, float *moments,
                         unsigned long long *result);
+
+// ---- hr_reproject.hip (include/hrcore_reproject.h)
+// the history -> the sampled pixels of the frame and the planes that the examined bits (rpExaminedWords 64-bit words, hr_reproject.h) do not
+// mark yet; result = {reused pixels, rejected pixels, samples taken over, pending pixels, examined pixels}, zeroed by the caller
+static const size_t kReprojectResultWords = 5;
+void launchReprojectMerge(hipStream_t st, int W, int H, const HsCam &cam, const HsParams &P, const float *hist, float *frame, float *albedo, float *normalDepth, float *moments,
+                          unsigned long long *examined, unsigned long long *result);
+// a one-sample image (W x H float4) of the frame's own means and, where it has none, the history's colour behind a neighbour's guide;
+// result = {own pixels, previewed pixels, empty pixels} in the first three of kReprojectResultWords words, zeroed by the caller
+void launchReprojectPreview(hipStream_t st, int W, int H, const HsCam &cam, const HsParams &P, const float *hist, const float *frame, const float *albedo,
+                            const float *normalDepth, float *out, unsigned long long *result);
 
 // ---- hr_build.hip
 // Per-geometry descriptor for the assemble kernel; all pointers are device pointers.  Attributes are addressed with a stride

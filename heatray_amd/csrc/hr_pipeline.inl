@@ -18,6 +18,7 @@ int hr_clear(hr_ctx *c)
     c->resolvedAtClear = c->aovZeroedAt = c->frameZeroedAt = c->nextResolveOrder;
     c->frame.mask = nullptr; // (include/hrcore_adaptive.h: a new frame starts without a sample mask)
     c->hsMerged = false;     // (include/hrcore_history.h: ... and may take over a captured history once)
+    c->rpMerged = false, c->rpStale = true; // (include/hrcore_reproject.h: ... or progressively: no pixel of the new frame has been examined)
     c->snapshotEpoch++;
     if (getenv("HR_DEBUG_PIPE")) fprintf(stderr, "hr_clear %p: ray-memory growths so far %llu, waits %llu (%.2f ms)\n", (void *)c, c->dbgGrowths, c->dbgWaits, (double)c->dbgWaitNs * 1e-6);
     c->drainTimes();

@@ -1,0 +1,127 @@
+// hr_reproject.h — the per-pixel arithmetic of the progressive history merge and the preview (include/hrcore_reproject.h states the
+// contract these lines implement).  Pure float32 functions like hr_history.h's, which this header builds on: the progressive merge IS
+// hsMerge, applied to the pixels the examined bits have not seen yet; the preview restates hsMerge's projection and taps for a point,
+// a normal and a class that come from a neighbour (hsMerge itself is left as it is: its kernels' registers are pinned).  The kernels in
+// hr_reproject.hip and the CPU test (tests/host/reproject_cpu.cpp, against heatray_amd/reproject.py) compile the same lines.
+#pragma once
+#include "hr_history.h"
+
+namespace hr {
+
+// what a pixel can tell an unsampled neighbour: the class and, for a surface, the unit world-space normal and the mean depth
+enum { RP_GUIDE_NONE = 0, RP_GUIDE_SKY = 1, RP_GUIDE_SURFACE = 2 };
+
+// F.w, A, G of one pixel -> its guide record (rec = N.xyz, d; 0 0 0 0 unless a surface).  The divisions and the normalisation of MERGE.
+HRN int rpGuide(float n, const dn4 &A, const dn4 &G, dn4 &rec)
+{
+    rec = dn4{0.0f, 0.0f, 0.0f, 0.0f};
+    if (!(n > 0.0f)) return RP_GUIDE_NONE;
+    if (!(A.w / n >= 0.5f)) return RP_GUIDE_SKY;
+    const float l2 = HS_DOT(G.x, G.y, G.z, G.x, G.y, G.z);
+    if (l2 > 0.0f) {
+        const float l = sqrt_(l2);
+        rec.x = G.x / l, rec.y = G.y / l, rec.z = G.z / l;
+    }
+    rec.w = G.w / A.w;
+    return RP_GUIDE_SURFACE;
+}
+
+// the 24 offsets with |dx| <= 2, |dy| <= 2 without (0, 0), in ascending order of (dx * dx + dy * dy, dy, dx): offset k = (dx, dy)
+enum { RP_GUIDE_OFFSETS = 24, RP_GUIDE_REACH = 2 };
+HRN void rpOffset(int k, int &dx, int &dy)
+{
+    // two bits per entry and axis would do; a byte each reads better: dx + 2 in the low nibble, dy + 2 in the high one
+    const unsigned char t[RP_GUIDE_OFFSETS] = {0x12, 0x21, 0x23, 0x32, 0x11, 0x13, 0x31, 0x33, 0x02, 0x20, 0x24, 0x42,
+                                               0x01, 0x03, 0x10, 0x14, 0x30, 0x34, 0x41, 0x43, 0x00, 0x04, 0x40, 0x44};
+    dx = (int)(t[k] & 15u) - 2, dy = (int)(t[k] >> 4) - 2;
+}
+
+enum { RP_OWN = 0, RP_PREVIEWED = 1, RP_EMPTY = 2 };
+
+// A guide source Q gives Q.cls(gx, gy) and Q.rec(gx, gy) (rpGuide's two answers) for pixels inside the image.
+
+// The first guide of pixel (x, y) in the contract's order: its class (RP_GUIDE_NONE: there is none), position and record.
+template <class Q> HRN int rpFindGuide(const Q &guides, int x, int y, int W, int H, int &gx, int &gy, dn4 &rec)
+{
+    int cls = RP_GUIDE_NONE;
+    gx = x, gy = y;
+    for (int k = 0; k < RP_GUIDE_OFFSETS && cls == RP_GUIDE_NONE; ++k) {
+        int dx, dy;
+        rpOffset(k, dx, dy);
+        gx = x + dx, gy = y + dy;
+        if (gx >= 0 && gx < W && gy >= 0 && gy < H) cls = guides.cls(gx, gy);
+    }
+    rec = dn4{0.0f, 0.0f, 0.0f, 0.0f};
+    if (cls != RP_GUIDE_NONE) rec = guides.rec(gx, gy);
+    return cls;
+}
+
+// The preview of an UNSAMPLED pixel (x, y) from its guide (cls, gx, gy, rec as rpFindGuide gave them; cls RP_GUIDE_NONE: no guide):
+// the history's colour at the point where the pixel's ray cuts the guide's tangent plane, through MERGE's projection and tap tests.
+// Like hsMerge written without a branch around a load: the eight float4 (H0 and H2 of four taps) are read at clamped addresses
+// whatever has been decided, and the sums skip a tap that does not count by a select.  *out = (colour, 1) and RP_PREVIEWED, or
+// 0 0 0 0 and RP_EMPTY.
+template <class S> HRN int rpPreviewFromGuide(const S &s, const HsCam &cam, const HsParams &P, int x, int y, int W, int H, int cls, int gx, int gy, const dn4 &rec, dn4 &out)
+{
+    bool ok = cls != RP_GUIDE_NONE;
+    const bool surf = cls == RP_GUIDE_SURFACE;
+    const float Wf = (float)W, Hf = (float)H;
+    const float cx = hsRayX(x, Wf, cam.aspectNew, cam.fovNew), cy = hsRayY(y, Hf, cam.fovNew), cz = -1.0f;
+    float q[3], Nq[3] = {0.0f, 0.0f, 0.0f};
+    const float N[3] = {rec.x, rec.y, rec.z};
+    for (int i = 0; i < 3; ++i) q[i] = (cam.R[3 * i] * cx + cam.R[3 * i + 1] * cy) + cam.R[3 * i + 2] * cz;
+    if (surf) {
+        const float gcx = hsRayX(gx, Wf, cam.aspectNew, cam.fovNew), gcy = hsRayY(gy, Hf, cam.fovNew);
+        float rcg[3];
+        for (int i = 0; i < 3; ++i) {
+            rcg[i] = (cam.R[3 * i] * gcx + cam.R[3 * i + 1] * gcy) + cam.R[3 * i + 2] * cz;
+            Nq[i] = HS_DOT(cam.O[3 * i], cam.O[3 * i + 1], cam.O[3 * i + 2], N[0], N[1], N[2]);
+        }
+        const float sd = (rec.w * HS_DOT(Nq[0], Nq[1], Nq[2], rcg[0], rcg[1], rcg[2])) / HS_DOT(Nq[0], Nq[1], Nq[2], q[0], q[1], q[2]);
+        ok = ok && sd > 0.0f && sd < __builtin_inff();
+        for (int i = 0; i < 3; ++i) q[i] = sd * q[i] + cam.t[i];
+    }
+    const float z = -q[2];
+    ok = ok && z > 0.0f;
+    const float sx = (((q[0] / z) / cam.axOld + 1.0f) * 0.5f) * Wf;
+    const float sy = (((q[1] / z) / cam.fovOld + 1.0f) * 0.5f) * Hf;
+    ok = ok && (sx >= -1.0f && sx <= Wf + 1.0f && sy >= -1.0f && sy <= Hf + 1.0f);
+    const float fx = ok ? sx - 0.5f : 0.0f, fy = ok ? sy - 0.5f : 0.0f;
+    const float x0f = floor_(fx), y0f = floor_(fy);
+    const float wx = fx - x0f, wy = fy - y0f;
+    const int x0 = (int)x0f, y0 = (int)y0f;
+    const float tol = P.planeTol * z;
+    float wsum = 0.0f, hs[3] = {0.0f, 0.0f, 0.0f};
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        const int tx = x0 + (k & 1), ty = y0 + (k >> 1);
+        const float w = ((k & 1) ? wx : 1.0f - wx) * ((k >> 1) ? wy : 1.0f - wy);
+        const bool inside = tx >= 0 && tx < W && ty >= 0 && ty < H;
+        const int ux = tx < 0 ? 0 : (tx >= W ? W - 1 : tx), uy = ty < 0 ? 0 : (ty >= H ? H - 1 : ty);
+        const int i = uy * W + ux;
+        const dn4 h0 = s.h0(i), h2 = s.h2(i);
+        bool use = ok && inside && h0.w > 0.0f && (hsFinite(h2.w) == surf);
+        if (surf) {
+            const float nd = HS_DOT(N[0], N[1], N[2], h2.x, h2.y, h2.z);
+            const float px = h2.w * hsRayX(ux, Wf, cam.aspectOld, cam.fovOld), py = h2.w * hsRayY(uy, Hf, cam.fovOld), pz = h2.w * -1.0f;
+            const float dx = px - q[0], dy = py - q[1], dz = pz - q[2];
+            const float pd = abs_(HS_DOT(Nq[0], Nq[1], Nq[2], dx, dy, dz));
+            use = use && nd >= P.normalCos && pd <= tol;
+        }
+        wsum = use ? wsum + w : wsum;
+        hs[0] = use ? hs[0] + w * h0.x : hs[0], hs[1] = use ? hs[1] + w * h0.y : hs[1], hs[2] = use ? hs[2] + w * h0.z : hs[2];
+    }
+    ok = ok && !(wsum < P.minWeight);
+    out = dn4{0.0f, 0.0f, 0.0f, 0.0f};
+    if (!ok) return RP_EMPTY;
+    out = dn4{hs[0] / wsum, hs[1] / wsum, hs[2] / wsum, 1.0f};
+    return RP_PREVIEWED;
+}
+
+// a sampled pixel's own mean
+HRN dn4 rpOwn(const dn4 &F) { return dn4{F.x / F.w, F.y / F.w, F.z / F.w, 1.0f}; }
+
+// the words of the examined bits: one 64-bit word per 8 x 8 block of pixels, bit (y & 7) * 8 + (x & 7) of word (y >> 3) * blocksX + (x >> 3)
+inline size_t rpExaminedWords(int W, int H) { return (size_t)((W + 7) / 8) * (size_t)((H + 7) / 8); }
+
+} // namespace hr

@@ -1,0 +1,160 @@
+// hr_reproject.hip — the kernels of the progressive history merge and the preview (include/hrcore_reproject.h is the contract,
+// hr_reproject.h the per-pixel arithmetic, hr_reproject.inl the entry points).  A translation unit of its own: nothing here touches the
+// register budgets of hr_history.hip or hr_render.hip.
+//
+//   k_reproject_merge    k_history_merge's shape: one lane per pixel, a wave = an 8 x 8 block of pixels, a workgroup four of them side by
+//                        side (32 x 8).  The examined bits are one 64-bit word per 8 x 8 block, bit = the lane: a wave reads its word
+//                        with one load, and one lane writes it back from a __ballot.  A wave without a pixel to examine (every sampled
+//                        pixel of its block examined already, or none sampled yet) leaves before any plane or history load: that branch
+//                        is wave-uniform.  Otherwise hsMerge: all twelve history loads at clamped addresses before the first decision.
+//   k_reproject_preview  a workgroup stages the guide records (rpGuide: class, unit normal, mean depth) of its 32 x 8 tile and a halo of
+//                        2 in LDS, 36 x 12 entries, each normalised and divided once; an unsampled lane walks the 24 offsets there
+//                        and stops at the first hit; the four taps' H0 and H2, eight float4, are issued together.  A wave whose pixels
+//                        all have samples writes their means and reads no history.
+// The counters of both: the wave's ballots (and a shuffle sum of the samples taken over), reduced in LDS, one integer atomic per
+// workgroup and counter: a result does not depend on the order workgroups finish in.  No scratch, no float atomics, plain vector stores.
+#include "hr_math.h"
+#include "hr_reproject.h"
+#include "hr_kernels.h"
+
+namespace hr {
+
+static constexpr int kRpTileW = 32, kRpTileH = 8;                                              // pixels of a workgroup: four waves of 8 x 8
+static constexpr int kRpHaloW = kRpTileW + 2 * RP_GUIDE_REACH, kRpHaloH = kRpTileH + 2 * RP_GUIDE_REACH; // 36 x 12 staged guide records
+
+struct RpGlobal {
+    const dn4 *p0, *p1, *p2;
+    HRD dn4 h0(int i) const { return G(p0)[i]; }
+    HRD dn4 h1(int i) const { return G(p1)[i]; }
+    HRD dn4 h2(int i) const { return G(p2)[i]; }
+};
+
+// result: {reused pixels, rejected pixels, samples taken over, pending pixels, examined pixels}, zeroed by the caller
+__global__ __launch_bounds__(256) void k_reproject_merge(int W, int H, HsCam cam, HsParams P, const dn4 *__restrict__ hist, dn4 *__restrict__ frame, dn4 *__restrict__ albedo,
+                                                         dn4 *__restrict__ normalDepth, dn4 *__restrict__ moments, unsigned long long *__restrict__ examined,
+                                                         unsigned long long *__restrict__ result)
+{
+    __shared__ uint32_t sRed[5];
+    if (threadIdx.x < 5u) sRed[threadIdx.x] = 0u;
+    __syncthreads();
+    const uint32_t tilesX = (uint32_t)(W + kRpTileW - 1) / (uint32_t)kRpTileW;
+    const uint32_t blocksX = (uint32_t)(W + 7) / 8u;
+    const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
+    const uint32_t blockX = (blockIdx.x % tilesX) * 4u + wave, blockY = blockIdx.x / tilesX; // the wave's 8 x 8 block
+    const int x = (int)(blockX * 8u + (lane & 7u));
+    const int y = (int)(blockY * 8u + (lane >> 3));
+    const bool in = x < W && y < H;
+    const int i = in ? y * W + x : 0; // (a lane outside the image reads pixel 0 and writes nothing)
+    const bool hasWord = blockX < blocksX; // (the last workgroup of a row may hold waves that lie outside the image altogether)
+    const size_t wordAt = (size_t)blockY * blocksX + blockX;
+    const unsigned long long word = hasWord ? G(examined)[wordAt] : 0ull;
+    dn4 F = G(frame)[i];
+    const bool todo = in && !((word >> lane) & 1ull) && F.w > 0.0f;
+    const unsigned long long todoMask = __ballot(todo);
+    uint32_t nReused = 0u, nRejected = 0u, samples = 0u;
+    if (todoMask) { // wave-uniform
+        const size_t n = (size_t)W * (size_t)H;
+        dn4 A = G(albedo)[i], Gn = G(normalDepth)[i], M = G(moments)[i];
+        const RpGlobal src{hist, hist + n, hist + 2 * n};
+        float nh = 0.0f;
+        const int st = hsMerge(src, cam, P, in ? x : 0, in ? y : 0, W, H, F, A, Gn, M, &nh);
+        const bool reused = todo && st == HS_REUSED, rejected = todo && st == HS_REJECTED;
+        if (reused) G(frame)[i] = F, G(albedo)[i] = A, G(normalDepth)[i] = Gn, G(moments)[i] = M;
+        samples = reused ? hsCount(nh) : 0u; // (at most 65536 per pixel: a workgroup's sum fits 32 bits)
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) samples += (uint32_t)__shfl_xor((int)samples, o);
+        nReused = (uint32_t)__popcll(__ballot(reused)), nRejected = (uint32_t)__popcll(__ballot(rejected));
+        if (lane == 0u) G(examined)[wordAt] = word | todoMask; // (todoMask != 0 implies hasWord)
+    }
+    const unsigned long long now = word | todoMask;
+    const uint32_t nExamined = (uint32_t)__popcll(now), nPending = (uint32_t)__popcll(__ballot(in) & ~now);
+    if (lane == 0u) {
+        if (nReused) atomicAdd(&sRed[0], nReused);
+        if (nRejected) atomicAdd(&sRed[1], nRejected);
+        if (samples) atomicAdd(&sRed[2], samples);
+        atomicAdd(&sRed[3], nPending), atomicAdd(&sRed[4], nExamined);
+    }
+    __syncthreads();
+    if (threadIdx.x < 5u && sRed[threadIdx.x]) atomicAdd(&result[threadIdx.x], (unsigned long long)sRed[threadIdx.x]);
+}
+
+// the workgroup's staged guide records behind rpFindGuide's source
+struct RpTileGuides {
+    const dn4 *rec_;
+    const unsigned char *cls_;
+    int x0, y0; // the image position of entry (0, 0)
+    HRD int at(int gx, int gy) const { return (gy - y0) * kRpHaloW + (gx - x0); }
+    HRD int cls(int gx, int gy) const { return (int)cls_[at(gx, gy)]; }
+    HRD dn4 rec(int gx, int gy) const { return rec_[at(gx, gy)]; }
+};
+
+// result: {own pixels, previewed pixels, empty pixels}, zeroed by the caller
+__global__ __launch_bounds__(256) void k_reproject_preview(int W, int H, HsCam cam, HsParams P, const dn4 *__restrict__ hist, const dn4 *__restrict__ frame,
+                                                           const dn4 *__restrict__ albedo, const dn4 *__restrict__ normalDepth, dn4 *__restrict__ out,
+                                                           unsigned long long *__restrict__ result)
+{
+    __shared__ dn4 sRec[kRpHaloW * kRpHaloH];
+    __shared__ unsigned char sCls[kRpHaloW * kRpHaloH];
+    __shared__ uint32_t sRed[3];
+    if (threadIdx.x < 3u) sRed[threadIdx.x] = 0u;
+    const uint32_t tilesX = (uint32_t)(W + kRpTileW - 1) / (uint32_t)kRpTileW;
+    const int tx0 = (int)(blockIdx.x % tilesX) * kRpTileW, ty0 = (int)(blockIdx.x / tilesX) * kRpTileH;
+    for (int e = (int)threadIdx.x; e < kRpHaloW * kRpHaloH; e += 256) {
+        const int gx = tx0 - RP_GUIDE_REACH + e % kRpHaloW, gy = ty0 - RP_GUIDE_REACH + e / kRpHaloW;
+        const bool inside = gx >= 0 && gx < W && gy >= 0 && gy < H;
+        const int gi = inside ? gy * W + gx : 0;
+        const dn4 Fg = G(frame)[gi], A = G(albedo)[gi], Gn = G(normalDepth)[gi];
+        dn4 rec;
+        const int cls = rpGuide(inside ? Fg.w : 0.0f, A, Gn, rec);
+        sRec[e] = rec, sCls[e] = (unsigned char)cls;
+    }
+    __syncthreads();
+    const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
+    const int x = tx0 + (int)(wave * 8u + (lane & 7u));
+    const int y = ty0 + (int)(lane >> 3);
+    const bool in = x < W && y < H;
+    const int i = in ? y * W + x : 0;
+    const dn4 F = G(frame)[i];
+    const bool own = in && F.w > 0.0f, needs = in && !own;
+    dn4 px = own ? rpOwn(F) : dn4{0.0f, 0.0f, 0.0f, 0.0f};
+    bool previewed = false;
+    if (__ballot(needs)) { // wave-uniform: a wave whose pixels all have samples reads no history
+        const RpTileGuides guides{sRec, sCls, tx0 - RP_GUIDE_REACH, ty0 - RP_GUIDE_REACH};
+        int gx = 0, gy = 0, cls = RP_GUIDE_NONE;
+        dn4 rec{0.0f, 0.0f, 0.0f, 0.0f};
+        if (needs) cls = rpFindGuide(guides, x, y, W, H, gx, gy, rec);
+        const size_t n = (size_t)W * (size_t)H;
+        const RpGlobal src{hist, hist + n, hist + 2 * n};
+        dn4 pv;
+        const int st = rpPreviewFromGuide(src, cam, P, in ? x : 0, in ? y : 0, W, H, cls, gx, gy, rec, pv);
+        previewed = needs && st == RP_PREVIEWED;
+        if (previewed) px = pv;
+    }
+    if (in) G(out)[i] = px;
+    const uint32_t nOwn = (uint32_t)__popcll(__ballot(own)), nPrev = (uint32_t)__popcll(__ballot(previewed)), nEmpty = (uint32_t)__popcll(__ballot(needs && !previewed));
+    if (lane == 0u) {
+        if (nOwn) atomicAdd(&sRed[0], nOwn);
+        if (nPrev) atomicAdd(&sRed[1], nPrev);
+        if (nEmpty) atomicAdd(&sRed[2], nEmpty);
+    }
+    __syncthreads();
+    if (threadIdx.x < 3u && sRed[threadIdx.x]) atomicAdd(&result[threadIdx.x], (unsigned long long)sRed[threadIdx.x]);
+}
+
+static dim3 rpGrid(int W, int H) { return dim3(((W + kRpTileW - 1) / kRpTileW) * ((H + kRpTileH - 1) / kRpTileH)); }
+
+void launchReprojectMerge(hipStream_t st, int W, int H, const HsCam &cam, const HsParams &P, const float *hist, float *frame, float *albedo, float *normalDepth, float *moments,
+                          unsigned long long *examined, unsigned long long *result)
+{
+    hipLaunchKernelGGL(k_reproject_merge, rpGrid(W, H), dim3(256), 0, st, W, H, cam, P, reinterpret_cast<const dn4 *>(hist), reinterpret_cast<dn4 *>(frame),
+                       reinterpret_cast<dn4 *>(albedo), reinterpret_cast<dn4 *>(normalDepth), reinterpret_cast<dn4 *>(moments), examined, result);
+}
+
+void launchReprojectPreview(hipStream_t st, int W, int H, const HsCam &cam, const HsParams &P, const float *hist, const float *frame, const float *albedo,
+                            const float *normalDepth, float *out, unsigned long long *result)
+{
+    hipLaunchKernelGGL(k_reproject_preview, rpGrid(W, H), dim3(256), 0, st, W, H, cam, P, reinterpret_cast<const dn4 *>(hist), reinterpret_cast<const dn4 *>(frame),
+                       reinterpret_cast<const dn4 *>(albedo), reinterpret_cast<const dn4 *>(normalDepth), reinterpret_cast<dn4 *>(out), result);
+}
+
+} // namespace hr

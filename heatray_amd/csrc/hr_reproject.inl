@@ -1,0 +1,149 @@
+// hr_reproject.inl — a section of hr_core.hip (included at its end): the entry points of include/hrcore_reproject.h.  The kernels are in
+// hr_reproject.hip, the per-pixel arithmetic in hr_reproject.h; the parameter, camera and frame checks are hr_history.inl's.
+//
+// Ordering: as in hr_history.inl.  Both kernels run on the context's stream after drainPipeline, which also makes each pipeline group's
+// next step wait for that stream; the next resolve is enqueued behind them there.
+#include "hr_reproject.h"
+
+// what merge and preview ask before they launch: parameters, camera, frame (drains the pipeline), a history; the buffers of the counters
+static int reprojectPrepare(hr_ctx *c, const char *what, const hr_pass_params *camera, const hr_history_params *params, hr_history_params *p, uint32_t *passes)
+{
+    int rc = historyCheckParams(c, params, p);
+    if (rc == HR_OK) rc = historyCheckCamera(c, camera);
+    if (rc) return rc;
+    rc = historyCheckFrame(c, what, passes);
+    if (rc) return rc;
+    if (!c->hsCaptured) FAIL(c, HR_ERR_INVALID, std::string(what) + ": no captured history (hr_history_capture; hr_frame_resize and hr_history_drop remove it)");
+    if (!c->rpResult) HIP_TRY(c, hipMalloc((void **)&c->rpResult, kReprojectResultWords * 8));
+    if (!c->rpResultHost) HIP_TRY(c, hipHostMalloc((void **)&c->rpResultHost, kReprojectResultWords * 8, hipHostMallocDefault));
+    return HR_OK;
+}
+
+// Checks, and enqueues the preview on the ctx stream; the image goes to `dst`, or to c->rpOut when dst is null.  With `out` it waits.
+static int previewRun(hr_ctx *c, const hr_pass_params *camera, const hr_history_params *params, float *dst, hr_reproject_preview_result *out)
+{
+    hr_history_params p;
+    uint32_t n = 0;
+    int rc = reprojectPrepare(c, "reproject preview", camera, params, &p, &n);
+    if (rc) return rc;
+    if (!dst) {
+        if (!c->rpOut) HIP_TRY(c, hipMalloc((void **)&c->rpOut, (size_t)c->W * c->H * 16));
+        dst = c->rpOut;
+    }
+    const HsCam cam = hsCameras(c->hsView, c->hsAspect, c->hsFovTan, camera->view_matrix, camera->aspect_ratio, camera->fov_tan);
+    const HsParams P{(float)p.max_history, p.normal_cos, p.plane_tol, p.min_weight};
+    HIP_TRY(c, hipMemsetAsync(c->rpResult, 0, kReprojectResultWords * 8, c->stream));
+    launchReprojectPreview(c->stream, c->W, c->H, cam, P, c->hsHist, c->fb(), c->aovPlane[HR_AOV_PLANE_ALBEDO], c->aovPlane[HR_AOV_PLANE_NORMAL_DEPTH], dst, c->rpResult);
+    HIP_TRY(c, hipGetLastError());
+    if (out) {
+        HIP_TRY(c, hipMemcpyAsync(c->rpResultHost, c->rpResult, kReprojectResultWords * 8, hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(c, hipStreamSynchronize(c->stream));
+        *out = hr_reproject_preview_result{};
+        out->own_pixels = c->rpResultHost[0], out->previewed_pixels = c->rpResultHost[1], out->empty_pixels = c->rpResultHost[2];
+    }
+    return HR_OK;
+}
+
+extern "C" {
+
+uint32_t hr_reproject_api_version(void) { return HR_REPROJECT_API_VERSION; }
+
+int hr_reproject_merge(hr_ctx *c, const hr_pass_params *camera, const hr_history_params *params, hr_reproject_result *out)
+{
+    ENTER(c);
+    hr_history_params p;
+    uint32_t n = 0;
+    int rc = reprojectPrepare(c, "reproject merge", camera, params, &p, &n);
+    if (rc) return rc;
+    if (c->hsMerged && !c->rpMerged)
+        FAIL(c, HR_ERR_INVALID, "reproject merge: hr_history_merge has already merged the history into this frame (a progressive merge would count it twice): hr_clear first");
+    const size_t words = rpExaminedWords(c->W, c->H);
+    if (!c->rpExamined) {
+        HIP_TRY(c, hipMalloc((void **)&c->rpExamined, words * 8));
+        c->rpStale = true;
+    }
+    if (c->rpStale) HIP_TRY(c, hipMemsetAsync(c->rpExamined, 0, words * 8, c->stream));
+    c->rpStale = false;
+    const HsCam cam = hsCameras(c->hsView, c->hsAspect, c->hsFovTan, camera->view_matrix, camera->aspect_ratio, camera->fov_tan);
+    const HsParams P{(float)p.max_history, p.normal_cos, p.plane_tol, p.min_weight};
+    HIP_TRY(c, hipMemsetAsync(c->rpResult, 0, kReprojectResultWords * 8, c->stream));
+    launchReprojectMerge(c->stream, c->W, c->H, cam, P, c->hsHist, c->fb(), c->aovPlane[HR_AOV_PLANE_ALBEDO], c->aovPlane[HR_AOV_PLANE_NORMAL_DEPTH],
+                         c->aovPlane[HR_AOV_PLANE_MOMENTS], c->rpExamined, c->rpResult);
+    HIP_TRY(c, hipGetLastError());
+    c->hsMerged = c->rpMerged = true;
+    c->snapshotEpoch++; // (progressive snapshots taken before the merge are not handed out any more)
+    HIP_TRY(c, hipMemcpyAsync(c->rpResultHost, c->rpResult, kReprojectResultWords * 8, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    if (out) {
+        *out = hr_reproject_result{};
+        out->reused_pixels = c->rpResultHost[0], out->rejected_pixels = c->rpResultHost[1], out->history_samples = c->rpResultHost[2];
+        out->pending_pixels = c->rpResultHost[3], out->examined_pixels = c->rpResultHost[4];
+        out->history_passes = c->hsPasses, out->passes = n;
+    }
+    return HR_OK;
+}
+
+int hr_reproject_examined_get(hr_ctx *c, uint8_t *host_out)
+{
+    ENTER(c);
+    if (!host_out) FAIL(c, HR_ERR_INVALID, "null output");
+    if (c->grp) FAIL(c, HR_ERR_INVALID, "reproject: a context group is not supported");
+    if (c->W <= 0) FAIL(c, HR_ERR_INVALID, "no frame");
+    const size_t px = (size_t)c->W * c->H;
+    std::memset(host_out, 0, px);
+    if (!c->rpExamined || c->rpStale) return HR_OK; // (no pixel of this frame has been examined)
+    std::vector<unsigned long long> words(rpExaminedWords(c->W, c->H));
+    HIP_TRY(c, hipMemcpyAsync(words.data(), c->rpExamined, words.size() * 8, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    const int blocksX = (c->W + 7) / 8;
+    for (int y = 0; y < c->H; ++y)
+        for (int x = 0; x < c->W; ++x) host_out[(size_t)y * c->W + x] = (uint8_t)((words[(size_t)(y >> 3) * blocksX + (x >> 3)] >> ((y & 7) * 8 + (x & 7))) & 1ull);
+    return HR_OK;
+}
+
+int hr_reproject_preview(hr_ctx *c, const hr_pass_params *camera, const hr_history_params *params, void *device_out, void *stream, hr_reproject_preview_result *out)
+{
+    ENTER(c);
+    if (!device_out) FAIL(c, HR_ERR_INVALID, "null output");
+    hipStream_t st = stream ? (hipStream_t)stream : c->stream;
+    if (st == c->stream) return previewRun(c, camera, params, (float *)device_out, out);
+    // a foreign stream: the kernel on the ctx stream into the ctx's image, the copy out over there, and the ctx's next work behind the copy
+    int rc = previewRun(c, camera, params, nullptr, out);
+    if (rc) return rc;
+    if (!c->evAov) HIP_TRY(c, hipEventCreateWithFlags(&c->evAov, hipEventDisableTiming));
+    HIP_TRY(c, hipEventRecord(c->evAov, c->stream));
+    HIP_TRY(c, hipStreamWaitEvent(st, c->evAov, 0));
+    HIP_TRY(c, hipMemcpyAsync(device_out, c->rpOut, (size_t)c->W * c->H * 16, hipMemcpyDeviceToDevice, st));
+    HIP_TRY(c, hipEventRecord(c->evAov, st));
+    HIP_TRY(c, hipStreamWaitEvent(c->stream, c->evAov, 0));
+    return HR_OK;
+}
+
+int hr_reproject_preview_readback(hr_ctx *c, const hr_pass_params *camera, const hr_history_params *params, const float **rgba, int32_t *w, int32_t *h,
+                                  hr_reproject_preview_result *out)
+{
+    ENTER(c);
+    if (!rgba) FAIL(c, HR_ERR_INVALID, "null output");
+    int rc = previewRun(c, camera, params, nullptr, nullptr);
+    if (rc) return rc;
+    const size_t bytes = (size_t)c->W * c->H * 16;
+    if (c->rpPinnedBytes < bytes) {
+        if (c->rpPinned) hipHostFree(c->rpPinned);
+        c->rpPinned = nullptr, c->rpPinnedBytes = 0;
+        HIP_TRY(c, hipHostMalloc((void **)&c->rpPinned, bytes, hipHostMallocDefault));
+        c->rpPinnedBytes = bytes;
+    }
+    HIP_TRY(c, hipMemcpyAsync(c->rpPinned, c->rpOut, bytes, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipMemcpyAsync(c->rpResultHost, c->rpResult, kReprojectResultWords * 8, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    if (out) {
+        *out = hr_reproject_preview_result{};
+        out->own_pixels = c->rpResultHost[0], out->previewed_pixels = c->rpResultHost[1], out->empty_pixels = c->rpResultHost[2];
+    }
+    *rgba = c->rpPinned;
+    if (w) *w = c->W;
+    if (h) *h = c->H;
+    return HR_OK;
+}
+
+} // extern "C"
