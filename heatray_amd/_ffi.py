@@ -192,6 +192,28 @@ class DenoiseParams(C.Structure):
                 ("kernel", C.c_int32), ("reserved", C.c_uint32 * 3)]
 
 
+# every symbol include/hrcore_denoise_spatial.h declares (the denoiser with a spatial variance estimate for pixels with few samples).
+# Resolved lazily like the AOV symbols
+HR_DENOISE_SPATIAL_API_VERSION = 1
+HR_DENOISE_SPATIAL_BELOW_LOWEST, HR_DENOISE_SPATIAL_BELOW_HIGHEST = 2, 64
+HR_DENOISE_SPATIAL_MIN_TAPS_LOWEST, HR_DENOISE_SPATIAL_MIN_TAPS_HIGHEST = 2, 49
+DENOISE_SPATIAL_SYMBOLS = ["denoise_spatial_api_version", "denoise_spatial_default_params", "denoise_spatial", "denoise_spatial_readback", "denoise_spatial_display",
+                           "denoise_spatial_variance"]
+
+
+class DenoiseSpatialParams(C.Structure):
+    """hr_denoise_spatial_params"""
+    _fields_ = [("below", C.c_int32), ("min_taps", C.c_int32), ("reserved", C.c_uint32 * 6)]
+
+
+class DenoiseSpatialResult(C.Structure):
+    """hr_denoise_spatial_result"""
+    _fields_ = [("spatial_pixels", C.c_uint64), ("estimated_pixels", C.c_uint64), ("starved_pixels", C.c_uint64)]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
 # every symbol include/hrcore_adaptive.h declares (the sample mask and the error estimate that builds it).  Resolved lazily like the AOV symbols
 HR_ADAPTIVE_API_VERSION = 1
 HR_ADAPTIVE_MIN_SAMPLES_LOWEST, HR_ADAPTIVE_MIN_SAMPLES_HIGHEST, HR_ADAPTIVE_MAX_RADIUS = 2, 65536, 4
@@ -628,6 +650,51 @@ class Engine:
         display = display if display is not None else display_params()
         self._denoise_call("denoise_display", C.byref(params) if params is not None else None, C.byref(display), C.c_int32(fmt),
                            C.c_void_p(int(device_ptr)), None)
+
+    # -- denoiser with the spatial variance estimate (include/hrcore_denoise_spatial.h)
+    def _denoise_spatial_call(self, name, *args):
+        if not getattr(self, "_denoise_spatial_checked", False):
+            missing = [s for s in DENOISE_SPATIAL_SYMBOLS if not hasattr(self._lib, self._p + s)]
+            if missing:
+                raise EngineError(f"this library has no spatial variance estimate (lacks {[self._p + s for s in missing]})")
+            ver = getattr(self._lib, self._p + "denoise_spatial_api_version")
+            ver.restype = C.c_uint32
+            if ver() != HR_DENOISE_SPATIAL_API_VERSION:
+                raise EngineError(f"{self._p}denoise_spatial_api_version() = {ver()}, this binding was written against {HR_DENOISE_SPATIAL_API_VERSION}: "
+                                  "rebuild the library")
+            self._denoise_spatial_checked = True
+        self._call(name, *args)
+
+    def denoise_spatial(self, params=None, spatial=None, with_result=False):
+        """denoise() with a spatial variance estimate for the pixels that have fewer than spatial.below samples (one-sample pixels no
+        longer pass through unfiltered).  params: a DenoiseParams, spatial: a DenoiseSpatialParams
+        (heatray_amd.denoise_spatial.default_params()); None = the defaults.  with_result: (image, the DenoiseSpatialResult as a dict)."""
+        p = f32p()
+        w, h, n = C.c_int32(), C.c_int32(), C.c_uint32()
+        r = DenoiseSpatialResult()
+        self._denoise_spatial_call("denoise_spatial_readback", C.byref(params) if params is not None else None, C.byref(spatial) if spatial is not None else None,
+                                   C.byref(p), C.byref(w), C.byref(h), C.byref(n), C.byref(r))
+        img = np.ctypeslib.as_array(p, shape=(h.value, w.value, 4)).copy()
+        return (img, r.as_dict()) if with_result else img
+
+    def denoise_spatial_to_device(self, device_ptr, params=None, spatial=None, stream=None):
+        """Asynchronous: denoise_spatial's image (W x H float4) into device memory; ordered like denoise_to_device."""
+        self._denoise_spatial_call("denoise_spatial", C.byref(params) if params is not None else None, C.byref(spatial) if spatial is not None else None,
+                                   C.c_void_p(int(device_ptr)), C.c_void_p(stream or 0), None, None)
+
+    def denoise_spatial_display(self, device_ptr, display=None, fmt=HR_DISPLAY_RGBA8, params=None, spatial=None):
+        """Asynchronous display resolve of denoise_spatial's image into device memory (like denoise_display)."""
+        display = display if display is not None else display_params()
+        self._denoise_spatial_call("denoise_spatial_display", C.byref(params) if params is not None else None, C.byref(spatial) if spatial is not None else None,
+                                   C.byref(display), C.c_int32(fmt), C.c_void_p(int(device_ptr)), None)
+
+    def denoise_spatial_variance(self, params=None, spatial=None, with_result=False):
+        """The luminance variance of every pixel after the estimate, before the first iteration (H x W float32); for inspection."""
+        out = np.empty((self.height, self.width), dtype=np.float32)
+        r = DenoiseSpatialResult()
+        self._denoise_spatial_call("denoise_spatial_variance", C.byref(params) if params is not None else None, C.byref(spatial) if spatial is not None else None,
+                                   _ptr(out), C.byref(r))
+        return (out, r.as_dict()) if with_result else out
 
     # -- adaptive sampling (include/hrcore_adaptive.h)
     def _adaptive_call(self, name, *args):

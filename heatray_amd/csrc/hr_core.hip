@@ -10,6 +10,7 @@
 //   hr_pipeline.inl   ray memory, the macro step, batching and the packet selector, hr_render_pass, the step log
 //   hr_group.inl      context groups (include/hrcore_group.h): member threads, the assembly of the members' tiles
 //   hr_aov.inl        the AOV planes (include/hrcore_aov.h);  hr_denoise.inl  the denoiser over them (include/hrcore_denoise.h)
+//   hr_denoise_spatial.inl  the denoiser with a spatial variance estimate for pixels with few samples (include/hrcore_denoise_spatial.h)
 //   hr_adaptive.inl   the sample mask and the error estimate that builds it (include/hrcore_adaptive.h)
 //   hr_history.inl    history reprojection across a camera change (include/hrcore_history.h)
 //   hr_reproject.inl  its progressive form and the preview of unsampled pixels (include/hrcore_reproject.h)
@@ -147,6 +148,9 @@ static void aovFreePlanes(hr_ctx *c)
     hipFree(c->dnWork), hipFree(c->dnOut); // (the denoiser's buffers live and die with the planes it reads)
     if (c->dnPinned) hipHostFree(c->dnPinned);
     c->dnWork = c->dnOut = c->dnPinned = nullptr, c->dnPinnedBytes = 0;
+    hipFree(c->dnSpatialResult);
+    if (c->dnSpatialResultHost) hipHostFree(c->dnSpatialResultHost);
+    c->dnSpatialResult = c->dnSpatialResultHost = nullptr;
     if (c->aovPinned) hipHostFree(c->aovPinned);
     c->aovPinned = nullptr, c->aovPinnedBytes = 0;
 }
@@ -758,3 +762,6 @@ int hr_debug_trace(hr_ctx *c, int32_t n, const float *o, const float *d, const f
 
 // ------------------------------------------------------------------------------------------ progressive merge and preview
 #include "hr_reproject.inl"
+
+// ------------------------------------------------------------------------------------------ denoiser with the spatial variance estimate
+#include "hr_denoise_spatial.inl"

@@ -442,6 +442,7 @@ struct hr_ctx {
     float *dnOut = nullptr;     // the result when it does not go straight to the caller's memory (W x H float4)
     float *dnPinned = nullptr;  // hr_denoise_readback's host buffer
     size_t dnPinnedBytes = 0;
+    unsigned long long *dnSpatialResult = nullptr, *dnSpatialResultHost = nullptr; // kDenoiseSpatialResultWords device words (include/hrcore_denoise_spatial.h) and their pinned host copy: made and freed with dnWork
     // Adaptive sampling (include/hrcore_adaptive.h).  frame.mask is smWords while a mask is installed, null otherwise.  The buffers are made
     // by the first call that needs them and go with the frame (adaptiveFree: hr_frame_resize, hr_ctx_destroy).
     uint32_t *smWords = nullptr;  // the installed mask's words (sampleMaskWords)

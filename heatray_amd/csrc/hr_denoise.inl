@@ -45,8 +45,15 @@ static int denoiseEnsureBuffers(hr_ctx *c, bool needOut)
     return HR_OK;
 }
 
+// hr_denoise_spatial.inl's calls: the spatial variance estimate of include/hrcore_denoise_spatial.h between Prepare and the first iteration
+struct DenoiseSpatialRun {
+    hr_denoise_spatial_params p; // checked by the caller
+    bool varianceOnly;           // stop after the estimate: cv[1] holds its variance, no image is written
+};
+
 // Completes the passes, checks, and enqueues the filter on the ctx stream; the image goes to `out`, or to c->dnOut when out is null.
-static int denoiseRun(hr_ctx *c, const hr_denoise_params *params, float *out, uint32_t *passes)
+// Without `spatial` every launch is hr_denoise's.
+static int denoiseRun(hr_ctx *c, const hr_denoise_params *params, float *out, uint32_t *passes, const DenoiseSpatialRun *spatial = nullptr)
 {
     hr_denoise_params p;
     int rc = denoiseCheckParams(c, params, &p);
@@ -71,16 +78,25 @@ static int denoiseRun(hr_ctx *c, const hr_denoise_params *params, float *out, ui
         n = (uint32_t)(c->nextResolveOrder - c->frameZeroedAt);
         frame = c->fb();
     }
-    rc = denoiseEnsureBuffers(c, out == nullptr);
+    rc = denoiseEnsureBuffers(c, out == nullptr && !(spatial && spatial->varianceOnly));
     if (rc) return rc;
+    if (spatial && !c->dnSpatialResult) HIP_TRY(c, hipMalloc((void **)&c->dnSpatialResult, kDenoiseSpatialResultWords * 8));
+    if (spatial && !c->dnSpatialResultHost) HIP_TRY(c, hipHostMalloc((void **)&c->dnSpatialResultHost, kDenoiseSpatialResultWords * 8, hipHostMallocDefault));
     if (!out) out = c->dnOut;
     const size_t px = (size_t)c->W * c->H;
     DenoiseBufs b;
     b.cv[0] = c->dnWork, b.cv[1] = b.cv[0] + 4 * px, b.nd = b.cv[1] + 4 * px, b.ac = b.nd + 4 * px, b.grad = b.ac + 4 * px;
     launchDenoisePrepare(c->stream, c->W, c->H, frame, c->aovPlane[HR_AOV_PLANE_ALBEDO], c->aovPlane[HR_AOV_PLANE_NORMAL_DEPTH], c->aovPlane[HR_AOV_PLANE_MOMENTS], b);
-    if (p.iterations == 0) launchDenoiseFinish(c->stream, c->W, c->H, b, out);
-    for (int it = 0; it < p.iterations; ++it)
-        launchDenoiseAtrous(c->stream, c->W, c->H, b, it & 1, 1 << it, p, denoiseUseTiled(p, 1 << it), it == p.iterations - 1 ? out : nullptr);
+    int first = 0; // the half of the ping-pong the iterations start from
+    if (spatial) {
+        HIP_TRY(c, hipMemsetAsync(c->dnSpatialResult, 0, kDenoiseSpatialResultWords * 8, c->stream));
+        launchDenoiseSpatial(c->stream, c->W, c->H, frame, b, p, spatial->p, c->dnSpatialResult); // cv[0] -> cv[1]: the same colour, the estimated variance
+        first = 1;
+    }
+    const int iterations = (spatial && spatial->varianceOnly) ? -1 : p.iterations;
+    if (iterations == 0) launchDenoiseFinish(c->stream, c->W, c->H, b, out); // (reads cv[0]: the colour the estimate left as it was)
+    for (int it = 0; it < iterations; ++it)
+        launchDenoiseAtrous(c->stream, c->W, c->H, b, (it & 1) ^ first, 1 << it, p, denoiseUseTiled(p, 1 << it), it == iterations - 1 ? out : nullptr);
     HIP_TRY(c, hipGetLastError());
     if (passes) *passes = n;
     return HR_OK;

@@ -5,6 +5,7 @@
 #include "../../include/hrcore_group.h"
 #include "../../include/hrcore_aov.h"
 #include "../../include/hrcore_denoise.h"
+#include "../../include/hrcore_denoise_spatial.h"
 #include "../../include/hrcore_adaptive.h"
 #include "../../include/hrcore_history.h"
 #include "../../include/hrcore_reproject.h"
@@ -189,6 +190,13 @@ void launchDenoisePrepare(hipStream_t st, int W, int H, const float *frame, cons
 bool denoiseTiledHasStep(int step);
 void launchDenoiseAtrous(hipStream_t st, int W, int H, const DenoiseBufs &b, int src, int step, const hr_denoise_params &p, bool tiled, float *finalOut);
 void launchDenoiseFinish(hipStream_t st, int W, int H, const DenoiseBufs &b, float *out); // (no iteration: cv[0] remodulated)
+
+// ---- hr_denoise_spatial.hip (include/hrcore_denoise_spatial.h)
+// after launchDenoisePrepare: cv[1] = cv[0] with the variance after the spatial estimate (the iterations then start from src = 1);
+// frame: the frame the planes were prepared from (its alpha is n); result = {spatial, estimated, starved pixels}, zeroed by the caller
+static const size_t kDenoiseSpatialResultWords = 3;
+void launchDenoiseSpatial(hipStream_t st, int W, int H, const float *frame, const DenoiseBufs &b, const hr_denoise_params &p, const hr_denoise_spatial_params &sp,
+                          unsigned long long *result);
 
 // ---- hr_adaptive.hip (include/hrcore_adaptive.h)
 size_t sampleMaskWords(int W, int H); // 32-bit words of a frame's sample mask (FrameDev::mask)

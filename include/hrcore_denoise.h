@@ -17,6 +17,7 @@
  *   n >= 2:  e = M.rgb - (n * c) * c, e = e > 0 ? e : 0;  v = lum(((e / (n - 1)) / n) / (a * a))      variance of the mean
  *   n <  2:  v = 0: ONE sample has no variance estimate; the pixel passes through unfiltered (and still is its neighbours' tap).
  *            The filter starts working at two passes; interactive mode's one-sample blocks pass through.
+ *            (hrcore_denoise_spatial.h has calls that give such pixels a variance borrowed from their neighbours first.)
  *   l2 = (G.x G.x + G.y G.y) + G.z G.z;  N = G.xyz / sqrt_(l2) where hits > 0 and l2 > 0, else 0 0 0
  *   z = G.w / hits where hits > 0, else 0;   cov = hits / n
  *   facing(p, q) = (cov_p == 0 and cov_q == 0) or dot(N_p, N_q) > 0, dot = (x x + y y) + z z: only then does q lend p its variance or depth
