@@ -276,6 +276,18 @@ class ReprojectPreviewResult(C.Structure):
         return {k: getattr(self, k) for k, _ in self._fields_}
 
 
+# The optional headers: feature -> (its symbols, the version the binding was written against, what "this library has no ..." calls it);
+# the version function is <feature>_api_version.  Engine._feature_call checks a feature on its first call
+FEATURES = {
+    "aov": (AOV_SYMBOLS, HR_AOV_API_VERSION, "AOVs"),
+    "denoise": (DENOISE_SYMBOLS, HR_DENOISE_API_VERSION, "denoiser"),
+    "denoise_spatial": (DENOISE_SPATIAL_SYMBOLS, HR_DENOISE_SPATIAL_API_VERSION, "spatial variance estimate"),
+    "adaptive": (ADAPTIVE_SYMBOLS, HR_ADAPTIVE_API_VERSION, "adaptive sampling"),
+    "history": (HISTORY_SYMBOLS, HR_HISTORY_API_VERSION, "history reprojection"),
+    "reproject": (REPROJECT_SYMBOLS, HR_REPROJECT_API_VERSION, "progressive history merge"),
+}
+
+
 class GroupInfo(C.Structure):
     _fields_ = [("n_members", C.c_int32), ("device_ids", C.c_int32 * HR_GROUP_MAX_MEMBERS), ("owned_pixels", C.c_uint64 * HR_GROUP_MAX_MEMBERS)]
 
@@ -325,6 +337,23 @@ class Engine:
             le.restype = C.c_char_p
             msg = le(self._ctx)
             raise EngineError(f"{self._p}{name}: status {rc}: {msg.decode() if msg else ''}")
+
+    def _feature_call(self, feature, name, *args):
+        """_call for an entry point of an optional header (FEATURES).  Its symbols are resolved lazily, on the feature's first call: a
+        library without them (the CPU oracle) still makes an Engine, and the feature's calls raise EngineError."""
+        # (made here, not in __init__: the context group's class has an __init__ of its own that does not chain to Engine's)
+        checked = self.__dict__.setdefault("_features_checked", set())
+        if feature not in checked:
+            symbols, want, words = FEATURES[feature]
+            missing = [s for s in symbols if not hasattr(self._lib, self._p + s)]
+            if missing:
+                raise EngineError(f"this library has no {words} (lacks {[self._p + s for s in missing]})")
+            ver = getattr(self._lib, f"{self._p}{feature}_api_version")
+            ver.restype = C.c_uint32
+            if ver() != want:
+                raise EngineError(f"{self._p}{feature}_api_version() = {ver()}, this binding was written against {want}: rebuild the library")
+            checked.add(feature)
+        self._call(name, *args)
 
     def close(self):
         if self._ctx:
@@ -576,33 +605,21 @@ class Engine:
         return (a.copy() if copy else a), int(n.value)
 
     # -- AOVs (include/hrcore_aov.h)
-    def _aov_call(self, name, *args):
-        if not getattr(self, "_aov_checked", False):
-            missing = [s for s in AOV_SYMBOLS if not hasattr(self._lib, self._p + s)]
-            if missing:
-                raise EngineError(f"this library has no AOVs (lacks {[self._p + s for s in missing]})")
-            ver = getattr(self._lib, self._p + "aov_api_version")
-            ver.restype = C.c_uint32
-            if ver() != HR_AOV_API_VERSION:
-                raise EngineError(f"{self._p}aov_api_version() = {ver()}, this binding was written against {HR_AOV_API_VERSION}: rebuild the library")
-            self._aov_checked = True
-        self._call(name, *args)
-
     def set_aovs(self, mask):
         """Enable the AOV planes of `mask` (HR_AOV_SURFACE | HR_AOV_MOMENTS; 0 frees them).  Completes the passes in flight; a changed
         mask starts the planes at zero, so they hold the passes requested after this call."""
-        self._aov_call("aov_enable", C.c_uint32(int(mask)))
+        self._feature_call("aov", "aov_enable", C.c_uint32(int(mask)))
 
     def aov_mask(self):
         m = C.c_uint32()
-        self._aov_call("aov_mask", C.byref(m))
+        self._feature_call("aov", "aov_mask", C.byref(m))
         return int(m.value)
 
     def aov_plane(self, plane):
         """(H x W x 4 float32 copy of one plane, passes summed into it); completes the enqueued passes first."""
         p = f32p()
         w, h, n = C.c_int32(), C.c_int32(), C.c_uint64()
-        self._aov_call("aov_readback", C.c_int32(plane), C.byref(p), C.byref(w), C.byref(h), C.byref(n))
+        self._feature_call("aov", "aov_readback", C.c_int32(plane), C.byref(p), C.byref(w), C.byref(h), C.byref(n))
         return np.ctypeslib.as_array(p, shape=(h.value, w.value, 4)).copy(), int(n.value)
 
     def aovs(self):
@@ -617,54 +634,29 @@ class Engine:
 
     def aov_to_device(self, plane, device_ptr, stream=None):
         """Asynchronous copy of one plane (W x H float4) into device memory, e.g. a torch tensor; ordered like display_device."""
-        self._aov_call("aov_copy", C.c_int32(plane), C.c_void_p(int(device_ptr)), C.c_void_p(stream or 0))
+        self._feature_call("aov", "aov_copy", C.c_int32(plane), C.c_void_p(int(device_ptr)), C.c_void_p(stream or 0))
 
     # -- denoiser (include/hrcore_denoise.h)
-    def _denoise_call(self, name, *args):
-        if not getattr(self, "_denoise_checked", False):
-            missing = [s for s in DENOISE_SYMBOLS if not hasattr(self._lib, self._p + s)]
-            if missing:
-                raise EngineError(f"this library has no denoiser (lacks {[self._p + s for s in missing]})")
-            ver = getattr(self._lib, self._p + "denoise_api_version")
-            ver.restype = C.c_uint32
-            if ver() != HR_DENOISE_API_VERSION:
-                raise EngineError(f"{self._p}denoise_api_version() = {ver()}, this binding was written against {HR_DENOISE_API_VERSION}: rebuild the library")
-            self._denoise_checked = True
-        self._call(name, *args)
-
     def denoise(self, params=None, with_passes=False):
         """The denoised frame (H x W x 4 float32: rgb = mean colour, a = 1) of the passes rendered so far; needs both AOV masks enabled
         before the frame's first pass.  params: a DenoiseParams (heatray_amd.denoise.default_params()), None = the defaults."""
         p = f32p()
         w, h, n = C.c_int32(), C.c_int32(), C.c_uint32()
-        self._denoise_call("denoise_readback", C.byref(params) if params is not None else None, C.byref(p), C.byref(w), C.byref(h), C.byref(n))
+        self._feature_call("denoise", "denoise_readback", C.byref(params) if params is not None else None, C.byref(p), C.byref(w), C.byref(h), C.byref(n))
         img = np.ctypeslib.as_array(p, shape=(h.value, w.value, 4)).copy()
         return (img, int(n.value)) if with_passes else img
 
     def denoise_to_device(self, device_ptr, params=None, stream=None):
         """Asynchronous: the denoised frame (W x H float4) into device memory, e.g. a torch tensor; ordered like aov_to_device."""
-        self._denoise_call("denoise", C.byref(params) if params is not None else None, C.c_void_p(int(device_ptr)), C.c_void_p(stream or 0), None)
+        self._feature_call("denoise", "denoise", C.byref(params) if params is not None else None, C.c_void_p(int(device_ptr)), C.c_void_p(stream or 0), None)
 
     def denoise_display(self, device_ptr, display=None, fmt=HR_DISPLAY_RGBA8, params=None):
         """Asynchronous display resolve of the denoised frame into device memory (like display_device)."""
         display = display if display is not None else display_params()
-        self._denoise_call("denoise_display", C.byref(params) if params is not None else None, C.byref(display), C.c_int32(fmt),
+        self._feature_call("denoise", "denoise_display", C.byref(params) if params is not None else None, C.byref(display), C.c_int32(fmt),
                            C.c_void_p(int(device_ptr)), None)
 
     # -- denoiser with the spatial variance estimate (include/hrcore_denoise_spatial.h)
-    def _denoise_spatial_call(self, name, *args):
-        if not getattr(self, "_denoise_spatial_checked", False):
-            missing = [s for s in DENOISE_SPATIAL_SYMBOLS if not hasattr(self._lib, self._p + s)]
-            if missing:
-                raise EngineError(f"this library has no spatial variance estimate (lacks {[self._p + s for s in missing]})")
-            ver = getattr(self._lib, self._p + "denoise_spatial_api_version")
-            ver.restype = C.c_uint32
-            if ver() != HR_DENOISE_SPATIAL_API_VERSION:
-                raise EngineError(f"{self._p}denoise_spatial_api_version() = {ver()}, this binding was written against {HR_DENOISE_SPATIAL_API_VERSION}: "
-                                  "rebuild the library")
-            self._denoise_spatial_checked = True
-        self._call(name, *args)
-
     def denoise_spatial(self, params=None, spatial=None, with_result=False):
         """denoise() with a spatial variance estimate for the pixels that have fewer than spatial.below samples (one-sample pixels no
         longer pass through unfiltered).  params: a DenoiseParams, spatial: a DenoiseSpatialParams
@@ -672,60 +664,48 @@ class Engine:
         p = f32p()
         w, h, n = C.c_int32(), C.c_int32(), C.c_uint32()
         r = DenoiseSpatialResult()
-        self._denoise_spatial_call("denoise_spatial_readback", C.byref(params) if params is not None else None, C.byref(spatial) if spatial is not None else None,
-                                   C.byref(p), C.byref(w), C.byref(h), C.byref(n), C.byref(r))
+        self._feature_call("denoise_spatial", "denoise_spatial_readback", C.byref(params) if params is not None else None, C.byref(spatial) if spatial is not None else None,
+                           C.byref(p), C.byref(w), C.byref(h), C.byref(n), C.byref(r))
         img = np.ctypeslib.as_array(p, shape=(h.value, w.value, 4)).copy()
         return (img, r.as_dict()) if with_result else img
 
     def denoise_spatial_to_device(self, device_ptr, params=None, spatial=None, stream=None):
         """Asynchronous: denoise_spatial's image (W x H float4) into device memory; ordered like denoise_to_device."""
-        self._denoise_spatial_call("denoise_spatial", C.byref(params) if params is not None else None, C.byref(spatial) if spatial is not None else None,
-                                   C.c_void_p(int(device_ptr)), C.c_void_p(stream or 0), None, None)
+        self._feature_call("denoise_spatial", "denoise_spatial", C.byref(params) if params is not None else None, C.byref(spatial) if spatial is not None else None,
+                           C.c_void_p(int(device_ptr)), C.c_void_p(stream or 0), None, None)
 
     def denoise_spatial_display(self, device_ptr, display=None, fmt=HR_DISPLAY_RGBA8, params=None, spatial=None):
         """Asynchronous display resolve of denoise_spatial's image into device memory (like denoise_display)."""
         display = display if display is not None else display_params()
-        self._denoise_spatial_call("denoise_spatial_display", C.byref(params) if params is not None else None, C.byref(spatial) if spatial is not None else None,
-                                   C.byref(display), C.c_int32(fmt), C.c_void_p(int(device_ptr)), None)
+        self._feature_call("denoise_spatial", "denoise_spatial_display", C.byref(params) if params is not None else None, C.byref(spatial) if spatial is not None else None,
+                           C.byref(display), C.c_int32(fmt), C.c_void_p(int(device_ptr)), None)
 
     def denoise_spatial_variance(self, params=None, spatial=None, with_result=False):
         """The luminance variance of every pixel after the estimate, before the first iteration (H x W float32); for inspection."""
         out = np.empty((self.height, self.width), dtype=np.float32)
         r = DenoiseSpatialResult()
-        self._denoise_spatial_call("denoise_spatial_variance", C.byref(params) if params is not None else None, C.byref(spatial) if spatial is not None else None,
-                                   _ptr(out), C.byref(r))
+        self._feature_call("denoise_spatial", "denoise_spatial_variance", C.byref(params) if params is not None else None, C.byref(spatial) if spatial is not None else None,
+                           _ptr(out), C.byref(r))
         return (out, r.as_dict()) if with_result else out
 
     # -- adaptive sampling (include/hrcore_adaptive.h)
-    def _adaptive_call(self, name, *args):
-        if not getattr(self, "_adaptive_checked", False):
-            missing = [s for s in ADAPTIVE_SYMBOLS if not hasattr(self._lib, self._p + s)]
-            if missing:
-                raise EngineError(f"this library has no adaptive sampling (lacks {[self._p + s for s in missing]})")
-            ver = getattr(self._lib, self._p + "adaptive_api_version")
-            ver.restype = C.c_uint32
-            if ver() != HR_ADAPTIVE_API_VERSION:
-                raise EngineError(f"{self._p}adaptive_api_version() = {ver()}, this binding was written against {HR_ADAPTIVE_API_VERSION}: rebuild the library")
-            self._adaptive_checked = True
-        self._call(name, *args)
-
     def set_sample_mask(self, mask):
         """Install a sample mask (H x W, row 0 = bottom like the frame, non-zero = the pixel is sampled by the passes requested from now
         on), or remove it with None.  Completes the enqueued passes first; clear() and resize() remove the mask too."""
         if mask is None:
-            self._adaptive_call("sample_mask_set", None)
+            self._feature_call("adaptive", "sample_mask_set", None)
             return
         m = np.asarray(mask)
         m = np.ascontiguousarray(m if m.dtype == np.uint8 else m != 0, dtype=np.uint8)  # (bytes go as they are: any non-zero value counts)
         if m.shape != (self.height, self.width):
             raise ValueError(f"sample mask of shape {m.shape} for a frame of {(self.height, self.width)}")
-        self._adaptive_call("sample_mask_set", m.ctypes.data_as(C.POINTER(C.c_uint8)))
+        self._feature_call("adaptive", "sample_mask_set", m.ctypes.data_as(C.POINTER(C.c_uint8)))
 
     def sample_mask(self):
         """(the mask in force as H x W uint8 of 0 / 1, whether one is installed); all ones when there is none."""
         out = np.empty((self.height, self.width), dtype=np.uint8)
         inst = C.c_int32()
-        self._adaptive_call("sample_mask_get", out.ctypes.data_as(C.POINTER(C.c_uint8)), C.byref(inst))
+        self._feature_call("adaptive", "sample_mask_get", out.ctypes.data_as(C.POINTER(C.c_uint8)), C.byref(inst))
         return out, bool(inst.value)
 
     def adaptive_update(self, params=None, install=True):
@@ -733,84 +713,60 @@ class Engine:
         sample mask from it and, with install, put it in force.  params: an AdaptiveParams (heatray_amd.adaptive.default_params()),
         None = the defaults.  Returns the AdaptiveResult."""
         r = AdaptiveResult()
-        self._adaptive_call("adaptive_update", C.byref(params) if params is not None else None, C.c_int32(int(bool(install))), C.byref(r))
+        self._feature_call("adaptive", "adaptive_update", C.byref(params) if params is not None else None, C.c_int32(int(bool(install))), C.byref(r))
         return r
 
     def adaptive_error_to_device(self, device_ptr, stream=None):
         """Asynchronous copy of the last adaptive_update's error map (W x H floats) into device memory; ordered like aov_to_device."""
-        self._adaptive_call("adaptive_error_copy", C.c_void_p(int(device_ptr)), C.c_void_p(stream or 0))
+        self._feature_call("adaptive", "adaptive_error_copy", C.c_void_p(int(device_ptr)), C.c_void_p(stream or 0))
 
     def adaptive_error(self):
         """The error map of the last adaptive_update as H x W float32 (+inf: fewer than min_samples samples)."""
         out = np.empty((self.height, self.width), dtype=np.float32)
-        self._adaptive_call("adaptive_error_readback", _ptr(out))
+        self._feature_call("adaptive", "adaptive_error_readback", _ptr(out))
         return out
 
     # -- history reprojection (include/hrcore_history.h)
-    def _history_call(self, name, *args):
-        if not getattr(self, "_history_checked", False):
-            missing = [s for s in HISTORY_SYMBOLS if not hasattr(self._lib, self._p + s)]
-            if missing:
-                raise EngineError(f"this library has no history reprojection (lacks {[self._p + s for s in missing]})")
-            ver = getattr(self._lib, self._p + "history_api_version")
-            ver.restype = C.c_uint32
-            if ver() != HR_HISTORY_API_VERSION:
-                raise EngineError(f"{self._p}history_api_version() = {ver()}, this binding was written against {HR_HISTORY_API_VERSION}: rebuild the library")
-            self._history_checked = True
-        self._call(name, *args)
-
     def history_capture(self, pass_params):
         """Turn the frame and the three AOV planes (set_aovs(HR_AOV_SURFACE | HR_AOV_MOMENTS) before the first pass) into the history, as
         seen by the camera of `pass_params` (view_matrix, fov_tan, aspect_ratio).  The history survives clear()."""
-        self._history_call("history_capture", C.byref(pass_params))
+        self._feature_call("history", "history_capture", C.byref(pass_params))
 
     def history_merge(self, pass_params, params=None):
         """Add the captured history to the frame and the planes of the view being rendered with `pass_params`; once per clear().  params: a
         HistoryParams (heatray_amd.history.default_params()), None = the defaults.  Returns the HistoryResult as a dict."""
         r = HistoryResult()
-        self._history_call("history_merge", C.byref(pass_params), C.byref(params) if params is not None else None, C.byref(r))
+        self._feature_call("history", "history_merge", C.byref(pass_params), C.byref(params) if params is not None else None, C.byref(r))
         return r.as_dict()
 
     def history_drop(self):
-        self._history_call("history_drop")
+        self._feature_call("history", "history_drop")
 
     def history_info(self):
         """(is there a captured history, the complete passes of the frame it was captured from)"""
         have, n = C.c_int32(), C.c_uint32()
-        self._history_call("history_info", C.byref(have), C.byref(n))
+        self._feature_call("history", "history_info", C.byref(have), C.byref(n))
         return bool(have.value), int(n.value)
 
     def history(self):
         """The captured history as 3 x H x W x 4 float32: H0 (mean colour, samples), H1 (mean second moment, coverage), H2 (unit normal,
         mean depth; +inf: sky)."""
         out = np.empty((3, self.height, self.width, 4), dtype=np.float32)
-        self._history_call("history_readback", _ptr(out))
+        self._feature_call("history", "history_readback", _ptr(out))
         return out
 
     # -- progressive merge and preview (include/hrcore_reproject.h)
-    def _reproject_call(self, name, *args):
-        if not getattr(self, "_reproject_checked", False):
-            missing = [s for s in REPROJECT_SYMBOLS if not hasattr(self._lib, self._p + s)]
-            if missing:
-                raise EngineError(f"this library has no progressive history merge (lacks {[self._p + s for s in missing]})")
-            ver = getattr(self._lib, self._p + "reproject_api_version")
-            ver.restype = C.c_uint32
-            if ver() != HR_REPROJECT_API_VERSION:
-                raise EngineError(f"{self._p}reproject_api_version() = {ver()}, this binding was written against {HR_REPROJECT_API_VERSION}: rebuild the library")
-            self._reproject_checked = True
-        self._call(name, *args)
-
     def reproject_merge(self, pass_params, params=None):
         """history_merge's progressive form: the sampled pixels no earlier call has examined since clear() take over their history; any
         number of calls per clear().  params: a HistoryParams, None = the defaults.  Returns the ReprojectResult as a dict."""
         r = ReprojectResult()
-        self._reproject_call("reproject_merge", C.byref(pass_params), C.byref(params) if params is not None else None, C.byref(r))
+        self._feature_call("reproject", "reproject_merge", C.byref(pass_params), C.byref(params) if params is not None else None, C.byref(r))
         return r.as_dict()
 
     def reproject_examined(self):
         """The examined bits as H x W bool (row 0 = bottom like the frame)."""
         out = np.empty((self.height, self.width), dtype=np.uint8)
-        self._reproject_call("reproject_examined_get", out.ctypes.data_as(C.POINTER(C.c_uint8)))
+        self._feature_call("reproject", "reproject_examined_get", out.ctypes.data_as(C.POINTER(C.c_uint8)))
         return out.astype(bool)
 
     def reproject_preview(self, pass_params, params=None):
@@ -819,14 +775,14 @@ class Engine:
         p = f32p()
         w, h = C.c_int32(), C.c_int32()
         r = ReprojectPreviewResult()
-        self._reproject_call("reproject_preview_readback", C.byref(pass_params), C.byref(params) if params is not None else None, C.byref(p), C.byref(w), C.byref(h),
-                             C.byref(r))
+        self._feature_call("reproject", "reproject_preview_readback", C.byref(pass_params), C.byref(params) if params is not None else None, C.byref(p), C.byref(w), C.byref(h),
+                           C.byref(r))
         return np.ctypeslib.as_array(p, shape=(h.value, w.value, 4)).copy(), r.as_dict()
 
     def reproject_preview_to_device(self, device_ptr, pass_params, params=None, stream=None):
         """Asynchronous: the preview (W x H float4) into device memory, e.g. a torch tensor; ordered like denoise_to_device."""
-        self._reproject_call("reproject_preview", C.byref(pass_params), C.byref(params) if params is not None else None, C.c_void_p(int(device_ptr)),
-                             C.c_void_p(stream or 0), None)
+        self._feature_call("reproject", "reproject_preview", C.byref(pass_params), C.byref(params) if params is not None else None, C.c_void_p(int(device_ptr)),
+                           C.c_void_p(stream or 0), None)
 
     def debug_trace(self, origins, dirs, tmax=None, skip_prim=None, any_hit=False):
         o, d = _f32(origins).reshape(-1, 3), _f32(dirs).reshape(-1, 3)

@@ -8,14 +8,15 @@
 //   k_adaptive_mask    a workgroup owns a tile of 64 x 16 pixels: it stages the unconverged flags of the tile and a halo of `radius`
 //                      as bytes in LDS, takes the separable maximum (rows, then columns) and writes the mask one bit per pixel: a
 //                      wave's 64 decisions of one row gathered with __ballot, the two words stored by lanes 0 and 32.  The counts
-//                      (popcounts of the ballots) and the largest finite error (as an ordered integer) are reduced in LDS and go to
-//                      the result block with one atomic each per workgroup: integer adds and a maximum, so the result does not depend
-//                      on the order workgroups finish in.
+//                      (popcounts of the ballots, hr_post_device.h) and the largest finite error (as an ordered integer) are reduced in
+//                      LDS and go to the result block with one atomic each per workgroup: integer adds and a maximum, so the result does
+//                      not depend on the order workgroups finish in.
 //   k_mask_pack / k_mask_unpack   the byte form of hr_sample_mask_set / _get <-> the words (the same ballot)
 // No scratch, no float atomics.
 #include "hr_math.h"
 #include "hr_adaptive.h"
 #include "hr_kernels.h"
+#include "hr_post_device.h"
 
 namespace hr {
 
@@ -50,7 +51,7 @@ __global__ __launch_bounds__(256) void k_adaptive_mask(int W, int H, int radius,
     __shared__ uint32_t sRed[4];
     const int tilesX = (W + kAdTileW - 1) / kAdTileW; // (a one-dimensional grid: no bound on the image's height)
     const int x0 = (int)(blockIdx.x % (uint32_t)tilesX) * kAdTileW, y0 = (int)(blockIdx.x / (uint32_t)tilesX) * kAdTileH;
-    if (threadIdx.x < 4u) sRed[threadIdx.x] = 0u;
+    wgCountersZero<4>(sRed);
     for (int e = (int)threadIdx.x; e < kAdSideH * kAdSideW; e += 256) {
         const int lx = e % kAdSideW - kAdHalo, ly = e / kAdSideW - kAdHalo; // relative to the tile
         const int gx = x0 + lx, gy = y0 + ly;
@@ -84,7 +85,7 @@ __global__ __launch_bounds__(256) void k_adaptive_mask(int W, int H, int radius,
         }
         const unsigned long long bits = __ballot(on);
         nAct += (uint32_t)__popcll(bits);
-        nUnc += (uint32_t)__popcll(__ballot(unc));
+        nUnc += waveCount(unc);
         storeMaskWords(words, W, x0, gy, bits, lane);
     }
 #pragma unroll
@@ -96,7 +97,7 @@ __global__ __launch_bounds__(256) void k_adaptive_mask(int W, int H, int radius,
         atomicAdd(&sRed[0], nUnc), atomicAdd(&sRed[1], nAct), atomicMax(&sRed[2], maxBits);
     }
     __syncthreads();
-    if (threadIdx.x == 0u) {
+    if (threadIdx.x == 0u) { // (32-bit words and a maximum among them: not wgCountersFlush's form)
         if (sRed[0]) atomicAdd(&result[0], sRed[0]);
         if (sRed[1]) atomicAdd(&result[1], sRed[1]);
         if (sRed[2]) atomicMax(&result[2], sRed[2]);

@@ -23,17 +23,6 @@ static int adaptiveCheckParams(hr_ctx *c, const hr_adaptive_params *in, hr_adapt
     return HR_OK;
 }
 
-// MOMENTS on, and zeroed when the frame was: the plane holds the frame's passes
-static int adaptiveCheckPlane(hr_ctx *c)
-{
-    if (!(c->aovMask & HR_AOV_MOMENTS))
-        FAIL(c, HR_ERR_INVALID, "adaptive sampling needs the sample moments: hr_aov_enable(HR_AOV_MOMENTS) before the frame's first pass (enabled mask: " +
-                                    std::to_string(c->aovMask) + ")");
-    if (c->aovZeroedAt != c->frameZeroedAt)
-        FAIL(c, HR_ERR_INVALID, "adaptive: the MOMENTS plane was enabled after the frame's first pass and does not hold the frame's passes: hr_clear, or hr_aov_enable before rendering");
-    return HR_OK;
-}
-
 static int sampleMaskEnsure(hr_ctx *c, bool bytesToo)
 {
     if (!c->smWords) HIP_TRY(c, hipMalloc((void **)&c->smWords, sampleMaskWords(c->W, c->H) * 4));
@@ -142,42 +131,28 @@ int hr_adaptive_update(hr_ctx *c, const hr_adaptive_params *params, int32_t inst
     hr_adaptive_params p;
     int rc = adaptiveCheckParams(c, params, &p);
     if (rc) return rc;
-    if (c->W <= 0) FAIL(c, HR_ERR_INVALID, "no frame");
+    if (c->W <= 0) FAIL(c, HR_ERR_INVALID, "no frame"); // (asked first: a sharded context without a frame hears this, not frameReady's refusal)
     uint32_t n = 0;
     const float *frame = nullptr;
-    if (c->grp) {
-        rc = adaptiveCheckPlane(c); // (the group's own mask: hr_aov_enable on the handle)
-        if (rc == HR_OK) rc = groupAll(c, [](hr_ctx *m, int) { return adaptiveCheckPlane(m); });
-        if (rc == HR_OK) rc = groupAssemble(c, true, &n, nullptr);
-        if (rc == HR_OK) rc = groupAovAssemble(c, HR_AOV_PLANE_MOMENTS, nullptr);
-        if (rc) return rc;
-        frame = c->fbInternal;
-    } else {
-        if (c->world > 1)
-            FAIL(c, HR_ERR_INVALID, "adaptive: a tile-sharded context (world > 1) holds only its own tiles and the mask's dilation reads across them: use a context group, which assembles the frame");
-        rc = adaptiveCheckPlane(c);
-        if (rc == HR_OK) rc = drainPipeline(c);
-        if (rc == HR_OK) rc = overflowCheck(c);
-        if (rc) return rc;
-        n = (uint32_t)(c->nextResolveOrder - c->frameZeroedAt);
-        frame = c->fb();
-    }
+    const FrameNeed need{HR_AOV_MOMENTS, "adaptive", "the mask's dilation", true, false, "adaptive sampling needs the sample moments: hr_aov_enable(HR_AOV_MOMENTS)",
+                         "adaptive: the MOMENTS plane was enabled after the frame's first pass and does not hold"};
+    rc = frameReady(c, need, &frame, &n);
+    if (rc) return rc;
     const size_t px = (size_t)c->W * c->H, maskBytes = sampleMaskWords(c->W, c->H) * 4;
     if (!c->adError) HIP_TRY(c, hipMalloc((void **)&c->adError, px * 4));
     if (!c->adWords) HIP_TRY(c, hipMalloc((void **)&c->adWords, maskBytes));
-    if (!c->adResult) HIP_TRY(c, hipMalloc((void **)&c->adResult, kAdaptiveResultWords * 4));
-    if (!c->adResultHost) HIP_TRY(c, hipHostMalloc((void **)&c->adResultHost, kAdaptiveResultWords * 4, hipHostMallocDefault));
+    HIP_TRY(c, c->ad.ensure(kAdaptiveResultWords));
     if (install) {
         rc = sampleMaskEnsure(c, false);
         if (rc) return rc;
     }
-    HIP_TRY(c, hipMemsetAsync(c->adResult, 0, kAdaptiveResultWords * 4, c->stream));
+    HIP_TRY(c, c->ad.zero(c->stream));
     launchAdaptiveError(c->stream, c->W, c->H, frame, c->aovPlane[HR_AOV_PLANE_MOMENTS], p, c->adError);
-    launchAdaptiveMask(c->stream, c->W, c->H, c->adError, p, c->adWords, c->adResult);
+    launchAdaptiveMask(c->stream, c->W, c->H, c->adError, p, c->adWords, c->ad.dev);
     HIP_TRY(c, hipGetLastError());
     c->adErrorValid = true;
     if (install) HIP_TRY(c, hipMemcpyAsync(c->smWords, c->adWords, maskBytes, hipMemcpyDeviceToDevice, c->stream));
-    HIP_TRY(c, hipMemcpyAsync(c->adResultHost, c->adResult, kAdaptiveResultWords * 4, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, c->ad.fetch(c->stream));
     HIP_TRY(c, hipStreamSynchronize(c->stream));
     if (install) {
         if (c->grp) {
@@ -188,8 +163,8 @@ int hr_adaptive_update(hr_ctx *c, const hr_adaptive_params *params, int32_t inst
     }
     if (out) {
         *out = hr_adaptive_result{};
-        out->unconverged_pixels = c->adResultHost[0], out->active_pixels = c->adResultHost[1];
-        std::memcpy(&out->max_error, &c->adResultHost[2], 4);
+        out->unconverged_pixels = c->ad.host[0], out->active_pixels = c->ad.host[1];
+        std::memcpy(&out->max_error, &c->ad.host[2], 4);
         out->passes = n;
     }
     return HR_OK;
@@ -201,19 +176,7 @@ int hr_adaptive_error_copy(hr_ctx *c, void *device_out, void *stream)
     if (!device_out) FAIL(c, HR_ERR_INVALID, "null output");
     if (c->W <= 0) FAIL(c, HR_ERR_INVALID, "no frame");
     if (!c->adErrorValid) FAIL(c, HR_ERR_INVALID, "adaptive: no error map: hr_adaptive_update has not run since the frame was last resized");
-    const size_t bytes = (size_t)c->W * c->H * sizeof(float);
-    hipStream_t st = stream ? (hipStream_t)stream : c->stream;
-    if (st != c->stream) {
-        if (!c->evAov) HIP_TRY(c, hipEventCreateWithFlags(&c->evAov, hipEventDisableTiming));
-        HIP_TRY(c, hipEventRecord(c->evAov, c->stream));
-        HIP_TRY(c, hipStreamWaitEvent(st, c->evAov, 0));
-    }
-    HIP_TRY(c, hipMemcpyAsync(device_out, c->adError, bytes, hipMemcpyDeviceToDevice, st));
-    if (st != c->stream) { // the next update rewrites the map: behind the copy
-        HIP_TRY(c, hipEventRecord(c->evAov, st));
-        HIP_TRY(c, hipStreamWaitEvent(c->stream, c->evAov, 0));
-    }
-    return HR_OK;
+    return copyOutOnStream(c, device_out, c->adError, (size_t)c->W * c->H * sizeof(float), stream); // (the next update rewrites the map: behind the copy)
 }
 
 int hr_adaptive_error_readback(hr_ctx *c, float *host_out)

@@ -14,34 +14,6 @@ static int aovCheckPlane(hr_ctx *c, int32_t plane)
     return HR_OK;
 }
 
-static int aovEnsurePinned(hr_ctx *c, size_t bytes)
-{
-    if (c->aovPinnedBytes >= bytes) return HR_OK;
-    if (c->aovPinned) hipHostFree(c->aovPinned);
-    c->aovPinned = nullptr, c->aovPinnedBytes = 0;
-    HIP_TRY(c, hipHostMalloc((void **)&c->aovPinned, bytes, hipHostMallocDefault));
-    c->aovPinnedBytes = bytes;
-    return HR_OK;
-}
-
-// the plane (already complete on c->stream) -> device_out on `stream`, ordered after the work on c->stream and before what follows there
-static int aovCopyOut(hr_ctx *c, int32_t plane, void *out, void *stream)
-{
-    const size_t bytes = (size_t)c->W * c->H * 4 * sizeof(float);
-    hipStream_t st = stream ? (hipStream_t)stream : c->stream;
-    if (st != c->stream) {
-        if (!c->evAov) HIP_TRY(c, hipEventCreateWithFlags(&c->evAov, hipEventDisableTiming));
-        HIP_TRY(c, hipEventRecord(c->evAov, c->stream));
-        HIP_TRY(c, hipStreamWaitEvent(st, c->evAov, 0));
-    }
-    HIP_TRY(c, hipMemcpyAsync(out, c->aovPlane[plane], bytes, hipMemcpyDeviceToDevice, st));
-    if (st != c->stream) { // the next resolve (or gather) rewrites the plane: behind the copy
-        HIP_TRY(c, hipEventRecord(c->evAov, st));
-        HIP_TRY(c, hipStreamWaitEvent(c->stream, c->evAov, 0));
-    }
-    return HR_OK;
-}
-
 // ---- context groups: every member holds its own planes (its tiles); the group's planes on the first device are assembled like the frame
 static int groupAovEnable(hr_ctx *c, uint32_t mask)
 {
@@ -150,7 +122,7 @@ int hr_aov_readback(hr_ctx *c, int32_t plane, const float **rgba, int32_t *w, in
         rc = drainPipeline(c);
         n = c->nextResolveOrder - c->aovZeroedAt;
     }
-    if (rc == HR_OK) rc = aovEnsurePinned(c, bytes);
+    if (rc == HR_OK) rc = growPinned(c, c->aovPinned, c->aovPinnedBytes, bytes);
     if (rc) return rc;
     HIP_TRY(c, hipMemcpyAsync(c->aovPinned, c->aovPlane[plane], bytes, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(c, hipStreamSynchronize(c->stream));
@@ -173,7 +145,7 @@ int hr_aov_copy(hr_ctx *c, int32_t plane, void *device_out, void *stream)
     if (rc) return rc;
     rc = c->grp ? groupAovAssemble(c, plane, nullptr) : drainPipeline(c);
     if (rc) return rc;
-    return aovCopyOut(c, plane, device_out, stream);
+    return copyOutOnStream(c, device_out, c->aovPlane[plane], (size_t)c->W * c->H * 4 * sizeof(float), stream); // (the next resolve or gather rewrites the plane: behind the copy)
 }
 
 } // extern "C"

@@ -9,6 +9,8 @@
 //   hr_scene.inl      geometry ingest, commit (build / refit / tree cache), textures, materials, lights, sample tables
 //   hr_pipeline.inl   ray memory, the macro step, batching and the packet selector, hr_render_pass, the step log
 //   hr_group.inl      context groups (include/hrcore_group.h): member threads, the assembly of the members' tiles
+//   hr_postprocess.inl  what the sections below share: the copy out on a caller's stream, the pinned read-back buffers, "is the frame
+//                     ready for a full-frame post-process?" (their result counters: ResultCounters in hr_ctx.h)
 //   hr_aov.inl        the AOV planes (include/hrcore_aov.h);  hr_denoise.inl  the denoiser over them (include/hrcore_denoise.h)
 //   hr_denoise_spatial.inl  the denoiser with a spatial variance estimate for pixels with few samples (include/hrcore_denoise_spatial.h)
 //   hr_adaptive.inl   the sample mask and the error estimate that builds it (include/hrcore_adaptive.h)
@@ -148,9 +150,7 @@ static void aovFreePlanes(hr_ctx *c)
     hipFree(c->dnWork), hipFree(c->dnOut); // (the denoiser's buffers live and die with the planes it reads)
     if (c->dnPinned) hipHostFree(c->dnPinned);
     c->dnWork = c->dnOut = c->dnPinned = nullptr, c->dnPinnedBytes = 0;
-    hipFree(c->dnSpatialResult);
-    if (c->dnSpatialResultHost) hipHostFree(c->dnSpatialResultHost);
-    c->dnSpatialResult = c->dnSpatialResultHost = nullptr;
+    c->dnSpatial.free();
     if (c->aovPinned) hipHostFree(c->aovPinned);
     c->aovPinned = nullptr, c->aovPinnedBytes = 0;
 }
@@ -178,9 +178,9 @@ static int aovAllocPlanes(hr_ctx *c)
 // Adaptive sampling (include/hrcore_adaptive.h): the mask and the update's buffers live and die with the frame's size
 static void adaptiveFree(hr_ctx *c)
 {
-    hipFree(c->smWords), hipFree(c->smBytes), hipFree(c->adError), hipFree(c->adWords), hipFree(c->adResult);
-    if (c->adResultHost) hipHostFree(c->adResultHost);
-    c->smWords = c->adWords = c->adResult = c->adResultHost = nullptr, c->smBytes = nullptr, c->adError = nullptr;
+    hipFree(c->smWords), hipFree(c->smBytes), hipFree(c->adError), hipFree(c->adWords);
+    c->ad.free();
+    c->smWords = c->adWords = nullptr, c->smBytes = nullptr, c->adError = nullptr;
     c->adErrorValid = false;
     c->frame.mask = nullptr;
 }
@@ -188,19 +188,19 @@ static void adaptiveFree(hr_ctx *c)
 // History reprojection (include/hrcore_history.h): the history goes with the frame's size, not with its contents
 static void historyFree(hr_ctx *c)
 {
-    hipFree(c->hsHist), hipFree(c->hsResult);
-    if (c->hsResultHost) hipHostFree(c->hsResultHost);
-    c->hsHist = nullptr, c->hsResult = c->hsResultHost = nullptr;
+    hipFree(c->hsHist);
+    c->hs.free();
+    c->hsHist = nullptr;
     c->hsCaptured = c->hsMerged = false, c->hsPasses = 0;
 }
 
 // Progressive merge and preview (include/hrcore_reproject.h): the examined bits and the preview's buffers go with the frame's size
 static void reprojectFree(hr_ctx *c)
 {
-    hipFree(c->rpExamined), hipFree(c->rpResult), hipFree(c->rpOut);
-    if (c->rpResultHost) hipHostFree(c->rpResultHost);
+    hipFree(c->rpExamined), hipFree(c->rpOut);
+    c->rp.free();
     if (c->rpPinned) hipHostFree(c->rpPinned);
-    c->rpExamined = c->rpResult = c->rpResultHost = nullptr, c->rpOut = c->rpPinned = nullptr, c->rpPinnedBytes = 0;
+    c->rpExamined = nullptr, c->rpOut = c->rpPinned = nullptr, c->rpPinnedBytes = 0;
     c->rpStale = true, c->rpMerged = false;
 }
 
@@ -747,6 +747,9 @@ int hr_debug_trace(hr_ctx *c, int32_t n, const float *o, const float *d, const f
 
 // ------------------------------------------------------------------------------------------ context groups
 #include "hr_group.inl"
+
+// ------------------------------------------------------------------------------------------ what the post-process sections share
+#include "hr_postprocess.inl"
 
 // ------------------------------------------------------------------------------------------ AOVs
 #include "hr_aov.inl"

@@ -59,6 +59,28 @@ static const int kMaxSlots = 2 * kMaxSegs; // passes in flight over all groups
 #define HR_BATCH_CAP 32 // most passes injected per macro step (small frames / tile shards reach it: 1/8 of a 1080p frame runs 6.6 % faster with 32 than with 12, profiles/r2p_shard_batch.txt)
 #endif
 
+// The result counters of a post-process feature: a few device words its kernel adds into and their pinned host copy.  A call runs
+// ensure, zero, its launches and fetch (each under HIP_TRY), synchronises the stream and fills its result struct from `host`.
+template <class Word> struct ResultCounters {
+    Word *dev = nullptr, *host = nullptr;
+    size_t words = 0;
+    hipError_t ensure(size_t n) // both buffers of n words, made by the first call
+    {
+        words = n;
+        hipError_t e = dev ? hipSuccess : hipMalloc((void **)&dev, n * sizeof(Word));
+        return e == hipSuccess && !host ? hipHostMalloc((void **)&host, n * sizeof(Word), hipHostMallocDefault) : e;
+    }
+    hipError_t zero(hipStream_t st) { return hipMemsetAsync(dev, 0, words * sizeof(Word), st); }
+    // enqueues dev -> host and does not wait: the caller synchronises `st`, once, with whatever else it copies back
+    hipError_t fetch(hipStream_t st) { return hipMemcpyAsync(host, dev, words * sizeof(Word), hipMemcpyDeviceToHost, st); }
+    void free()
+    {
+        hipFree(dev);
+        if (host) hipHostFree(host);
+        dev = host = nullptr, words = 0;
+    }
+};
+
 struct hr_ctx {
     int device = 0;
     hipStream_t stream = nullptr;
@@ -435,22 +457,21 @@ struct hr_ctx {
     float *aovPinned = nullptr;                       // hr_aov_readback's host buffer
     size_t aovPinnedBytes = 0;
     unsigned long long aovZeroedAt = 0;               // value of nextResolveOrder when the planes were last zeroed
-    hipEvent_t evAov = nullptr;                       // orders hr_aov_copy on a foreign stream against the resolves
+    hipEvent_t evAov = nullptr;                       // orders a copy out on a foreign stream against the ctx stream (copyOutOnStream)
     // Denoiser (include/hrcore_denoise.h): working planes and result image, allocated by the first call, freed with the AOV planes
     unsigned long long frameZeroedAt = 0; // value of nextResolveOrder when the frame was last zeroed (hr_clear, hr_frame_resize): the planes hold the frame's passes when aovZeroedAt equals it
     float *dnWork = nullptr;    // kDenoiseBytesPerPixel x W x H, cut into DenoiseBufs
     float *dnOut = nullptr;     // the result when it does not go straight to the caller's memory (W x H float4)
     float *dnPinned = nullptr;  // hr_denoise_readback's host buffer
     size_t dnPinnedBytes = 0;
-    unsigned long long *dnSpatialResult = nullptr, *dnSpatialResultHost = nullptr; // kDenoiseSpatialResultWords device words (include/hrcore_denoise_spatial.h) and their pinned host copy: made and freed with dnWork
+    ResultCounters<unsigned long long> dnSpatial; // kDenoiseSpatialResultWords (include/hrcore_denoise_spatial.h): made and freed with dnWork
     // Adaptive sampling (include/hrcore_adaptive.h).  frame.mask is smWords while a mask is installed, null otherwise.  The buffers are made
     // by the first call that needs them and go with the frame (adaptiveFree: hr_frame_resize, hr_ctx_destroy).
     uint32_t *smWords = nullptr;  // the installed mask's words (sampleMaskWords)
     uint8_t *smBytes = nullptr;   // W x H bytes: staging of the byte form (hr_sample_mask_set / _get)
     float *adError = nullptr;     // W x H floats: the error map of the last hr_adaptive_update
     uint32_t *adWords = nullptr;  // the mask that update built (copied to smWords when it is installed)
-    uint32_t *adResult = nullptr; // kAdaptiveResultWords device words ...
-    uint32_t *adResultHost = nullptr; // ... and their pinned host copy
+    ResultCounters<uint32_t> ad;  // kAdaptiveResultWords
     bool adErrorValid = false;    // adError holds an update's map at this frame size
     // History reprojection (include/hrcore_history.h).  The history survives hr_clear; it goes with the frame's size (historyFree:
     // hr_frame_resize, hr_history_drop, hr_ctx_destroy).
@@ -459,13 +480,13 @@ struct hr_ctx {
     uint32_t hsPasses = 0;            // complete passes of the frame it was captured from
     float hsView[16] = {0}, hsFovTan = 0.0f, hsAspect = 0.0f; // ... and its camera
     bool hsMerged = false;            // the history has been merged into the frame since its last hr_clear
-    unsigned long long *hsResult = nullptr, *hsResultHost = nullptr; // kHistoryResultWords device words and their pinned host copy
+    ResultCounters<unsigned long long> hs; // kHistoryResultWords
     // Progressive merge and preview (include/hrcore_reproject.h).  Everything here goes with the frame's size (reprojectFree: hr_frame_resize,
     // hr_ctx_destroy); hr_clear marks the examined bits stale and the next hr_reproject_merge zeroes them.
     unsigned long long *rpExamined = nullptr; // rpExaminedWords(W, H) words: one per 8 x 8 block of pixels
     bool rpStale = true;                      // the bits belong to an earlier frame (or were never zeroed): all pixels count as not examined
     bool rpMerged = false;                    // hr_reproject_merge has merged into the frame since its last hr_clear (hsMerged is set with it)
-    unsigned long long *rpResult = nullptr, *rpResultHost = nullptr; // kReprojectResultWords device words and their pinned host copy
+    ResultCounters<unsigned long long> rp;    // kReprojectResultWords (the preview uses the first three)
     float *rpOut = nullptr;                   // the preview when it does not go straight to the caller's memory (W x H float4)
     float *rpPinned = nullptr;                // hr_reproject_preview_readback's host buffer
     size_t rpPinnedBytes = 0;

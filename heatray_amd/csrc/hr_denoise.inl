@@ -1,5 +1,6 @@
 // hr_denoise.inl — a section of hr_core.hip (included at its end): the entry points of include/hrcore_denoise.h.  The kernels are in
-// hr_denoise.hip; the buffers' life follows the AOV planes' (aovFreePlanes).
+// hr_denoise.hip; the buffers' life follows the AOV planes' (aovFreePlanes).  The calls of include/hrcore_denoise_spatial.h run through
+// the same three functions (denoiseToDevice, denoiseReadback, denoiseDisplay) with a DenoiseSpatialRun.
 
 // Which kernel runs an iteration when the caller leaves the choice to the library: the LDS-tiled kernel for the steps it exists for
 // (1 and 2), the plain one beyond (profiles/denoise_time.txt has the measurement).
@@ -25,18 +26,6 @@ static int denoiseCheckParams(hr_ctx *c, const hr_denoise_params *in, hr_denoise
     return HR_OK;
 }
 
-// both masks on, and the planes zeroed when the frame was: they hold the frame's passes
-static int denoiseCheckPlanes(hr_ctx *c)
-{
-    const uint32_t both = HR_AOV_SURFACE | HR_AOV_MOMENTS;
-    if ((c->aovMask & both) != both)
-        FAIL(c, HR_ERR_INVALID, "denoise needs the AOV planes: hr_aov_enable(HR_AOV_SURFACE | HR_AOV_MOMENTS) before the frame's first pass (enabled mask: " +
-                                    std::to_string(c->aovMask) + ")");
-    if (c->aovZeroedAt != c->frameZeroedAt)
-        FAIL(c, HR_ERR_INVALID, "denoise: the AOV planes were enabled after the frame's first pass and do not hold the frame's passes: hr_clear, or hr_aov_enable before rendering");
-    return HR_OK;
-}
-
 static int denoiseEnsureBuffers(hr_ctx *c, bool needOut)
 {
     const size_t px = (size_t)c->W * c->H;
@@ -58,30 +47,15 @@ static int denoiseRun(hr_ctx *c, const hr_denoise_params *params, float *out, ui
     hr_denoise_params p;
     int rc = denoiseCheckParams(c, params, &p);
     if (rc) return rc;
-    if (c->W <= 0) FAIL(c, HR_ERR_INVALID, "no frame");
+    if (c->W <= 0) FAIL(c, HR_ERR_INVALID, "no frame"); // (asked first: a sharded context without a frame hears this, not frameReady's refusal)
     uint32_t n = 0;
     const float *frame = nullptr;
-    if (c->grp) {
-        rc = denoiseCheckPlanes(c); // (the group's own mask: hr_aov_enable on the handle)
-        if (rc == HR_OK) rc = groupAll(c, [](hr_ctx *m, int) { return denoiseCheckPlanes(m); });
-        if (rc == HR_OK) rc = groupAssemble(c, true, &n, nullptr);
-        for (int plane = 0; plane < 3 && rc == HR_OK; ++plane) rc = groupAovAssemble(c, plane, nullptr);
-        if (rc) return rc;
-        frame = c->fbInternal;
-    } else {
-        if (c->world > 1)
-            FAIL(c, HR_ERR_INVALID, "denoise: a tile-sharded context (world > 1) holds only its own tiles and the filter reads across them: use a context group, which assembles the frame");
-        rc = denoiseCheckPlanes(c);
-        if (rc == HR_OK) rc = drainPipeline(c);
-        if (rc == HR_OK) rc = overflowCheck(c);
-        if (rc) return rc;
-        n = (uint32_t)(c->nextResolveOrder - c->frameZeroedAt);
-        frame = c->fb();
-    }
+    const FrameNeed need{HR_AOV_SURFACE | HR_AOV_MOMENTS, "denoise", "the filter", true, false, std::string("denoise") + kNeedsAovPlanes, std::string("denoise") + kAovPlanesLate};
+    rc = frameReady(c, need, &frame, &n);
+    if (rc) return rc;
     rc = denoiseEnsureBuffers(c, out == nullptr && !(spatial && spatial->varianceOnly));
     if (rc) return rc;
-    if (spatial && !c->dnSpatialResult) HIP_TRY(c, hipMalloc((void **)&c->dnSpatialResult, kDenoiseSpatialResultWords * 8));
-    if (spatial && !c->dnSpatialResultHost) HIP_TRY(c, hipHostMalloc((void **)&c->dnSpatialResultHost, kDenoiseSpatialResultWords * 8, hipHostMallocDefault));
+    if (spatial) HIP_TRY(c, c->dnSpatial.ensure(kDenoiseSpatialResultWords));
     if (!out) out = c->dnOut;
     const size_t px = (size_t)c->W * c->H;
     DenoiseBufs b;
@@ -89,8 +63,8 @@ static int denoiseRun(hr_ctx *c, const hr_denoise_params *params, float *out, ui
     launchDenoisePrepare(c->stream, c->W, c->H, frame, c->aovPlane[HR_AOV_PLANE_ALBEDO], c->aovPlane[HR_AOV_PLANE_NORMAL_DEPTH], c->aovPlane[HR_AOV_PLANE_MOMENTS], b);
     int first = 0; // the half of the ping-pong the iterations start from
     if (spatial) {
-        HIP_TRY(c, hipMemsetAsync(c->dnSpatialResult, 0, kDenoiseSpatialResultWords * 8, c->stream));
-        launchDenoiseSpatial(c->stream, c->W, c->H, frame, b, p, spatial->p, c->dnSpatialResult); // cv[0] -> cv[1]: the same colour, the estimated variance
+        HIP_TRY(c, c->dnSpatial.zero(c->stream));
+        launchDenoiseSpatial(c->stream, c->W, c->H, frame, b, p, spatial->p, c->dnSpatial.dev); // cv[0] -> cv[1]: the same colour, the estimated variance
         first = 1;
     }
     const int iterations = (spatial && spatial->varianceOnly) ? -1 : p.iterations;
@@ -99,6 +73,60 @@ static int denoiseRun(hr_ctx *c, const hr_denoise_params *params, float *out, ui
         launchDenoiseAtrous(c->stream, c->W, c->H, b, (it & 1) ^ first, 1 << it, p, denoiseUseTiled(p, 1 << it), it == iterations - 1 ? out : nullptr);
     HIP_TRY(c, hipGetLastError());
     if (passes) *passes = n;
+    return HR_OK;
+}
+
+// the estimate's counters, fetched and waited for, -> its result (null: nobody asked)
+static void denoiseSpatialFill(const hr_ctx *c, hr_denoise_spatial_result *out)
+{
+    if (!out) return;
+    *out = hr_denoise_spatial_result{};
+    out->spatial_pixels = c->dnSpatial.host[0], out->estimated_pixels = c->dnSpatial.host[1], out->starved_pixels = c->dnSpatial.host[2];
+}
+
+// The three calls of include/hrcore_denoise.h behind their argument checks.  hr_denoise_spatial.inl's calls are the same with `spatial`
+// (and a `result` to fetch); without it every launch, and their order, is the plain call's.
+static int denoiseToDevice(hr_ctx *c, const hr_denoise_params *params, const DenoiseSpatialRun *spatial, void *device_out, void *stream, uint32_t *passes,
+                           hr_denoise_spatial_result *result)
+{
+    // a foreign stream: filter on the ctx stream into the ctx's image, and copy out over there
+    const bool foreign = stream && (hipStream_t)stream != c->stream;
+    int rc = denoiseRun(c, params, foreign ? nullptr : (float *)device_out, passes, spatial);
+    if (rc == HR_OK && result) { // (a result asked for: the call waits for the kernels)
+        HIP_TRY(c, c->dnSpatial.fetch(c->stream));
+        HIP_TRY(c, hipStreamSynchronize(c->stream));
+        denoiseSpatialFill(c, result);
+    }
+    if (rc || !foreign) return rc;
+    return copyOutOnStream(c, device_out, c->dnOut, (size_t)c->W * c->H * 16, stream);
+}
+
+static int denoiseReadback(hr_ctx *c, const hr_denoise_params *params, const DenoiseSpatialRun *spatial, const float **rgba, int32_t *w, int32_t *h, uint32_t *passes,
+                           hr_denoise_spatial_result *result)
+{
+    int rc = denoiseRun(c, params, nullptr, passes, spatial);
+    const size_t bytes = (size_t)c->W * c->H * 16;
+    if (rc == HR_OK) rc = growPinned(c, c->dnPinned, c->dnPinnedBytes, bytes);
+    if (rc) return rc;
+    HIP_TRY(c, hipMemcpyAsync(c->dnPinned, c->dnOut, bytes, hipMemcpyDeviceToHost, c->stream));
+    if (spatial) HIP_TRY(c, c->dnSpatial.fetch(c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream)); // (one wait for the image and the counters)
+    denoiseSpatialFill(c, result);
+    *rgba = c->dnPinned;
+    if (w) *w = c->W;
+    if (h) *h = c->H;
+    return HR_OK;
+}
+
+static int denoiseDisplay(hr_ctx *c, const hr_denoise_params *params, const DenoiseSpatialRun *spatial, const hr_display_params *display, int32_t format, void *device_out,
+                          uint32_t *passes_shown)
+{
+    int rc = denoiseRun(c, params, nullptr, passes_shown, spatial);
+    if (rc) return rc;
+    FrameDev fr = c->frame; // (denoiseRun has refused world > 1: every pixel is this context's; a group's frame is rank 0 of 1)
+    fr.fb = c->dnOut;
+    launchDisplay(c->cfg(c->stream), fr, *display, format, device_out);
+    HIP_TRY(c, hipGetLastError());
     return HR_OK;
 }
 
@@ -117,39 +145,14 @@ int hr_denoise(hr_ctx *c, const hr_denoise_params *params, void *device_out, voi
 {
     ENTER(c);
     if (!device_out) FAIL(c, HR_ERR_INVALID, "null output");
-    hipStream_t st = stream ? (hipStream_t)stream : c->stream;
-    if (st == c->stream) return denoiseRun(c, params, (float *)device_out, passes);
-    // a foreign stream: filter on the ctx stream into the ctx's image, copy out over there, and the ctx's next work behind the copy
-    int rc = denoiseRun(c, params, nullptr, passes);
-    if (rc) return rc;
-    if (!c->evAov) HIP_TRY(c, hipEventCreateWithFlags(&c->evAov, hipEventDisableTiming));
-    HIP_TRY(c, hipEventRecord(c->evAov, c->stream));
-    HIP_TRY(c, hipStreamWaitEvent(st, c->evAov, 0));
-    HIP_TRY(c, hipMemcpyAsync(device_out, c->dnOut, (size_t)c->W * c->H * 16, hipMemcpyDeviceToDevice, st));
-    HIP_TRY(c, hipEventRecord(c->evAov, st));
-    HIP_TRY(c, hipStreamWaitEvent(c->stream, c->evAov, 0));
-    return HR_OK;
+    return denoiseToDevice(c, params, nullptr, device_out, stream, passes, nullptr);
 }
 
 int hr_denoise_readback(hr_ctx *c, const hr_denoise_params *params, const float **rgba, int32_t *w, int32_t *h, uint32_t *passes)
 {
     ENTER(c);
     if (!rgba) FAIL(c, HR_ERR_INVALID, "null output");
-    int rc = denoiseRun(c, params, nullptr, passes);
-    if (rc) return rc;
-    const size_t bytes = (size_t)c->W * c->H * 16;
-    if (c->dnPinnedBytes < bytes) {
-        if (c->dnPinned) hipHostFree(c->dnPinned);
-        c->dnPinned = nullptr, c->dnPinnedBytes = 0;
-        HIP_TRY(c, hipHostMalloc((void **)&c->dnPinned, bytes, hipHostMallocDefault));
-        c->dnPinnedBytes = bytes;
-    }
-    HIP_TRY(c, hipMemcpyAsync(c->dnPinned, c->dnOut, bytes, hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(c, hipStreamSynchronize(c->stream));
-    *rgba = c->dnPinned;
-    if (w) *w = c->W;
-    if (h) *h = c->H;
-    return HR_OK;
+    return denoiseReadback(c, params, nullptr, rgba, w, h, passes, nullptr);
 }
 
 int hr_denoise_display(hr_ctx *c, const hr_denoise_params *params, const hr_display_params *display, int32_t format, void *device_out, uint32_t *passes_shown)
@@ -157,13 +160,7 @@ int hr_denoise_display(hr_ctx *c, const hr_denoise_params *params, const hr_disp
     ENTER(c);
     if (!display || !device_out) FAIL(c, HR_ERR_INVALID, "null argument");
     if (format < HR_DISPLAY_RGBA8 || format > HR_DISPLAY_HDR_RGBA32F) FAIL(c, HR_ERR_INVALID, "unknown display format (the denoised display has no progressive form)");
-    int rc = denoiseRun(c, params, nullptr, passes_shown);
-    if (rc) return rc;
-    FrameDev fr = c->frame; // (denoiseRun has refused world > 1: every pixel is this context's; a group's frame is rank 0 of 1)
-    fr.fb = c->dnOut;
-    launchDisplay(c->cfg(c->stream), fr, *display, format, device_out);
-    HIP_TRY(c, hipGetLastError());
-    return HR_OK;
+    return denoiseDisplay(c, params, nullptr, display, format, device_out, passes_shown);
 }
 
 } // extern "C"

@@ -11,11 +11,12 @@
 //                        and lum(d), lum(a), n and cov as floats: 32 B per entry, 15488 B (a row of 22 entries: a wave's four rows of 16 lanes
 //                        overlap in six banks of 32, a two-way conflict the taps' arithmetic hides).  Both tap
 //                        passes of dsEstimate read LDS; both luminances are computed once per entry.
-//                        The counters: ballots, summed in LDS, one 64-bit integer atomic per workgroup and counter, as in k_history_merge.
+//                        The counters: ballots, summed in LDS, one 64-bit integer atomic per workgroup and counter (hr_post_device.h).
 // No scratch, no float atomics.
 #include "hr_math.h"
 #include "hr_denoise_spatial.h"
 #include "hr_kernels.h"
+#include "hr_post_device.h"
 
 namespace hr {
 
@@ -51,7 +52,7 @@ __global__ __launch_bounds__(256) void k_spatial_variance(int W, int H, DsParams
     __shared__ float sN[kDsEntries];
     __shared__ float sCov[kDsEntries];
     __shared__ uint32_t sRed[4]; // spatial, estimated, starved pixels of the workgroup; [3]: does it have a spatial pixel at all
-    if (threadIdx.x < 4u) sRed[threadIdx.x] = 0u;
+    wgCountersZero<4>(sRed);
     const uint32_t lane = threadIdx.x & 63u;
     const int x = (int)(blockIdx.x * kDsTile + (threadIdx.x & (kDsTile - 1))), y = (int)(blockIdx.y * kDsTile + threadIdx.x / kDsTile);
     const bool in = x < W && y < H;
@@ -60,7 +61,7 @@ __global__ __launch_bounds__(256) void k_spatial_variance(int W, int H, DsParams
     const dn4 c = G(cvIn)[i];
     const bool spatial = in && n > 0.0f && dsSpatial(n, P);
     __syncthreads();
-    const uint32_t nSpatial = (uint32_t)__popcll(__ballot(spatial));
+    const uint32_t nSpatial = waveCount(spatial);
     if (lane == 0u && nSpatial) atomicAdd(&sRed[0], nSpatial), sRed[3] = 1u;
     __syncthreads();
     if (sRed[3] == 0u) { // (the same word for every lane of the workgroup: nobody waits at a barrier below)
@@ -90,10 +91,9 @@ __global__ __launch_bounds__(256) void k_spatial_variance(int W, int H, DsParams
         st = r.status, v = r.v;
     }
     if (in) G(cvOut)[i] = dn4{c.x, c.y, c.z, v};
-    const uint32_t nEstimated = (uint32_t)__popcll(__ballot(st == DS_ESTIMATED)), nStarved = (uint32_t)__popcll(__ballot(st == DS_STARVED));
+    const uint32_t nEstimated = waveCount(st == DS_ESTIMATED), nStarved = waveCount(st == DS_STARVED);
     if (lane == 0u) atomicAdd(&sRed[1], nEstimated), atomicAdd(&sRed[2], nStarved);
-    __syncthreads();
-    if (threadIdx.x < 3u && sRed[threadIdx.x]) atomicAdd(&result[threadIdx.x], (unsigned long long)sRed[threadIdx.x]);
+    wgCountersFlush<3>(sRed, result); // (sRed[3] is the vote, no counter)
 }
 
 static inline const dn4 *P4(const float *p) { return reinterpret_cast<const dn4 *>(p); }

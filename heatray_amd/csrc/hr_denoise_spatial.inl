@@ -1,6 +1,7 @@
-// hr_denoise_spatial.inl — a section of hr_core.hip (included at its end): the entry points of include/hrcore_denoise_spatial.h.  The
-// kernel is in hr_denoise_spatial.hip; the checks, the buffers and the launches around it are denoiseRun's (hr_denoise.inl), which takes
-// the estimate's parameters as its optional last argument.
+// hr_denoise_spatial.inl — a section of hr_core.hip (included at its end, after hr_denoise.inl): the entry points of
+// include/hrcore_denoise_spatial.h.  The kernel is in hr_denoise_spatial.hip; the checks, the buffers and the launches around it are
+// denoiseRun's, and the calls are hr_denoise.inl's three (denoiseToDevice, denoiseReadback, denoiseDisplay) with the estimate's
+// parameters in a DenoiseSpatialRun.  What is left here: the parameter check, the defaults, hr_denoise_spatial_variance.
 
 static int denoiseSpatialCheckParams(hr_ctx *c, const hr_denoise_spatial_params *in, hr_denoise_spatial_params *p)
 {
@@ -16,24 +17,6 @@ static int denoiseSpatialCheckParams(hr_ctx *c, const hr_denoise_spatial_params 
                                     std::to_string(HR_DENOISE_SPATIAL_MIN_TAPS_HIGHEST));
     for (int k = 0; k < 6; ++k)
         if (p->reserved[k]) FAIL(c, HR_ERR_INVALID, "denoise spatial: reserved[" + std::to_string(k) + "] must be 0");
-    return HR_OK;
-}
-
-// denoiseRun with the estimate; with `out` it waits for the kernels and returns the counters
-static int denoiseSpatialRun(hr_ctx *c, const hr_denoise_params *dparams, const hr_denoise_spatial_params *sparams, float *dst, uint32_t *passes, bool varianceOnly,
-                             hr_denoise_spatial_result *out)
-{
-    DenoiseSpatialRun run;
-    run.varianceOnly = varianceOnly;
-    int rc = denoiseSpatialCheckParams(c, sparams, &run.p);
-    if (rc == HR_OK) rc = denoiseRun(c, dparams, dst, passes, &run);
-    if (rc) return rc;
-    if (out) {
-        HIP_TRY(c, hipMemcpyAsync(c->dnSpatialResultHost, c->dnSpatialResult, kDenoiseSpatialResultWords * 8, hipMemcpyDeviceToHost, c->stream));
-        HIP_TRY(c, hipStreamSynchronize(c->stream));
-        *out = hr_denoise_spatial_result{};
-        out->spatial_pixels = c->dnSpatialResultHost[0], out->estimated_pixels = c->dnSpatialResultHost[1], out->starved_pixels = c->dnSpatialResultHost[2];
-    }
     return HR_OK;
 }
 
@@ -53,18 +36,9 @@ int hr_denoise_spatial(hr_ctx *c, const hr_denoise_params *dparams, const hr_den
 {
     ENTER(c);
     if (!device_out) FAIL(c, HR_ERR_INVALID, "null output");
-    hipStream_t st = stream ? (hipStream_t)stream : c->stream;
-    if (st == c->stream) return denoiseSpatialRun(c, dparams, sparams, (float *)device_out, passes, false, result);
-    // a foreign stream: as in hr_denoise
-    int rc = denoiseSpatialRun(c, dparams, sparams, nullptr, passes, false, result);
-    if (rc) return rc;
-    if (!c->evAov) HIP_TRY(c, hipEventCreateWithFlags(&c->evAov, hipEventDisableTiming));
-    HIP_TRY(c, hipEventRecord(c->evAov, c->stream));
-    HIP_TRY(c, hipStreamWaitEvent(st, c->evAov, 0));
-    HIP_TRY(c, hipMemcpyAsync(device_out, c->dnOut, (size_t)c->W * c->H * 16, hipMemcpyDeviceToDevice, st));
-    HIP_TRY(c, hipEventRecord(c->evAov, st));
-    HIP_TRY(c, hipStreamWaitEvent(c->stream, c->evAov, 0));
-    return HR_OK;
+    DenoiseSpatialRun run{{}, false};
+    const int rc = denoiseSpatialCheckParams(c, sparams, &run.p);
+    return rc ? rc : denoiseToDevice(c, dparams, &run, device_out, stream, passes, result);
 }
 
 int hr_denoise_spatial_readback(hr_ctx *c, const hr_denoise_params *dparams, const hr_denoise_spatial_params *sparams, const float **rgba, int32_t *w, int32_t *h,
@@ -72,26 +46,9 @@ int hr_denoise_spatial_readback(hr_ctx *c, const hr_denoise_params *dparams, con
 {
     ENTER(c);
     if (!rgba) FAIL(c, HR_ERR_INVALID, "null output");
-    int rc = denoiseSpatialRun(c, dparams, sparams, nullptr, passes, false, nullptr);
-    if (rc) return rc;
-    const size_t bytes = (size_t)c->W * c->H * 16;
-    if (c->dnPinnedBytes < bytes) {
-        if (c->dnPinned) hipHostFree(c->dnPinned);
-        c->dnPinned = nullptr, c->dnPinnedBytes = 0;
-        HIP_TRY(c, hipHostMalloc((void **)&c->dnPinned, bytes, hipHostMallocDefault));
-        c->dnPinnedBytes = bytes;
-    }
-    HIP_TRY(c, hipMemcpyAsync(c->dnPinned, c->dnOut, bytes, hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(c, hipMemcpyAsync(c->dnSpatialResultHost, c->dnSpatialResult, kDenoiseSpatialResultWords * 8, hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(c, hipStreamSynchronize(c->stream));
-    if (result) {
-        *result = hr_denoise_spatial_result{};
-        result->spatial_pixels = c->dnSpatialResultHost[0], result->estimated_pixels = c->dnSpatialResultHost[1], result->starved_pixels = c->dnSpatialResultHost[2];
-    }
-    *rgba = c->dnPinned;
-    if (w) *w = c->W;
-    if (h) *h = c->H;
-    return HR_OK;
+    DenoiseSpatialRun run{{}, false};
+    const int rc = denoiseSpatialCheckParams(c, sparams, &run.p);
+    return rc ? rc : denoiseReadback(c, dparams, &run, rgba, w, h, passes, result);
 }
 
 int hr_denoise_spatial_display(hr_ctx *c, const hr_denoise_params *dparams, const hr_denoise_spatial_params *sparams, const hr_display_params *display, int32_t format,
@@ -100,31 +57,26 @@ int hr_denoise_spatial_display(hr_ctx *c, const hr_denoise_params *dparams, cons
     ENTER(c);
     if (!display || !device_out) FAIL(c, HR_ERR_INVALID, "null argument");
     if (format < HR_DISPLAY_RGBA8 || format > HR_DISPLAY_HDR_RGBA32F) FAIL(c, HR_ERR_INVALID, "unknown display format (the denoised display has no progressive form)");
-    int rc = denoiseSpatialRun(c, dparams, sparams, nullptr, passes_shown, false, nullptr);
-    if (rc) return rc;
-    FrameDev fr = c->frame; // (as in hr_denoise_display)
-    fr.fb = c->dnOut;
-    launchDisplay(c->cfg(c->stream), fr, *display, format, device_out);
-    HIP_TRY(c, hipGetLastError());
-    return HR_OK;
+    DenoiseSpatialRun run{{}, false};
+    const int rc = denoiseSpatialCheckParams(c, sparams, &run.p);
+    return rc ? rc : denoiseDisplay(c, dparams, &run, display, format, device_out, passes_shown);
 }
 
 int hr_denoise_spatial_variance(hr_ctx *c, const hr_denoise_params *dparams, const hr_denoise_spatial_params *sparams, float *host_out, hr_denoise_spatial_result *result)
 {
     ENTER(c);
     if (!host_out) FAIL(c, HR_ERR_INVALID, "null output");
-    int rc = denoiseSpatialRun(c, dparams, sparams, nullptr, nullptr, true, nullptr);
+    DenoiseSpatialRun run{{}, true};
+    int rc = denoiseSpatialCheckParams(c, sparams, &run.p);
+    if (rc == HR_OK) rc = denoiseRun(c, dparams, nullptr, nullptr, &run);
     if (rc) return rc;
     const size_t px = (size_t)c->W * c->H;
     std::vector<float> cv(px * 4); // (cv[1]: colour + variance; a call for inspection, not a hot path)
     HIP_TRY(c, hipMemcpyAsync(cv.data(), c->dnWork + 4 * px, px * 16, hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(c, hipMemcpyAsync(c->dnSpatialResultHost, c->dnSpatialResult, kDenoiseSpatialResultWords * 8, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, c->dnSpatial.fetch(c->stream));
     HIP_TRY(c, hipStreamSynchronize(c->stream));
     for (size_t i = 0; i < px; ++i) host_out[i] = cv[4 * i + 3];
-    if (result) {
-        *result = hr_denoise_spatial_result{};
-        result->spatial_pixels = c->dnSpatialResultHost[0], result->estimated_pixels = c->dnSpatialResultHost[1], result->starved_pixels = c->dnSpatialResultHost[2];
-    }
+    denoiseSpatialFill(c, result);
     return HR_OK;
 }
 

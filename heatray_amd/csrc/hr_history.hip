@@ -9,23 +9,17 @@
 //                      wave's own pixels is one 128-byte line per plane, and the wave's four-tap footprints (which a camera change
 //                      moves together) overlap in a handful of lines.  Own pixel 4 x 16 B in and, where history was taken over,
 //                      4 x 16 B out; 12 gathered float4 of history, every load issued before the first decision.  The counters: the
-//                      wave's ballots and a shuffle sum of the samples taken over, reduced in LDS, one integer atomic per workgroup and
-//                      counter: the result does not depend on the order workgroups finish in.
+//                      wave's ballots and a shuffle sum of the samples taken over, reduced in LDS (hr_post_device.h), one integer
+//                      atomic per workgroup and counter: the result does not depend on the order workgroups finish in.
 // No scratch, no float atomics.
 #include "hr_math.h"
 #include "hr_history.h"
 #include "hr_kernels.h"
+#include "hr_post_device.h"
 
 namespace hr {
 
 static constexpr int kHsTileW = 32, kHsTileH = 8; // pixels of a workgroup of k_history_merge: four waves of 8 x 8
-
-struct HsGlobal {
-    const dn4 *p0, *p1, *p2;
-    HRD dn4 h0(int i) const { return G(p0)[i]; }
-    HRD dn4 h1(int i) const { return G(p1)[i]; }
-    HRD dn4 h2(int i) const { return G(p2)[i]; }
-};
 
 __global__ __launch_bounds__(256) void k_history_capture(int n, const dn4 *__restrict__ frame, const dn4 *__restrict__ albedo, const dn4 *__restrict__ normalDepth,
                                                          const dn4 *__restrict__ moments, dn4 *__restrict__ hist)
@@ -42,7 +36,7 @@ __global__ __launch_bounds__(256) void k_history_merge(int W, int H, HsCam cam, 
                                                        dn4 *__restrict__ normalDepth, dn4 *__restrict__ moments, unsigned long long *__restrict__ result)
 {
     __shared__ uint32_t sRed[3];
-    if (threadIdx.x < 3u) sRed[threadIdx.x] = 0u;
+    wgCountersZero<3>(sRed);
     __syncthreads();
     const uint32_t tilesX = (uint32_t)(W + kHsTileW - 1) / (uint32_t)kHsTileW; // (a one-dimensional grid: no bound on the image's height)
     const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
@@ -50,20 +44,16 @@ __global__ __launch_bounds__(256) void k_history_merge(int W, int H, HsCam cam, 
     const int y = (int)(blockIdx.x / tilesX) * kHsTileH + (int)(lane >> 3);
     const bool in = x < W && y < H;
     const int i = in ? y * W + x : 0; // (a lane outside the image reads pixel 0 and writes nothing)
-    const size_t n = (size_t)W * (size_t)H;
     dn4 F = G(frame)[i], A = G(albedo)[i], Gn = G(normalDepth)[i], M = G(moments)[i];
-    const HsGlobal src{hist, hist + n, hist + 2 * n};
+    const HsPlanes src(hist, (size_t)W * (size_t)H);
     float nh = 0.0f;
     const int st = hsMerge(src, cam, P, in ? x : 0, in ? y : 0, W, H, F, A, Gn, M, &nh);
     const bool reused = in && st == HS_REUSED, rejected = in && st == HS_REJECTED;
     if (reused) G(frame)[i] = F, G(albedo)[i] = A, G(normalDepth)[i] = Gn, G(moments)[i] = M;
-    uint32_t samples = reused ? hsCount(nh) : 0u; // (at most 65536 per pixel: a workgroup's sum fits 32 bits)
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) samples += (uint32_t)__shfl_xor((int)samples, o);
-    const uint32_t nReused = (uint32_t)__popcll(__ballot(reused)), nRejected = (uint32_t)__popcll(__ballot(rejected));
+    const uint32_t samples = waveSum(reused ? hsCount(nh) : 0u); // (at most 65536 per pixel: a workgroup's sum fits 32 bits)
+    const uint32_t nReused = waveCount(reused), nRejected = waveCount(rejected);
     if (lane == 0u) atomicAdd(&sRed[0], nReused), atomicAdd(&sRed[1], nRejected), atomicAdd(&sRed[2], samples);
-    __syncthreads();
-    if (threadIdx.x < 3u && sRed[threadIdx.x]) atomicAdd(&result[threadIdx.x], (unsigned long long)sRed[threadIdx.x]);
+    wgCountersFlush<3>(sRed, result);
 }
 
 void launchHistoryCapture(hipStream_t st, int W, int H, const float *frame, const float *albedo, const float *normalDepth, const float *moments, float *hist)

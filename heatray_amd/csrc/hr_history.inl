@@ -31,25 +31,12 @@ static int historyCheckCamera(hr_ctx *c, const hr_pass_params *cam)
     return HR_OK;
 }
 
-// what capture and merge both ask of the context; *passes = the complete passes in its frame
+// what capture, merge and hr_reproject.inl's calls all ask of the context: a plain one, whose frame (c->fb()) holds at least one pass
 static int historyCheckFrame(hr_ctx *c, const char *what, uint32_t *passes)
 {
-    if (c->grp) FAIL(c, HR_ERR_INVALID, std::string(what) + ": a context group is not supported (the gather reads across the members' tiles): capture and merge on a plain context");
-    if (c->world > 1)
-        FAIL(c, HR_ERR_INVALID, std::string(what) + ": a tile-sharded context (world > 1) holds only its own tiles and the gather reads across them");
-    if (c->W <= 0) FAIL(c, HR_ERR_INVALID, "no frame");
-    const uint32_t both = HR_AOV_SURFACE | HR_AOV_MOMENTS;
-    if ((c->aovMask & both) != both)
-        FAIL(c, HR_ERR_INVALID, std::string(what) + " needs the AOV planes: hr_aov_enable(HR_AOV_SURFACE | HR_AOV_MOMENTS) before the frame's first pass (enabled mask: " +
-                                    std::to_string(c->aovMask) + ")");
-    if (c->aovZeroedAt != c->frameZeroedAt)
-        FAIL(c, HR_ERR_INVALID, std::string(what) + ": the AOV planes were enabled after the frame's first pass and do not hold the frame's passes: hr_clear, or hr_aov_enable before rendering");
-    int rc = drainPipeline(c);
-    if (rc == HR_OK) rc = overflowCheck(c);
-    if (rc) return rc;
-    *passes = (uint32_t)(c->nextResolveOrder - c->frameZeroedAt);
-    if (*passes == 0) FAIL(c, HR_ERR_INVALID, std::string(what) + ": the frame is empty (0 passes)");
-    return HR_OK;
+    const float *frame = nullptr;
+    const FrameNeed need{HR_AOV_SURFACE | HR_AOV_MOMENTS, what, "the gather", false, true, std::string(what) + kNeedsAovPlanes, std::string(what) + kAovPlanesLate};
+    return frameReady(c, need, &frame, passes);
 }
 
 extern "C" {
@@ -93,21 +80,20 @@ int hr_history_merge(hr_ctx *c, const hr_pass_params *camera, const hr_history_p
     if (rc) return rc;
     if (!c->hsCaptured) FAIL(c, HR_ERR_INVALID, "history merge: no captured history (hr_history_capture; hr_frame_resize and hr_history_drop remove it)");
     if (c->hsMerged) FAIL(c, HR_ERR_INVALID, "history merge: the history has already been merged into this frame (one merge per hr_clear: a second would count it twice)");
-    if (!c->hsResult) HIP_TRY(c, hipMalloc((void **)&c->hsResult, kHistoryResultWords * 8));
-    if (!c->hsResultHost) HIP_TRY(c, hipHostMalloc((void **)&c->hsResultHost, kHistoryResultWords * 8, hipHostMallocDefault));
+    HIP_TRY(c, c->hs.ensure(kHistoryResultWords));
+    HIP_TRY(c, c->hs.zero(c->stream));
     const HsCam cam = hsCameras(c->hsView, c->hsAspect, c->hsFovTan, camera->view_matrix, camera->aspect_ratio, camera->fov_tan);
     const HsParams P{(float)p.max_history, p.normal_cos, p.plane_tol, p.min_weight};
-    HIP_TRY(c, hipMemsetAsync(c->hsResult, 0, kHistoryResultWords * 8, c->stream));
     launchHistoryMerge(c->stream, c->W, c->H, cam, P, c->hsHist, c->fb(), c->aovPlane[HR_AOV_PLANE_ALBEDO], c->aovPlane[HR_AOV_PLANE_NORMAL_DEPTH],
-                       c->aovPlane[HR_AOV_PLANE_MOMENTS], c->hsResult);
+                       c->aovPlane[HR_AOV_PLANE_MOMENTS], c->hs.dev);
     HIP_TRY(c, hipGetLastError());
     c->hsMerged = true;
     c->snapshotEpoch++; // (progressive snapshots taken before the merge are not handed out any more)
-    HIP_TRY(c, hipMemcpyAsync(c->hsResultHost, c->hsResult, kHistoryResultWords * 8, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, c->hs.fetch(c->stream));
     HIP_TRY(c, hipStreamSynchronize(c->stream));
     if (out) {
         *out = hr_history_result{};
-        out->reused_pixels = c->hsResultHost[0], out->rejected_pixels = c->hsResultHost[1], out->history_samples = c->hsResultHost[2];
+        out->reused_pixels = c->hs.host[0], out->rejected_pixels = c->hs.host[1], out->history_samples = c->hs.host[2];
         out->history_passes = c->hsPasses, out->passes = n;
     }
     return HR_OK;

@@ -11,23 +11,17 @@
 //                        2 in LDS, 36 x 12 entries, each normalised and divided once; an unsampled lane walks the 24 offsets there
 //                        and stops at the first hit; the four taps' H0 and H2, eight float4, are issued together.  A wave whose pixels
 //                        all have samples writes their means and reads no history.
-// The counters of both: the wave's ballots (and a shuffle sum of the samples taken over), reduced in LDS, one integer atomic per
+// The counters of both (hr_post_device.h): ballots (and a shuffle sum of the samples taken over), reduced in LDS, one integer atomic per
 // workgroup and counter: a result does not depend on the order workgroups finish in.  No scratch, no float atomics, plain vector stores.
 #include "hr_math.h"
 #include "hr_reproject.h"
 #include "hr_kernels.h"
+#include "hr_post_device.h"
 
 namespace hr {
 
 static constexpr int kRpTileW = 32, kRpTileH = 8;                                              // pixels of a workgroup: four waves of 8 x 8
 static constexpr int kRpHaloW = kRpTileW + 2 * RP_GUIDE_REACH, kRpHaloH = kRpTileH + 2 * RP_GUIDE_REACH; // 36 x 12 staged guide records
-
-struct RpGlobal {
-    const dn4 *p0, *p1, *p2;
-    HRD dn4 h0(int i) const { return G(p0)[i]; }
-    HRD dn4 h1(int i) const { return G(p1)[i]; }
-    HRD dn4 h2(int i) const { return G(p2)[i]; }
-};
 
 // result: {reused pixels, rejected pixels, samples taken over, pending pixels, examined pixels}, zeroed by the caller
 __global__ __launch_bounds__(256) void k_reproject_merge(int W, int H, HsCam cam, HsParams P, const dn4 *__restrict__ hist, dn4 *__restrict__ frame, dn4 *__restrict__ albedo,
@@ -35,7 +29,7 @@ __global__ __launch_bounds__(256) void k_reproject_merge(int W, int H, HsCam cam
                                                          unsigned long long *__restrict__ result)
 {
     __shared__ uint32_t sRed[5];
-    if (threadIdx.x < 5u) sRed[threadIdx.x] = 0u;
+    wgCountersZero<5>(sRed);
     __syncthreads();
     const uint32_t tilesX = (uint32_t)(W + kRpTileW - 1) / (uint32_t)kRpTileW;
     const uint32_t blocksX = (uint32_t)(W + 7) / 8u;
@@ -53,29 +47,25 @@ __global__ __launch_bounds__(256) void k_reproject_merge(int W, int H, HsCam cam
     const unsigned long long todoMask = __ballot(todo);
     uint32_t nReused = 0u, nRejected = 0u, samples = 0u;
     if (todoMask) { // wave-uniform
-        const size_t n = (size_t)W * (size_t)H;
         dn4 A = G(albedo)[i], Gn = G(normalDepth)[i], M = G(moments)[i];
-        const RpGlobal src{hist, hist + n, hist + 2 * n};
+        const HsPlanes src(hist, (size_t)W * (size_t)H);
         float nh = 0.0f;
         const int st = hsMerge(src, cam, P, in ? x : 0, in ? y : 0, W, H, F, A, Gn, M, &nh);
         const bool reused = todo && st == HS_REUSED, rejected = todo && st == HS_REJECTED;
         if (reused) G(frame)[i] = F, G(albedo)[i] = A, G(normalDepth)[i] = Gn, G(moments)[i] = M;
-        samples = reused ? hsCount(nh) : 0u; // (at most 65536 per pixel: a workgroup's sum fits 32 bits)
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) samples += (uint32_t)__shfl_xor((int)samples, o);
-        nReused = (uint32_t)__popcll(__ballot(reused)), nRejected = (uint32_t)__popcll(__ballot(rejected));
+        samples = waveSum(reused ? hsCount(nh) : 0u); // (at most 65536 per pixel: a workgroup's sum fits 32 bits)
+        nReused = waveCount(reused), nRejected = waveCount(rejected);
         if (lane == 0u) G(examined)[wordAt] = word | todoMask; // (todoMask != 0 implies hasWord)
     }
     const unsigned long long now = word | todoMask;
-    const uint32_t nExamined = (uint32_t)__popcll(now), nPending = (uint32_t)__popcll(__ballot(in) & ~now);
+    const uint32_t nExamined = (uint32_t)__popcll(now), nPending = (uint32_t)__popcll(__ballot(in) & ~now); // (bit masks in hand: no waveCount)
     if (lane == 0u) {
         if (nReused) atomicAdd(&sRed[0], nReused);
         if (nRejected) atomicAdd(&sRed[1], nRejected);
         if (samples) atomicAdd(&sRed[2], samples);
         atomicAdd(&sRed[3], nPending), atomicAdd(&sRed[4], nExamined);
     }
-    __syncthreads();
-    if (threadIdx.x < 5u && sRed[threadIdx.x]) atomicAdd(&result[threadIdx.x], (unsigned long long)sRed[threadIdx.x]);
+    wgCountersFlush<5>(sRed, result);
 }
 
 // the workgroup's staged guide records behind rpFindGuide's source
@@ -96,7 +86,7 @@ __global__ __launch_bounds__(256) void k_reproject_preview(int W, int H, HsCam c
     __shared__ dn4 sRec[kRpHaloW * kRpHaloH];
     __shared__ unsigned char sCls[kRpHaloW * kRpHaloH];
     __shared__ uint32_t sRed[3];
-    if (threadIdx.x < 3u) sRed[threadIdx.x] = 0u;
+    wgCountersZero<3>(sRed); // (the barrier behind the staging loop comes before the first add)
     const uint32_t tilesX = (uint32_t)(W + kRpTileW - 1) / (uint32_t)kRpTileW;
     const int tx0 = (int)(blockIdx.x % tilesX) * kRpTileW, ty0 = (int)(blockIdx.x / tilesX) * kRpTileH;
     for (int e = (int)threadIdx.x; e < kRpHaloW * kRpHaloH; e += 256) {
@@ -123,22 +113,20 @@ __global__ __launch_bounds__(256) void k_reproject_preview(int W, int H, HsCam c
         int gx = 0, gy = 0, cls = RP_GUIDE_NONE;
         dn4 rec{0.0f, 0.0f, 0.0f, 0.0f};
         if (needs) cls = rpFindGuide(guides, x, y, W, H, gx, gy, rec);
-        const size_t n = (size_t)W * (size_t)H;
-        const RpGlobal src{hist, hist + n, hist + 2 * n};
+        const HsPlanes src(hist, (size_t)W * (size_t)H);
         dn4 pv;
         const int st = rpPreviewFromGuide(src, cam, P, in ? x : 0, in ? y : 0, W, H, cls, gx, gy, rec, pv);
         previewed = needs && st == RP_PREVIEWED;
         if (previewed) px = pv;
     }
     if (in) G(out)[i] = px;
-    const uint32_t nOwn = (uint32_t)__popcll(__ballot(own)), nPrev = (uint32_t)__popcll(__ballot(previewed)), nEmpty = (uint32_t)__popcll(__ballot(needs && !previewed));
+    const uint32_t nOwn = waveCount(own), nPrev = waveCount(previewed), nEmpty = waveCount(needs && !previewed);
     if (lane == 0u) {
         if (nOwn) atomicAdd(&sRed[0], nOwn);
         if (nPrev) atomicAdd(&sRed[1], nPrev);
         if (nEmpty) atomicAdd(&sRed[2], nEmpty);
     }
-    __syncthreads();
-    if (threadIdx.x < 3u && sRed[threadIdx.x]) atomicAdd(&result[threadIdx.x], (unsigned long long)sRed[threadIdx.x]);
+    wgCountersFlush<3>(sRed, result);
 }
 
 static dim3 rpGrid(int W, int H) { return dim3(((W + kRpTileW - 1) / kRpTileW) * ((H + kRpTileH - 1) / kRpTileH)); }

@@ -14,9 +14,16 @@ static int reprojectPrepare(hr_ctx *c, const char *what, const hr_pass_params *c
     rc = historyCheckFrame(c, what, passes);
     if (rc) return rc;
     if (!c->hsCaptured) FAIL(c, HR_ERR_INVALID, std::string(what) + ": no captured history (hr_history_capture; hr_frame_resize and hr_history_drop remove it)");
-    if (!c->rpResult) HIP_TRY(c, hipMalloc((void **)&c->rpResult, kReprojectResultWords * 8));
-    if (!c->rpResultHost) HIP_TRY(c, hipHostMalloc((void **)&c->rpResultHost, kReprojectResultWords * 8, hipHostMallocDefault));
+    HIP_TRY(c, c->rp.ensure(kReprojectResultWords));
     return HR_OK;
+}
+
+// the preview's counters, fetched and waited for, -> its result (null: nobody asked)
+static void previewFill(const hr_ctx *c, hr_reproject_preview_result *out)
+{
+    if (!out) return;
+    *out = hr_reproject_preview_result{};
+    out->own_pixels = c->rp.host[0], out->previewed_pixels = c->rp.host[1], out->empty_pixels = c->rp.host[2];
 }
 
 // Checks, and enqueues the preview on the ctx stream; the image goes to `dst`, or to c->rpOut when dst is null.  With `out` it waits.
@@ -32,14 +39,13 @@ static int previewRun(hr_ctx *c, const hr_pass_params *camera, const hr_history_
     }
     const HsCam cam = hsCameras(c->hsView, c->hsAspect, c->hsFovTan, camera->view_matrix, camera->aspect_ratio, camera->fov_tan);
     const HsParams P{(float)p.max_history, p.normal_cos, p.plane_tol, p.min_weight};
-    HIP_TRY(c, hipMemsetAsync(c->rpResult, 0, kReprojectResultWords * 8, c->stream));
-    launchReprojectPreview(c->stream, c->W, c->H, cam, P, c->hsHist, c->fb(), c->aovPlane[HR_AOV_PLANE_ALBEDO], c->aovPlane[HR_AOV_PLANE_NORMAL_DEPTH], dst, c->rpResult);
+    HIP_TRY(c, c->rp.zero(c->stream));
+    launchReprojectPreview(c->stream, c->W, c->H, cam, P, c->hsHist, c->fb(), c->aovPlane[HR_AOV_PLANE_ALBEDO], c->aovPlane[HR_AOV_PLANE_NORMAL_DEPTH], dst, c->rp.dev);
     HIP_TRY(c, hipGetLastError());
     if (out) {
-        HIP_TRY(c, hipMemcpyAsync(c->rpResultHost, c->rpResult, kReprojectResultWords * 8, hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(c, c->rp.fetch(c->stream));
         HIP_TRY(c, hipStreamSynchronize(c->stream));
-        *out = hr_reproject_preview_result{};
-        out->own_pixels = c->rpResultHost[0], out->previewed_pixels = c->rpResultHost[1], out->empty_pixels = c->rpResultHost[2];
+        previewFill(c, out);
     }
     return HR_OK;
 }
@@ -66,18 +72,18 @@ int hr_reproject_merge(hr_ctx *c, const hr_pass_params *camera, const hr_history
     c->rpStale = false;
     const HsCam cam = hsCameras(c->hsView, c->hsAspect, c->hsFovTan, camera->view_matrix, camera->aspect_ratio, camera->fov_tan);
     const HsParams P{(float)p.max_history, p.normal_cos, p.plane_tol, p.min_weight};
-    HIP_TRY(c, hipMemsetAsync(c->rpResult, 0, kReprojectResultWords * 8, c->stream));
+    HIP_TRY(c, c->rp.zero(c->stream));
     launchReprojectMerge(c->stream, c->W, c->H, cam, P, c->hsHist, c->fb(), c->aovPlane[HR_AOV_PLANE_ALBEDO], c->aovPlane[HR_AOV_PLANE_NORMAL_DEPTH],
-                         c->aovPlane[HR_AOV_PLANE_MOMENTS], c->rpExamined, c->rpResult);
+                         c->aovPlane[HR_AOV_PLANE_MOMENTS], c->rpExamined, c->rp.dev);
     HIP_TRY(c, hipGetLastError());
     c->hsMerged = c->rpMerged = true;
     c->snapshotEpoch++; // (progressive snapshots taken before the merge are not handed out any more)
-    HIP_TRY(c, hipMemcpyAsync(c->rpResultHost, c->rpResult, kReprojectResultWords * 8, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, c->rp.fetch(c->stream));
     HIP_TRY(c, hipStreamSynchronize(c->stream));
     if (out) {
         *out = hr_reproject_result{};
-        out->reused_pixels = c->rpResultHost[0], out->rejected_pixels = c->rpResultHost[1], out->history_samples = c->rpResultHost[2];
-        out->pending_pixels = c->rpResultHost[3], out->examined_pixels = c->rpResultHost[4];
+        out->reused_pixels = c->rp.host[0], out->rejected_pixels = c->rp.host[1], out->history_samples = c->rp.host[2];
+        out->pending_pixels = c->rp.host[3], out->examined_pixels = c->rp.host[4];
         out->history_passes = c->hsPasses, out->passes = n;
     }
     return HR_OK;
@@ -105,18 +111,11 @@ int hr_reproject_preview(hr_ctx *c, const hr_pass_params *camera, const hr_histo
 {
     ENTER(c);
     if (!device_out) FAIL(c, HR_ERR_INVALID, "null output");
-    hipStream_t st = stream ? (hipStream_t)stream : c->stream;
-    if (st == c->stream) return previewRun(c, camera, params, (float *)device_out, out);
-    // a foreign stream: the kernel on the ctx stream into the ctx's image, the copy out over there, and the ctx's next work behind the copy
+    if (!stream || (hipStream_t)stream == c->stream) return previewRun(c, camera, params, (float *)device_out, out);
+    // a foreign stream: the kernel on the ctx stream into the ctx's image, and the copy out over there
     int rc = previewRun(c, camera, params, nullptr, out);
     if (rc) return rc;
-    if (!c->evAov) HIP_TRY(c, hipEventCreateWithFlags(&c->evAov, hipEventDisableTiming));
-    HIP_TRY(c, hipEventRecord(c->evAov, c->stream));
-    HIP_TRY(c, hipStreamWaitEvent(st, c->evAov, 0));
-    HIP_TRY(c, hipMemcpyAsync(device_out, c->rpOut, (size_t)c->W * c->H * 16, hipMemcpyDeviceToDevice, st));
-    HIP_TRY(c, hipEventRecord(c->evAov, st));
-    HIP_TRY(c, hipStreamWaitEvent(c->stream, c->evAov, 0));
-    return HR_OK;
+    return copyOutOnStream(c, device_out, c->rpOut, (size_t)c->W * c->H * 16, stream);
 }
 
 int hr_reproject_preview_readback(hr_ctx *c, const hr_pass_params *camera, const hr_history_params *params, const float **rgba, int32_t *w, int32_t *h,
@@ -127,19 +126,12 @@ int hr_reproject_preview_readback(hr_ctx *c, const hr_pass_params *camera, const
     int rc = previewRun(c, camera, params, nullptr, nullptr);
     if (rc) return rc;
     const size_t bytes = (size_t)c->W * c->H * 16;
-    if (c->rpPinnedBytes < bytes) {
-        if (c->rpPinned) hipHostFree(c->rpPinned);
-        c->rpPinned = nullptr, c->rpPinnedBytes = 0;
-        HIP_TRY(c, hipHostMalloc((void **)&c->rpPinned, bytes, hipHostMallocDefault));
-        c->rpPinnedBytes = bytes;
-    }
+    rc = growPinned(c, c->rpPinned, c->rpPinnedBytes, bytes);
+    if (rc) return rc;
     HIP_TRY(c, hipMemcpyAsync(c->rpPinned, c->rpOut, bytes, hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(c, hipMemcpyAsync(c->rpResultHost, c->rpResult, kReprojectResultWords * 8, hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(c, hipStreamSynchronize(c->stream));
-    if (out) {
-        *out = hr_reproject_preview_result{};
-        out->own_pixels = c->rpResultHost[0], out->previewed_pixels = c->rpResultHost[1], out->empty_pixels = c->rpResultHost[2];
-    }
+    HIP_TRY(c, c->rp.fetch(c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream)); // (one wait for the image and the counters)
+    previewFill(c, out);
     *rgba = c->rpPinned;
     if (w) *w = c->W;
     if (h) *h = c->H;
