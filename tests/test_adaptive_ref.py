@@ -1,15 +1,12 @@
 """The arithmetic of adaptive sampling without a GPU: heatray_amd/csrc/hr_adaptive.h compiled for the CPU (tests/host/adaptive_cpu.cpp)
 against its numpy restatement heatray_amd.adaptive.reference_error / reference_mask, bit for bit, on random and on hand-made inputs whose
 answers are known (include/hrcore_adaptive.h is the contract).  tests/test_gpu_adaptive.py holds the device to the same reference."""
-import os
-import subprocess
-
 import numpy as np
 import pytest
 
+import cpu_header
 from heatray_amd import adaptive
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 F = np.float32
 
 
@@ -21,22 +18,12 @@ def params(threshold=0.02, floor=0.05, min_samples=16, radius=2):
 
 @pytest.fixture(scope="module")
 def cpu(tmp_path_factory):
-    d = tmp_path_factory.mktemp("adaptive_cpu")
-    exe = d / "adaptive_cpu"
-    # -ffp-contract=off like the library: the header's float lines must mean the same on both sides
-    subprocess.check_call(["g++", "-std=c++17", "-O1", "-ffp-contract=off", "-Wall", "-I" + os.path.join(ROOT, "heatray_amd", "csrc"),
-                           os.path.join(ROOT, "tests", "host", "adaptive_cpu.cpp"), "-o", str(exe)])
+    exe = cpu_header.build("adaptive", tmp_path_factory.mktemp("adaptive_cpu"))
 
     def run(frame, moments, p):
         H, W = frame.shape[:2]
-        with open(d / "in.bin", "wb") as f:
-            f.write(np.array([W, H, p.min_samples, p.radius], np.int32).tobytes())
-            f.write(np.array([p.threshold, p.floor], F).tobytes())
-            f.write(np.ascontiguousarray(frame, F).tobytes())
-            f.write(np.ascontiguousarray(moments, F).tobytes())
-        out = subprocess.run([str(exe), str(d / "in.bin"), str(d / "out.bin")], capture_output=True, text=True)
-        assert out.returncode == 0 and "adaptive cpu: ok" in out.stdout, (out.returncode, out.stderr)
-        raw = open(d / "out.bin", "rb").read()
+        data = [np.array([W, H, p.min_samples, p.radius], np.int32), np.array([p.threshold, p.floor], F), np.ascontiguousarray(frame, F), np.ascontiguousarray(moments, F)]
+        raw = cpu_header.run(exe, b"".join(a.tobytes() for a in data))
         n = W * H
         err = np.frombuffer(raw[:4 * n], F).reshape(H, W)
         mask = np.frombuffer(raw[4 * n:5 * n], np.uint8).reshape(H, W)
@@ -46,7 +33,7 @@ def cpu(tmp_path_factory):
     return run
 
 
-def synthetic(W, H, seed, max_n=40, holes=True):
+def noisy_frame(W, H, seed, max_n=40, holes=True):
     """A frame and its MOMENTS as a renderer with a per-pixel sample count would leave them: per pixel n samples around a mean, a
     constant strip (variance exactly 0), a dark strip (luminance below the floor), pixels without samples."""
     rng = np.random.default_rng(seed)
@@ -101,7 +88,7 @@ CASES = [
 @pytest.mark.parametrize("case", CASES, ids=lambda c: "-".join(str(v) for v in c))
 def test_cpu_header_equals_numpy_reference_bit_for_bit(cpu, case):
     W, H, seed, thr, floor, ms, radius = case
-    frame, mom = synthetic(W, H, seed)
+    frame, mom = noisy_frame(W, H, seed)
     p = params(thr, floor, ms, radius)
     err, mask, res = _check(cpu, frame, mom, p, f"case {case}")
     if W * H > 100:  # the inputs exercise both answers
@@ -179,7 +166,7 @@ def test_luminance_below_the_floor_is_an_absolute_error(cpu):
 
 
 def test_radius_zero_leaves_the_unconverged_map(cpu):
-    frame, mom = synthetic(45, 30, 21)
+    frame, mom = noisy_frame(45, 30, 21)
     p = params(threshold=0.1, radius=0)
     err, mask, res = _check(cpu, frame, mom, p, "radius 0")
     assert (mask.astype(bool) == adaptive.unconverged(err, p)).all()
@@ -205,7 +192,7 @@ def test_one_unconverged_pixel_in_a_corner_sets_the_clipped_square(cpu, radius, 
 
 
 def test_nan_and_inf_frames_do_not_count_as_unconverged_or_as_the_maximum(cpu):
-    frame, mom = synthetic(20, 10, 31, holes=False)
+    frame, mom = noisy_frame(20, 10, 31, holes=False)
     frame[..., 3] = np.maximum(frame[..., 3], F(16))
     frame[2, 3, :3] = F(np.inf)
     mom[2, 3, :3] = F(np.inf)

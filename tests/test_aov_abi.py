@@ -2,31 +2,25 @@
 disjoint from hrcore.h's and hrcore_group.h's, calls without a context fail loudly, the oracle-style Engine without the symbols still
 constructs, and the helper that turns the sums into means never divides by zero."""
 import ctypes
-import os
 import re
+import subprocess
 
 import numpy as np
 import pytest
 
+import abi_checks
 from heatray_amd import _ffi as ffi
 from heatray_amd import aov, core
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HEADER = os.path.join(ROOT, "include", "hrcore_aov.h")
-
-
-def aov_declared_functions():
-    return sorted(set(re.findall(r"\b(hr_[a-z0-9_]+)\s*\(", open(HEADER).read())))
+HEADER = "hrcore_aov.h"
 
 
 def test_aov_header_and_python_binding_agree():
-    assert sorted("hr_" + s for s in ffi.AOV_SYMBOLS) == aov_declared_functions()
-    assert not set(ffi.AOV_SYMBOLS) & set(ffi.ABI_SYMBOLS)
-    assert not set(ffi.AOV_SYMBOLS) & set(ffi.GROUP_SYMBOLS)
+    abi_checks.check_binding_agrees_and_is_disjoint(HEADER)
 
 
 def test_aov_constants_match_the_header():
-    text = open(HEADER).read()
+    text = abi_checks.header_text(HEADER)
     assert int(re.findall(r"#define HR_AOV_API_VERSION (\d+)u", text)[0]) == ffi.HR_AOV_API_VERSION
     assert int(re.findall(r"#define HR_AOV_SURFACE (\d+)u", text)[0]) == ffi.HR_AOV_SURFACE
     assert int(re.findall(r"#define HR_AOV_MOMENTS (\d+)u", text)[0]) == ffi.HR_AOV_MOMENTS
@@ -36,21 +30,16 @@ def test_aov_constants_match_the_header():
 
 
 def test_library_exports_every_aov_symbol_and_the_version_matches():
-    lib = core.load_library()
-    for name in aov_declared_functions():
-        assert hasattr(lib, name), name
-    lib.hr_aov_api_version.restype = ctypes.c_uint32
-    assert lib.hr_aov_api_version() == ffi.HR_AOV_API_VERSION
+    abi_checks.check_library_exports(HEADER)
 
 
 def test_header_compiles_as_c_and_adds_no_struct(tmp_path):
     # the header declares functions and constants only: nothing whose layout a ctypes mirror would have to follow
-    assert not re.search(r"\bstruct\b|\btypedef\b", open(HEADER).read().split("#include \"hrcore.h\"", 1)[1])
-    import subprocess
+    assert not re.search(r"\bstruct\b|\btypedef\b", abi_checks.header_text(HEADER).split("#include \"hrcore.h\"", 1)[1])
     src = tmp_path / "aov.c"
     src.write_text('#include "hrcore_aov.h"\nint main(void) { return (int)HR_AOV_API_VERSION - 1 + HR_AOV_PLANE_ALBEDO; }\n')
     exe = tmp_path / "aov"
-    subprocess.run(["gcc", "-Wall", "-Werror", "-I", os.path.join(ROOT, "include"), str(src), "-o", str(exe)], check=True, capture_output=True, text=True)
+    subprocess.run(["gcc", "-Wall", "-Werror", "-I", abi_checks.INCLUDE, str(src), "-o", str(exe)], check=True, capture_output=True, text=True)
     assert subprocess.run([str(exe)]).returncode == 0
 
 
@@ -71,11 +60,8 @@ def test_aov_calls_without_a_context_fail_loudly():
 
 def test_engine_without_aov_symbols_constructs_and_its_aov_calls_raise(oracle_lib):
     # the suite binds Engine to the CPU oracle, which has no AOVs: construction must not need them
-    eng = ffi.Engine(oracle_lib, "ora_")
-    for call in (lambda: eng.set_aovs(ffi.HR_AOV_SURFACE), eng.aovs, eng.aov_mask, lambda: eng.aov_plane(0), lambda: eng.aov_to_device(0, 16)):
-        with pytest.raises(ffi.EngineError, match="no AOVs"):
-            call()
-    eng.close()
+    abi_checks.check_oracle_engine_lacks(oracle_lib, lambda eng: (lambda: eng.set_aovs(ffi.HR_AOV_SURFACE), eng.aovs, eng.aov_mask, lambda: eng.aov_plane(0),
+                                                                  lambda: eng.aov_to_device(0, 16)), "no AOVs")
 
 
 def test_resolve_turns_sums_into_means_without_dividing_by_zero():

@@ -2,34 +2,11 @@
 (no GPU needed: hipcc cross-compiles gfx950).  Nothing in scratch; the a-trous kernels keep a row of five taps' loads in flight and
 still seven waves per SIMD (all 25 taps in flight cost 190 VGPRs and left two), and the tiled ones stay inside the LDS their tile and
 halo need."""
-import os
-import re
-import subprocess
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(ROOT, "heatray_amd", "csrc")
-
-
-def _resources(src):
-    flags = subprocess.run(["make", "-s", "-C", CSRC, "print-flags"], capture_output=True, text=True, check=True).stdout.split()
-    out = subprocess.run(["/opt/rocm/bin/hipcc", *flags, "-c", os.path.join(CSRC, src), "-o", os.devnull, "-Rpass-analysis=kernel-resource-usage"],
-                         capture_output=True, text=True, cwd=CSRC)
-    assert out.returncode == 0, out.stderr[-2000:]
-    res, name = {}, None
-    for line in out.stderr.splitlines():
-        m = re.search(r"remark:\s+Function Name: (\S+)", line)
-        if m:
-            name = subprocess.run(["c++filt", m.group(1)], capture_output=True, text=True).stdout.strip()
-            res[name] = {}
-            continue
-        m = re.search(r"remark:\s+([A-Za-z ]+?)(?: \[[^\]]*\])?: (\d+)", line)
-        if m and name:
-            res[name][m.group(1).strip()] = int(m.group(2))
-    return res
+from kernel_resources import resources
 
 
 def test_denoise_kernels_use_no_scratch_and_keep_their_occupancy():
-    res = _resources("hr_denoise.hip")
+    res = resources("hr_denoise.hip")
     kernels = {k.split("(")[0].replace("void ", "").replace("hr::", ""): v for k, v in res.items() if "k_denoise" in k}
     assert sorted(kernels) == ["k_denoise_atrous", "k_denoise_atrous_tiled<1>", "k_denoise_atrous_tiled<2>", "k_denoise_finish", "k_denoise_gradient",
                                "k_denoise_prepare"], sorted(kernels)

@@ -2,86 +2,27 @@
 numpy restatement heatray_amd.denoise.reference, bit for bit; the numpy exp_ against the oracle's; and properties of the reference
 whose answers are exact (include/hrcore_denoise.h is the contract).  tests/test_gpu_denoise.py holds the device to the same reference."""
 import ctypes as C
-import os
-import subprocess
 
 import numpy as np
 import pytest
 
+import cpu_header
+from device_support import same
 from heatray_amd import _ffi as ffi
 from heatray_amd import denoise
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-F = np.float32
-
-
-def params(iterations=5, normal_power=7, sigma_l=4.0, sigma_z=4.0):
-    p = denoise.default_params()
-    p.iterations, p.normal_power, p.sigma_l, p.sigma_z = iterations, normal_power, sigma_l, sigma_z
-    return p
-
-
-def synthetic(W, H, n_passes, seed, hits="partial", holes=False):
-    """A frame and its planes as n_passes of a noisy renderer would leave them: two surfaces split by a slanted edge, a background
-    strip, per-pass samples around a smooth mean."""
-    rng = np.random.default_rng(seed)
-    y, x = np.mgrid[0:H, 0:W].astype(F)
-    side = (x + F(0.5) * y) > F(0.55) * F(W)
-    frame, alb, nd, mom = (np.zeros((H, W, 4), F) for _ in range(4))
-    for _ in range(n_passes):
-        if hits == "none":
-            hit = np.zeros((H, W), bool)
-        elif hits == "all":
-            hit = np.ones((H, W), bool)
-        else:
-            hit = (rng.random((H, W)) < np.where(y < F(0.15) * F(H), 0.0, np.where(np.abs(x - F(0.3) * F(W)) < 2, 0.5, 1.0)))
-        base = np.where(side[..., None], F([0.8, 0.3, 0.2]), F([0.2, 0.5, 0.9])).astype(F) * (F(0.6) + F(0.4) * rng.random((H, W, 1)).astype(F))
-        light = (F(0.5) + x / F(max(W, 2))) [..., None] * rng.gamma(2.0, 0.5, (H, W, 3)).astype(F)
-        s = np.where(hit[..., None], base * light, F(0.7)).astype(F)
-        frame[..., :3] += s
-        frame[..., 3] += F(1)
-        mom[..., :3] += s * s
-        mom[..., 3] += F(1)
-        nrm = np.where(side[..., None], F([0.0, 0.6, 0.8]), F([0.6, 0.0, 0.8])).astype(F) + F(0.05) * rng.standard_normal((H, W, 3)).astype(F)
-        nrm = (nrm / np.linalg.norm(nrm, axis=-1, keepdims=True)).astype(F)
-        depth = (F(3.0) + F(0.02) * x + np.where(side, F(1.5), F(0.0)) + F(0.01) * rng.random((H, W)).astype(F)).astype(F)
-        alb[..., :3] += np.where(hit[..., None], base, F(0))
-        alb[..., 3] += hit
-        nd[..., :3] += np.where(hit[..., None], nrm, F(0))
-        nd[..., 3] += np.where(hit, depth, F(0))
-    if holes:
-        dead = rng.random((H, W)) < 0.3
-        for p in (frame, alb, nd, mom):
-            p[dead] = 0
-    return frame, {"albedo": alb, "normal_depth": nd, "moments": mom}
+from synthetic_frames import F, filter_params as params, synthetic
 
 
 @pytest.fixture(scope="module")
 def cpu_filter(tmp_path_factory):
-    d = tmp_path_factory.mktemp("denoise_cpu")
-    exe = d / "denoise_cpu"
-    # -ffp-contract=off like the library: the header's float lines must mean the same on both sides
-    subprocess.check_call(["g++", "-std=c++17", "-O1", "-ffp-contract=off", "-Wall", "-I" + os.path.join(ROOT, "heatray_amd", "csrc"),
-                           os.path.join(ROOT, "tests", "host", "denoise_cpu.cpp"), "-o", str(exe)])
+    exe = cpu_header.build("denoise", tmp_path_factory.mktemp("denoise_cpu"))
 
     def run(frame, planes, p):
         H, W = frame.shape[:2]
-        with open(d / "in.bin", "wb") as f:
-            f.write(np.array([W, H, p.iterations, p.normal_power], np.int32).tobytes())
-            f.write(np.array([p.sigma_l, p.sigma_z], F).tobytes())
-            for a in (frame, planes["albedo"], planes["normal_depth"], planes["moments"]):
-                f.write(np.ascontiguousarray(a, F).tobytes())
-        out = subprocess.run([str(exe), str(d / "in.bin"), str(d / "out.bin")], capture_output=True, text=True)
-        assert out.returncode == 0 and "denoise cpu: ok" in out.stdout, (out.returncode, out.stderr)
-        return np.fromfile(d / "out.bin", F).reshape(H, W, 4)
+        data = [np.array([W, H, p.iterations, p.normal_power], np.int32), np.array([p.sigma_l, p.sigma_z], F)]
+        data += [np.ascontiguousarray(a, F) for a in (frame, planes["albedo"], planes["normal_depth"], planes["moments"])]
+        return np.frombuffer(cpu_header.run(exe, b"".join(a.tobytes() for a in data)), F).reshape(H, W, 4)
     return run
-
-
-def _same(got, want, what):
-    g, w = got.view(np.uint32), want.view(np.uint32)
-    bad = np.argwhere((g != w).any(-1))
-    assert len(bad) == 0, f"{what}: {len(bad)} of {g.shape[0] * g.shape[1]} pixels differ, first at (y, x) = {tuple(bad[0])}: " \
-                          f"{got[tuple(bad[0])]} against {want[tuple(bad[0])]}"
 
 
 CASES = [
@@ -104,7 +45,7 @@ def test_cpu_header_equals_numpy_reference_bit_for_bit(cpu_filter, case):
     p = params(it, power, sl, sz)
     want = denoise.reference(frame, planes, p)
     assert np.isfinite(want).all()
-    _same(cpu_filter(frame, planes, p), want, f"case {case}")
+    same(cpu_filter(frame, planes, p), want, f"case {case}")
 
 
 def test_numpy_exp_equals_the_oracles_bit_for_bit(oracle_lib):

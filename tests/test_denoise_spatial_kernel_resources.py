@@ -1,34 +1,11 @@
 """Resource budgets of the spatial variance estimate's kernel (heatray_amd/csrc/hr_denoise_spatial.hip), checked at build time like
 test_denoise_kernel_resources.py (no GPU needed: hipcc cross-compiles gfx950).  Nothing in scratch, no spill, no AGPRs; the LDS is the
 staged tile and the counters and nothing else (a struct copied through a private array once showed up as 3072 more bytes of it)."""
-import os
-import re
-import subprocess
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(ROOT, "heatray_amd", "csrc")
-
-
-def _resources(src):
-    flags = subprocess.run(["make", "-s", "-C", CSRC, "print-flags"], capture_output=True, text=True, check=True).stdout.split()
-    out = subprocess.run(["/opt/rocm/bin/hipcc", *flags, "-c", os.path.join(CSRC, src), "-o", os.devnull, "-Rpass-analysis=kernel-resource-usage"],
-                         capture_output=True, text=True, cwd=CSRC)
-    assert out.returncode == 0, out.stderr[-2000:]
-    res, name = {}, None
-    for line in out.stderr.splitlines():
-        m = re.search(r"remark:\s+Function Name: (\S+)", line)
-        if m:
-            name = subprocess.run(["c++filt", m.group(1)], capture_output=True, text=True).stdout.strip()
-            res[name] = {}
-            continue
-        m = re.search(r"remark:\s+([A-Za-z ]+?)(?: \[[^\]]*\])?: (\d+)", line)
-        if m and name:
-            res[name][m.group(1).strip()] = int(m.group(2))
-    return res
+from kernel_resources import resources
 
 
 def test_spatial_kernel_uses_no_scratch_and_only_its_tile_of_lds():
-    res = _resources("hr_denoise_spatial.hip")
+    res = resources("hr_denoise_spatial.hip")
     kernels = {k.split("(")[0].replace("void ", "").replace("hr::", ""): v for k, v in res.items()}
     assert sorted(kernels) == ["k_spatial_variance"], sorted(kernels)
     for name, r in kernels.items():

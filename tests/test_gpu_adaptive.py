@@ -11,41 +11,11 @@ import numpy as np
 import pytest
 
 import oracle_lib
+from device_support import BOTH, F, device_engine, host_tables, same
 from heatray_amd import _ffi as ffi
 from heatray_amd import adaptive, convergence, core, denoise, scenes
 
 pytestmark = pytest.mark.gpu
-F = np.float32
-BOTH = ffi.HR_AOV_SURFACE | ffi.HR_AOV_MOMENTS
-
-_TABLE_CACHE = {}
-
-
-def host_tables(sc):
-    """Sample tables made once on the host by the oracle's generators and uploaded to both engines (as tests/test_gpu_parity.py does)."""
-    key = (sc.options.sample_mode, sc.options.bokeh_shape, sc.options.max_render_passes, sc.width, sc.height)
-    if key not in _TABLE_CACHE:
-        o = oracle_lib.engine()
-        P = sc.options.max_render_passes
-        seq = np.stack([o.qmc_generate(sc.options.sample_mode, s, P) for s in range(16)])
-        ap = np.stack([o.qmc_generate(ffi.HR_SAMPLE_SOBOL, s, P, radial=True) for s in range(16)])
-        off = o.qmc_generate(ffi.HR_SAMPLE_SOBOL, 0, sc.width * sc.height)
-        o.close()
-        _TABLE_CACHE[key] = (seq, ap, off)
-    return _TABLE_CACHE[key]
-
-
-def _same(a, b, what):
-    a, b = np.ascontiguousarray(a), np.ascontiguousarray(b)
-    assert a.shape == b.shape and a.dtype == b.dtype, (what, a.shape, b.shape, a.dtype, b.dtype)
-    if a.tobytes() != b.tobytes():
-        ua = a.view(np.uint32) if a.dtype == F else a
-        ub = b.view(np.uint32) if b.dtype == F else b
-        bad = (ua != ub).reshape(a.shape[0], a.shape[1], -1).any(axis=-1)
-        ys, xs = np.nonzero(bad)
-        raise AssertionError(f"{what}: {int(bad.sum())} pixels differ, first at (x={xs[0]}, y={ys[0]}): {a[ys[0], xs[0]]} vs {b[ys[0], xs[0]]}")
-
-
 def make_masks(W, H, seed=7):
     """Three host masks (H x W uint8): a checkerboard; SplitMix64-random BYTES (any non-zero value means sampled), about half of them
     zero; whole 8 x 8 blocks chosen at random with every other 32 x 32 tile emptied."""
@@ -72,14 +42,6 @@ def oracle_samples(sc, pass_params, golden):
         out.append(o.readback())
     o.close()
     return out
-
-
-def device_engine(sc, golden, aovs=0, **kw):
-    eng = core.create_engine(**kw)
-    sc.apply(eng, lut=golden["multiscatter_lut"], tables=host_tables(sc))
-    if aovs:
-        eng.set_aovs(aovs)
-    return eng
 
 
 def device_pass_planes(sc, pass_params, golden):
@@ -147,17 +109,17 @@ def test_the_mask_decides_who_is_sampled_and_nothing_else(golden, name):
     frame, mom = construct(oracle_samples(sc, pps, golden), per_pass)
     al, nd = construct_planes(device_pass_planes(sc, pps, golden), per_pass)
     got = eng.readback()
-    _same(got, frame, f"{name}: frame")
+    same(got, frame, f"{name}: frame")
     planes = eng.aovs()
     assert planes["passes"] == 3 * B
-    _same(planes["moments"], mom, f"{name}: MOMENTS")
-    _same(planes["albedo"], al, f"{name}: ALBEDO")
-    _same(planes["normal_depth"], nd, f"{name}: NORMAL_DEPTH")
-    _same(got[..., 3], sum(((m != 0).astype(F) * F(B) for m in masks), np.zeros((sc.height, sc.width), F)), f"{name}: alpha = per-pixel sample count")
+    same(planes["moments"], mom, f"{name}: MOMENTS")
+    same(planes["albedo"], al, f"{name}: ALBEDO")
+    same(planes["normal_depth"], nd, f"{name}: NORMAL_DEPTH")
+    same(got[..., 3], sum(((m != 0).astype(F) * F(B) for m in masks), np.zeros((sc.height, sc.width), F)), f"{name}: alpha = per-pixel sample count")
     assert eng.stats().paths == sum(int((m != 0).sum()) * B for m in masks)
     m, installed = eng.sample_mask()
     assert installed
-    _same(m, (masks[2] != 0).astype(np.uint8), f"{name}: sample_mask()")
+    same(m, (masks[2] != 0).astype(np.uint8), f"{name}: sample_mask()")
     eng.close()
 
 
@@ -176,10 +138,10 @@ def test_all_ones_none_all_zeros_clear_and_resize(golden):
     plain.close()
 
     def check(eng, what):
-        _same(eng.readback(), frame, what + ": frame")
+        same(eng.readback(), frame, what + ": frame")
         got = eng.aovs()
         for k in ("albedo", "normal_depth", "moments"):
-            _same(got[k], planes[k], f"{what}: {k}")
+            same(got[k], planes[k], f"{what}: {k}")
         s = eng.stats().as_dict()
         assert {k: v for k, v in s.items() if k != "ms"} == {k: v for k, v in stats.items() if k != "ms"}, what
 
@@ -250,8 +212,8 @@ def test_the_mask_is_honoured_on_every_camera_path(golden, monkeypatch, mode):
     masked_render(eng, pps, masks, B)
     frame, mom = construct(oracle_samples(sc, pps, golden), [masks[k // B] for k in range(3 * B)])
     got = eng.readback()
-    _same(got, frame, f"{mode}: frame")
-    _same(eng.aovs()["moments"], mom, f"{mode}: MOMENTS")
+    same(got, frame, f"{mode}: frame")
+    same(eng.aovs()["moments"], mom, f"{mode}: MOMENTS")
     assert eng.stats().paths == int(frame[..., 3].sum())
     if mode == "interactive":
         assert 0 < frame[..., 3].sum() < sum(int((m != 0).sum()) * B for m in masks)
@@ -276,16 +238,16 @@ def test_the_mask_at_1920_x_1080(golden):
     eng.set_aovs(ffi.HR_AOV_MOMENTS)
     masked_render(eng, pps, [mask], B)
     frame, mom = construct(samples, [mask] * B)
-    _same(eng.readback(), frame, "1080p: frame")
-    _same(eng.aovs()["moments"], mom, "1080p: MOMENTS")
+    same(eng.readback(), frame, "1080p: frame")
+    same(eng.aovs()["moments"], mom, "1080p: MOMENTS")
     assert eng.stats().paths == int((mask != 0).sum()) * B
     # ... and the mask the device builds from it equals the reference at this size
     p = adaptive.default_params()
     p.min_samples = min(16, B)
     r = eng.adaptive_update(p)
     err = adaptive.reference_error(frame, mom, p)
-    _same(eng.adaptive_error(), err, "1080p: error map")
-    _same(eng.sample_mask()[0], adaptive.reference_mask(err, p), "1080p: mask")
+    same(eng.adaptive_error(), err, "1080p: error map")
+    same(eng.sample_mask()[0], adaptive.reference_mask(err, p), "1080p: mask")
     want = adaptive.reference_result(err, p, passes=B)
     assert (r.unconverged_pixels, r.active_pixels, r.passes) == (want["unconverged_pixels"], want["active_pixels"], B)
     assert F(r.max_error).tobytes() == F(want["max_error"]).tobytes()
@@ -305,7 +267,7 @@ def _check_update(eng, p, what, install=True):
     r = eng.adaptive_update(p, install=install)
     q = p if p is not None else adaptive.default_params()
     err = adaptive.reference_error(frame, mom, q)
-    _same(eng.adaptive_error(), err, what + ": error map")
+    same(eng.adaptive_error(), err, what + ": error map")
     want = adaptive.reference_result(err, q, passes=int(eng.aovs()["passes"]))
     got = r.as_dict()
     assert F(got.pop("max_error")).tobytes() == F(want.pop("max_error")).tobytes(), (what, r.max_error)
@@ -314,7 +276,7 @@ def _check_update(eng, p, what, install=True):
     if install:
         m, installed = eng.sample_mask()
         assert installed
-        _same(m, mask, what + ": installed mask")
+        same(m, mask, what + ": installed mask")
     return err, mask, r
 
 
@@ -341,7 +303,7 @@ def test_adaptive_update_equals_the_reference(name):
     _check_update(eng, adaptive.default_params(), f"{name}: defaults, not installed", install=False)
     m, installed = eng.sample_mask()
     assert installed
-    _same(m, checker, f"{name}: the mask in force after install == 0")
+    same(m, checker, f"{name}: the mask in force after install == 0")
     # the defaults: neither empty nor full after 16 passes
     err, mask, r = _check_update(eng, None, f"{name}: defaults")
     share = r.active_pixels / px
@@ -365,7 +327,7 @@ def test_adaptive_update_equals_the_reference(name):
     paths = eng.stats().paths
     for k in range(16, 20):
         eng.render_pass(sc.options.pass_params(k))
-    _same(eng.readback(), before, f"{name}: passes under an empty mask")
+    same(eng.readback(), before, f"{name}: passes under an empty mask")
     assert eng.stats().paths == paths
     # the device copy of the map, on the context's stream and on a foreign one
     import torch
@@ -375,7 +337,7 @@ def test_adaptive_update_equals_the_reference(name):
         eng.adaptive_error_to_device(t.data_ptr(), stream=stream.cuda_stream if stream else None)
         eng.synchronize()
         torch.cuda.synchronize()
-        _same(t.cpu().numpy(), want, f"{name}: hr_adaptive_error_copy")
+        same(t.cpu().numpy(), want, f"{name}: hr_adaptive_error_copy")
     eng.close()
 
 
@@ -439,7 +401,7 @@ def test_errors_and_the_context_stays_usable():
         before = eng.sample_mask()[0]
         with pytest.raises(ffi.EngineError, match=text):
             eng.adaptive_update(_params(**kw))
-        _same(eng.sample_mask()[0], before, f"the mask after a refused update ({kw})")
+        same(eng.sample_mask()[0], before, f"the mask after a refused update ({kw})")
         _check_update(eng, _params(min_samples=2, radius=1), f"usable after {kw}")
     eng.close()
 
@@ -474,15 +436,15 @@ def test_a_context_group_gives_the_plain_contexts_results(n):
     grp.clear()
     assert not grp.sample_mask()[1]
     grp.close()
-    _same(got[0], want[0], f"group of {n}: masked frame")
-    _same(got[1], want[1], f"group of {n}: error map")
+    same(got[0], want[0], f"group of {n}: masked frame")
+    same(got[1], want[1], f"group of {n}: error map")
     assert got[2][1] and want[2][1]
-    _same(got[2][0], want[2][0], f"group of {n}: mask")
+    same(got[2][0], want[2][0], f"group of {n}: mask")
     assert got[3] == want[3], (got[3], want[3])
-    _same(got[4], want[4], f"group of {n}: MOMENTS")
-    _same(got[5], want[5], f"group of {n}: frame after passes under the built mask")
+    same(got[4], want[4], f"group of {n}: MOMENTS")
+    same(got[5], want[5], f"group of {n}: frame after passes under the built mask")
     assert got[6] == want[6]
-    _same(got[5][..., 3], want[0][..., 3] + F(4) * want[2][0].astype(F), f"group of {n}: sample counts")
+    same(got[5][..., 3], want[0][..., 3] + F(4) * want[2][0].astype(F), f"group of {n}: sample counts")
 
 
 # ------------------------------------------------------------------------------------------------ 7
@@ -503,7 +465,7 @@ def test_the_denoiser_on_an_adaptively_sampled_frame():
     for kernel in (ffi.HR_DENOISE_KERNEL_PLAIN, ffi.HR_DENOISE_KERNEL_TILED):
         p = denoise.default_params()
         p.kernel = kernel
-        _same(eng.denoise(p), want, f"denoise of an adaptively sampled frame, kernel {kernel}")
+        same(eng.denoise(p), want, f"denoise of an adaptively sampled frame, kernel {kernel}")
     eng.close()
 
 

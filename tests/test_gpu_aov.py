@@ -7,33 +7,13 @@ import ctypes as C
 import numpy as np
 import pytest
 
+from device_support import F, render_passes, same
 from heatray_amd import _ffi as ffi
 from heatray_amd import aov, core, host, scenes
 
 pytestmark = pytest.mark.gpu
-F = np.float32
 SURF, MOM, BOTH = ffi.HR_AOV_SURFACE, ffi.HR_AOV_MOMENTS, ffi.HR_AOV_SURFACE | ffi.HR_AOV_MOMENTS
 ALB, ND, MOMP = ffi.HR_AOV_PLANE_ALBEDO, ffi.HR_AOV_PLANE_NORMAL_DEPTH, ffi.HR_AOV_PLANE_MOMENTS
-
-
-def _params(sc, s, **kw):
-    p = sc.options.pass_params(s)
-    for k, v in kw.items():
-        setattr(p, k, v)
-    return p
-
-
-def _render(eng, sc, passes, **kw):
-    for s in passes:
-        eng.render_pass(_params(sc, s, **kw))
-
-
-def _same(a, b, what):
-    assert a.shape == b.shape, what
-    if a.tobytes() != b.tobytes():
-        bad = (a.view(np.uint32) != b.view(np.uint32)).reshape(a.shape[0], a.shape[1], -1).any(axis=-1)
-        ys, xs = np.nonzero(bad)
-        raise AssertionError(f"{what}: {int(bad.sum())} pixels differ, first at (x={xs[0]}, y={ys[0]}): {a[ys[0], xs[0]]} vs {b[ys[0], xs[0]]}")
 
 
 def _run(sc, mask, passes, engine=None, **kw):
@@ -42,7 +22,7 @@ def _run(sc, mask, passes, engine=None, **kw):
     sc.apply(eng)
     if mask:
         eng.set_aovs(mask)
-    _render(eng, sc, passes, **kw)
+    render_passes(eng, sc, passes, **kw)
     frame = eng.readback()
     planes = eng.aovs() if mask else {}
     eng.close()
@@ -72,10 +52,10 @@ def test_frame_is_unchanged_with_aovs_on(case):
     for mask in (SURF, BOTH):
         sc, kw = FRAME_CASES[case]()
         on, planes = _run(sc, mask, range(6), **kw)
-        _same(on, off, f"{case}: frame with AOVs {mask}")
+        same(on, off, f"{case}: frame with AOVs {mask}")
         assert planes["passes"] == 6
         if mask & MOM:
-            _same(planes["moments"][..., 3:], on[..., 3:], f"{case}: MOMENTS.a is the frame's alpha")
+            same(planes["moments"][..., 3:], on[..., 3:], f"{case}: MOMENTS.a is the frame's alpha")
 
 
 def test_frame_is_unchanged_in_interactive_mode():
@@ -94,7 +74,7 @@ def test_frame_is_unchanged_in_interactive_mode():
         return out
     off, _ = run(0)
     on, planes = run(BOTH)
-    _same(on, off, "interactive")
+    same(on, off, "interactive")
     assert (planes["moments"][..., 3] == on[..., 3]).all() and (on[..., 3] == 1.0).all()
     assert (planes["albedo"][..., 3] <= 1.0).all() and planes["albedo"][..., 3].sum() > 0
 
@@ -105,9 +85,9 @@ def test_frame_is_unchanged_under_a_tight_memory_budget():
     sc = scenes.triangle_soup(20000, width=320, height=180, bounces=4, env=True)
     tight = core.create_engine(memory_budget=256 << 20)
     on, planes = _run(sc, BOTH, range(24), engine=tight)
-    _same(on, off, "memory budget")
+    same(on, off, "memory budget")
     assert planes["passes"] == 24
-    _same(planes["moments"][..., 3:], on[..., 3:], "memory budget: MOMENTS.a")
+    same(planes["moments"][..., 3:], on[..., 3:], "memory budget: MOMENTS.a")
 
 
 # ------------------------------------------------------------------------------------------------ 2. ALBEDO = HR_VIS_BASE_COLOR
@@ -124,7 +104,7 @@ def test_albedo_is_the_base_color_visualizer(name):
     frame, planes = _run(ALBEDO_SCENES[name](), SURF, range(n))
     vis, _ = _run(ALBEDO_SCENES[name](), 0, range(n), enable_visualizer=1, visualizer_mode=ffi.HR_VIS_BASE_COLOR)
     alb = planes["albedo"]
-    _same(alb[..., :3].copy(), vis[..., :3].copy(), f"{name}: ALBEDO.rgb vs HR_VIS_BASE_COLOR")
+    same(alb[..., :3].copy(), vis[..., :3].copy(), f"{name}: ALBEDO.rgb vs HR_VIS_BASE_COLOR")
     assert (alb[..., 3] == vis[..., 3] - frame[..., 3]).all(), name
     assert alb[..., 3].max() == n and alb[..., :3].max() > 0.0
     if name == "stacked_sheets":  # every camera ray passes the sheets: what one pass records is the surface behind them
@@ -162,7 +142,7 @@ def test_normals_per_pass_are_the_final_normals_visualizer():
         vis, _ = _run(_normal_mapped_scene(), 0, [k], enable_visualizer=1, visualizer_mode=ffi.HR_VIS_FINAL_NORMALS)
         nd, hit = planes["normal_depth"], planes["albedo"][..., 3] > 0
         want = np.where(hit[..., None], (nd[..., :3] + F(1.0)) * F(0.5), F(0.0)).astype(F)
-        _same(want, vis[..., :3].copy(), f"sample {k}: (N + 1) * 0.5 vs HR_VIS_FINAL_NORMALS")
+        same(want, vis[..., :3].copy(), f"sample {k}: (N + 1) * 0.5 vs HR_VIS_FINAL_NORMALS")
         assert hit.mean() > 0.5 and (nd[~hit] == 0).all()
 
 
@@ -247,8 +227,8 @@ def test_moments_are_the_sequential_sum_of_squared_samples(estimator):
         want[..., 3] = want[..., 3] + s[..., 3]
     frame, planes = _run(mk(), MOM, range(K), estimator=estimator)
     assert set(planes) == {"moments", "passes"} and planes["passes"] == K
-    _same(planes["moments"], want, "MOMENTS vs numpy")
-    _same(planes["moments"][..., 3:], frame[..., 3:], "MOMENTS.a vs the frame's alpha")
+    same(planes["moments"], want, "MOMENTS vs numpy")
+    same(planes["moments"][..., 3:], frame[..., 3:], "MOMENTS.a vs the frame's alpha")
     r = aov.resolve(planes, frame)
     assert np.isfinite(r["variance"]).all() and r["variance"].max() > 0
 
@@ -261,12 +241,12 @@ def test_life_cycle():
     with pytest.raises(ffi.EngineError, match="not enabled"):
         eng.aov_plane(ALB)
     assert eng.aov_mask() == 0 and eng.aovs() == {}
-    _render(eng, sc, range(3))
+    render_passes(eng, sc, range(3))
     eng.set_aovs(BOTH)                                    # enabled after 3 passes: the planes start at zero
     assert eng.aov_mask() == BOTH
     alb, n = eng.aov_plane(ALB)
     assert n == 0 and not alb.any()
-    _render(eng, sc, range(3, 7))
+    render_passes(eng, sc, range(3, 7))
     frame = eng.readback()
     planes = eng.aovs()
     assert planes["passes"] == 4 and (planes["moments"][..., 3] == 4).all() and (frame[..., 3] == 7).all()
@@ -274,9 +254,9 @@ def test_life_cycle():
     ref = core.create_engine()
     sc.apply(ref)
     ref.set_aovs(BOTH)
-    _render(ref, sc, range(3, 7))
+    render_passes(ref, sc, range(3, 7))
     for name in ("albedo", "normal_depth", "moments"):
-        _same(planes[name], ref.aovs()[name], f"enabled late: {name}")
+        same(planes[name], ref.aovs()[name], f"enabled late: {name}")
     ref.close()
     for bad in (-1, 3, 99):
         with pytest.raises(ffi.EngineError, match="bad AOV plane"):
@@ -287,12 +267,12 @@ def test_life_cycle():
     for p in (ALB, ND, MOMP):
         a, n = eng.aov_plane(p)
         assert n == 0 and not a.any()
-    _render(eng, sc, range(2))
+    render_passes(eng, sc, range(2))
     eng.resize(40, 30)                                    # so does a resize, at the new size
     for p in (ALB, ND, MOMP):
         a, n = eng.aov_plane(p)
         assert a.shape == (30, 40, 4) and n == 0 and not a.any()
-    _render(eng, sc, range(2))
+    render_passes(eng, sc, range(2))
     assert eng.aovs()["passes"] == 2
     eng.set_aovs(MOM)                                     # a smaller mask frees what it no longer names
     with pytest.raises(ffi.EngineError, match="not enabled"):
@@ -301,7 +281,7 @@ def test_life_cycle():
     for p in (ALB, ND, MOMP):
         with pytest.raises(ffi.EngineError, match="not enabled"):
             eng.aov_plane(p)
-    _render(eng, sc, range(2))                             # and the plain path renders on
+    render_passes(eng, sc, range(2))                             # and the plain path renders on
     assert (eng.readback()[..., 3] == 4).all()
     eng.close()
 
@@ -312,18 +292,18 @@ def test_aov_to_device_is_the_readback():
     eng = core.create_engine()
     sc.apply(eng)
     eng.set_aovs(BOTH)
-    _render(eng, sc, range(4))
+    render_passes(eng, sc, range(4))
     for p in (ALB, ND, MOMP):
         t = torch.empty((36, 64, 4), dtype=torch.float32, device="cuda:0")
         eng.aov_to_device(p, t.data_ptr())
         eng.synchronize()
         torch.cuda.synchronize()
-        _same(t.cpu().numpy(), eng.aov_plane(p)[0], f"plane {p}: device copy")
+        same(t.cpu().numpy(), eng.aov_plane(p)[0], f"plane {p}: device copy")
     s = torch.cuda.Stream()
     t = torch.empty((36, 64, 4), dtype=torch.float32, device="cuda:0")
     eng.aov_to_device(ALB, t.data_ptr(), stream=s.cuda_stream)
     s.synchronize()
-    _same(t.cpu().numpy(), eng.aov_plane(ALB)[0], "copy on a foreign stream")
+    same(t.cpu().numpy(), eng.aov_plane(ALB)[0], "copy on a foreign stream")
     eng.close()
 
 
@@ -333,9 +313,9 @@ def test_planes_do_not_depend_on_scheduling(tune, monkeypatch):
     ref_frame, ref = _run(mk(), BOTH, range(10))
     monkeypatch.setenv("HR_TUNE", tune)
     frame, planes = _run(mk(), BOTH, range(10))
-    _same(frame, ref_frame, f"{tune}: frame")
+    same(frame, ref_frame, f"{tune}: frame")
     for name in ("albedo", "normal_depth", "moments"):
-        _same(planes[name], ref[name], f"{tune}: {name}")
+        same(planes[name], ref[name], f"{tune}: {name}")
 
 
 # ------------------------------------------------------------------------------------------------------------- 7. sharding
@@ -352,18 +332,18 @@ def test_group_of_three_on_one_device_gives_a_plain_contexts_planes():
     sc.apply(grp)
     grp.set_aovs(BOTH)
     assert grp.aov_mask() == BOTH
-    _render(grp, sc, range(5))
-    _same(grp.readback(), ref_frame, "group frame")
+    render_passes(grp, sc, range(5))
+    same(grp.readback(), ref_frame, "group frame")
     planes = grp.aovs()
     assert planes["passes"] == 5
     for name in ("albedo", "normal_depth", "moments"):
-        _same(planes[name], ref[name], f"group: {name}")
+        same(planes[name], ref[name], f"group: {name}")
     import torch
     t = torch.empty((70, 100, 4), dtype=torch.float32, device="cuda:0")
     grp.aov_to_device(ND, t.data_ptr())
     grp.synchronize()
     torch.cuda.synchronize()
-    _same(t.cpu().numpy(), ref["normal_depth"], "group: device copy")
+    same(t.cpu().numpy(), ref["normal_depth"], "group: device copy")
     grp.clear()
     a, n = grp.aov_plane(MOMP)
     assert n == 0 and not a.any()
@@ -378,5 +358,5 @@ def test_tile_sharded_contexts_own_their_pixels_and_zero_the_rest():
         _, planes = _run(mk(), BOTH, range(4), engine=eng)
         own = _owned(70, 100, 16, rank, 3)
         for name in ("albedo", "normal_depth", "moments"):
-            _same(planes[name][own], ref[name][own], f"rank {rank}: {name} on owned pixels")
+            same(planes[name][own], ref[name][own], f"rank {rank}: {name} on owned pixels")
             assert (planes[name][~own].view(np.uint32) == 0).all(), (rank, name)

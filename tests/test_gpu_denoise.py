@@ -13,41 +13,12 @@ import numpy as np
 import pytest
 
 import oracle_lib
+from device_support import BOTH, denoise_params, engine_with_passes, render_passes, same, truth
 from heatray_amd import _ffi as ffi
 from heatray_amd import core, denoise, scenes
 
 pytestmark = pytest.mark.gpu
-F = np.float32
-BOTH = ffi.HR_AOV_SURFACE | ffi.HR_AOV_MOMENTS
 AUTO, PLAIN, TILED = ffi.HR_DENOISE_KERNEL_AUTO, ffi.HR_DENOISE_KERNEL_PLAIN, ffi.HR_DENOISE_KERNEL_TILED
-
-
-def _params(iterations=5, kernel=AUTO, normal_power=7, sigma_l=4.0, sigma_z=4.0):
-    p = denoise.default_params()
-    p.iterations, p.kernel, p.normal_power, p.sigma_l, p.sigma_z = iterations, kernel, normal_power, sigma_l, sigma_z
-    return p
-
-
-def _render(eng, sc, passes):
-    for s in passes:
-        eng.render_pass(sc.options.pass_params(s))
-
-
-def _engine(sc, passes, mask=BOTH):
-    eng = core.create_engine()
-    sc.apply(eng)
-    if mask:
-        eng.set_aovs(mask)
-    _render(eng, sc, passes)
-    return eng
-
-
-def _same(a, b, what):
-    assert a.shape == b.shape, what
-    if a.tobytes() != b.tobytes():
-        bad = (a.view(np.uint32) != b.view(np.uint32)).reshape(a.shape[0], a.shape[1], -1).any(axis=-1)
-        ys, xs = np.nonzero(bad)
-        raise AssertionError(f"{what}: {int(bad.sum())} pixels differ, first at (x={xs[0]}, y={ys[0]}): {a[ys[0], xs[0]]} vs {b[ys[0], xs[0]]}")
 
 
 SCENES = {
@@ -61,26 +32,26 @@ SCENES = {
 @pytest.mark.parametrize("name", sorted(SCENES))
 def test_device_equals_reference(name):
     sc = SCENES[name]()
-    eng = _engine(sc, range(4))
+    eng = engine_with_passes(sc, range(4))
     frame, planes = eng.readback(), eng.aovs()
     want = denoise.reference(frame, planes)
     assert np.isfinite(want).all() and (want[..., 3] == 1).all()
     for kernel in (AUTO, PLAIN, TILED):
-        got, n = eng.denoise(_params(kernel=kernel), with_passes=True)
+        got, n = eng.denoise(denoise_params(kernel=kernel), with_passes=True)
         assert n == 4
-        _same(got, want, f"{name}, kernel {kernel}")
-    _same(eng.denoise(), want, f"{name}, NULL params")
+        same(got, want, f"{name}, kernel {kernel}")
+    same(eng.denoise(), want, f"{name}, NULL params")
     eng.close()
 
 
 @pytest.mark.parametrize("iterations", range(0, 6))
 def test_every_iteration_count(iterations):
     sc = SCENES["multi_material"]()
-    eng = _engine(sc, range(3))
+    eng = engine_with_passes(sc, range(3))
     frame, planes = eng.readback(), eng.aovs()
-    want = denoise.reference(frame, planes, _params(iterations))
+    want = denoise.reference(frame, planes, denoise_params(iterations))
     for kernel in (PLAIN, TILED):
-        _same(eng.denoise(_params(iterations, kernel)), want, f"{iterations} iterations, kernel {kernel}")
+        same(eng.denoise(denoise_params(iterations, kernel)), want, f"{iterations} iterations, kernel {kernel}")
     if iterations == 0:  # the remodulated mean
         c = frame[..., :3] / frame[..., 3:4]
         assert np.abs(want[..., :3] - c).max() <= 4 * np.spacing(np.abs(c).max())
@@ -89,12 +60,12 @@ def test_every_iteration_count(iterations):
 
 def test_non_default_sigmas_and_normal_power():
     sc = SCENES["cornell"]()
-    eng = _engine(sc, range(6))
+    eng = engine_with_passes(sc, range(6))
     frame, planes = eng.readback(), eng.aovs()
     outs = []
     for kw in (dict(sigma_l=1.5, sigma_z=0.5, normal_power=2), dict(sigma_l=0.0, sigma_z=0.0, normal_power=0), dict(iterations=8, sigma_l=8.0, normal_power=16)):
-        want = denoise.reference(frame, planes, _params(**kw))
-        _same(eng.denoise(_params(**kw)), want, str(kw))
+        want = denoise.reference(frame, planes, denoise_params(**kw))
+        same(eng.denoise(denoise_params(**kw)), want, str(kw))
         outs.append(want)
     assert outs[0].tobytes() != outs[2].tobytes()
     eng.close()
@@ -114,8 +85,8 @@ def test_interactive_mode_holes():
     assert 0.3 < holes.mean() < 0.8
     want = denoise.reference(frame, planes)
     for kernel in (PLAIN, TILED):
-        got = eng.denoise(_params(kernel=kernel))
-        _same(got, want, f"interactive, kernel {kernel}")
+        got = eng.denoise(denoise_params(kernel=kernel))
+        same(got, want, f"interactive, kernel {kernel}")
     assert (got[holes] == 0).all() and (got[~holes][:, 3] == 1).all()
     # one-sample pixels have no variance estimate: they pass through (taps of exactly equal luminance aside)
     # (a tap weighs exp_(-|dl| / 1e-6) there: only a neighbour within ~1e-5 in demodulated luminance can mix in)
@@ -126,29 +97,29 @@ def test_interactive_mode_holes():
 
 def test_1080p():
     sc = scenes.multi_material(1920, 1080, bounces=3, textured=True)
-    eng = _engine(sc, range(4))
+    eng = engine_with_passes(sc, range(4))
     frame, planes = eng.readback(), eng.aovs()
     got = eng.denoise()
-    _same(got, denoise.reference(frame, planes), "1920 x 1080, AUTO")
+    same(got, denoise.reference(frame, planes), "1920 x 1080, AUTO")
     eng.close()
 
 
 def test_device_output_on_a_foreign_stream_and_display():
     import torch
     sc = SCENES["multi_material"]()
-    eng = _engine(sc, range(4))
+    eng = engine_with_passes(sc, range(4))
     want = eng.denoise()
     H, W = want.shape[:2]
     t = torch.zeros((H, W, 4), dtype=torch.float32, device="cuda:0")
     eng.denoise_to_device(t.data_ptr())  # the ctx stream
     eng.synchronize()
     torch.cuda.synchronize()
-    _same(t.cpu().numpy(), want, "hr_denoise on the ctx stream")
+    same(t.cpu().numpy(), want, "hr_denoise on the ctx stream")
     s = torch.cuda.Stream()
     t2 = torch.zeros((H, W, 4), dtype=torch.float32, device="cuda:0")
-    eng.denoise_to_device(t2.data_ptr(), _params(kernel=PLAIN), stream=s.cuda_stream)
+    eng.denoise_to_device(t2.data_ptr(), denoise_params(kernel=PLAIN), stream=s.cuda_stream)
     s.synchronize()
-    _same(t2.cpu().numpy(), want, "hr_denoise on a foreign stream")
+    same(t2.cpu().numpy(), want, "hr_denoise on a foreign stream")
     # the display resolve of the denoised image = the oracle's display resolve of the denoised read-back
     ora = oracle_lib.engine()
     ora.resize(W, H)
@@ -166,7 +137,7 @@ def test_device_output_on_a_foreign_stream_and_display():
         ref = ora.display(dp, fmt)
         got = out.cpu().numpy()
         assert got.dtype == ref.dtype
-        _same(got.view(np.uint8).reshape(H, W, -1), ref.view(np.uint8).reshape(H, W, -1), f"display format {fmt}")
+        same(got.view(np.uint8).reshape(H, W, -1), ref.view(np.uint8).reshape(H, W, -1), f"display format {fmt}")
     with pytest.raises(ffi.EngineError, match="display format"):
         eng.denoise_display(t.data_ptr(), dp, ffi.HR_DISPLAY_RGBA8 | ffi.HR_DISPLAY_PROGRESSIVE)
     ora.close()
@@ -175,41 +146,41 @@ def test_device_output_on_a_foreign_stream_and_display():
 
 def test_denoising_changes_neither_the_frame_nor_the_planes_nor_later_passes():
     sc = SCENES["multi_material"]()
-    eng = _engine(sc, range(4))
+    eng = engine_with_passes(sc, range(4))
     frame, planes = eng.readback(), eng.aovs()
     eng.denoise()
-    eng.denoise(_params(kernel=PLAIN))
-    _same(eng.readback(), frame, "frame after denoise")
+    eng.denoise(denoise_params(kernel=PLAIN))
+    same(eng.readback(), frame, "frame after denoise")
     after = eng.aovs()
     for name in ("albedo", "normal_depth", "moments"):
-        _same(after[name], planes[name], f"{name} after denoise")
-    _render(eng, sc, range(4, 8))
-    plain = _engine(SCENES["multi_material"](), range(8), mask=0)
-    _same(eng.readback(), plain.readback(), "4 more passes after a denoise")
+        same(after[name], planes[name], f"{name} after denoise")
+    render_passes(eng, sc, range(4, 8))
+    plain = engine_with_passes(SCENES["multi_material"](), range(8), mask=0)
+    same(eng.readback(), plain.readback(), "4 more passes after a denoise")
     plain.close()
     eng.close()
 
 
 def test_group_of_three_gives_the_plain_contexts_image():
     mk = lambda: scenes.multi_material(100, 70, bounces=3, textured=True)
-    eng = _engine(mk(), range(5))
+    eng = engine_with_passes(mk(), range(5))
     want = eng.denoise()
-    _same(want, denoise.reference(eng.readback(), eng.aovs()), "plain 100 x 70")
+    same(want, denoise.reference(eng.readback(), eng.aovs()), "plain 100 x 70")
     eng.close()
     grp = core.create_group([0, 0, 0], tile_size=16)
     sc = mk()
     sc.apply(grp)
     grp.set_aovs(BOTH)
-    _render(grp, sc, range(5))
+    render_passes(grp, sc, range(5))
     got, n = grp.denoise(with_passes=True)
     assert n == 5
-    _same(got, want, "group of three")
+    same(got, want, "group of three")
     import torch
     t = torch.zeros((70, 100, 4), dtype=torch.float32, device="cuda:0")
     grp.denoise_to_device(t.data_ptr())
     grp.synchronize()
     torch.cuda.synchronize()
-    _same(t.cpu().numpy(), want, "group: device output")
+    same(t.cpu().numpy(), want, "group: device output")
     grp.close()
 
 
@@ -220,49 +191,42 @@ def test_errors_and_life_cycle():
         eng = core.create_engine(rank=rank, world=3, tile_size=16)
         sc.apply(eng)
         eng.set_aovs(BOTH)
-        _render(eng, sc, range(2))
+        render_passes(eng, sc, range(2))
         with pytest.raises(ffi.EngineError, match="tile-sharded.*world > 1"):
             eng.denoise()
         eng.close()
     eng = core.create_engine()
     sc.apply(eng)
-    _render(eng, sc, range(2))
+    render_passes(eng, sc, range(2))
     with pytest.raises(ffi.EngineError, match="hr_aov_enable"):      # AOVs off
         eng.denoise()
     for mask in (ffi.HR_AOV_SURFACE, ffi.HR_AOV_MOMENTS):            # only one mask on
         eng.clear()
         eng.set_aovs(mask)
-        _render(eng, sc, range(2))
+        render_passes(eng, sc, range(2))
         with pytest.raises(ffi.EngineError, match="hr_aov_enable"):
             eng.denoise()
     eng.set_aovs(0)
     eng.clear()
-    _render(eng, sc, range(2))
+    render_passes(eng, sc, range(2))
     eng.set_aovs(BOTH)                                               # enabled after the first pass
-    _render(eng, sc, range(2, 4))
+    render_passes(eng, sc, range(2, 4))
     with pytest.raises(ffi.EngineError, match="hr_clear.*hr_aov_enable|hr_aov_enable.*hr_clear"):
         eng.denoise()
     eng.clear()                                                      # ... and after hr_clear it works
-    _render(eng, sc, range(3))
-    _same(eng.denoise(), denoise.reference(eng.readback(), eng.aovs()), "after clear")
+    render_passes(eng, sc, range(3))
+    same(eng.denoise(), denoise.reference(eng.readback(), eng.aovs()), "after clear")
     for kw, text in ((dict(iterations=9), "iterations"), (dict(iterations=-1), "iterations"), (dict(sigma_l=float("nan")), "sigma_l"),
                      (dict(sigma_l=-1.0), "sigma_l"), (dict(sigma_z=float("inf")), "sigma_z"), (dict(sigma_z=-0.5), "sigma_z"),
                      (dict(normal_power=17), "normal_power"), (dict(kernel=3), "kernel")):
         with pytest.raises(ffi.EngineError, match=text):
-            eng.denoise(_params(**kw))
+            eng.denoise(denoise_params(**kw))
     eng.resize(50, 30)                                               # a resize frees the working planes: the next call has its own
-    _render(eng, sc, range(3))
+    render_passes(eng, sc, range(3))
     got = eng.denoise()
     assert got.shape == (30, 50, 4)
-    _same(got, denoise.reference(eng.readback(), eng.aovs()), "after resize")
+    same(got, denoise.reference(eng.readback(), eng.aovs()), "after resize")
     eng.close()
-
-
-def _truth(mk):
-    eng = _engine(mk(), range(64, 64 + 1024), mask=0)
-    f = eng.readback()
-    eng.close()
-    return f[..., :3] / f[..., 3:4]
 
 
 QUALITY = {
@@ -280,14 +244,14 @@ def test_quality_against_the_renderer_itself(name):
     plain frame at 2 N.  Asserted for cornell at 4 and 16 and multi_material at 4; multi_material at 16 and the soup are printed
     (DESIGN.md records them)."""
     mk, asserted, reported = QUALITY[name]
-    ref = _truth(mk)
+    ref = truth(mk)
     for N in sorted(asserted + reported):
-        eng = _engine(mk(), range(N))
+        eng = engine_with_passes(mk(), range(N))
         frame = eng.readback()
         den = eng.denoise()
-        _render(eng, mk(), range(N, 2 * N))
+        render_passes(eng, mk(), range(N, 2 * N))
         f2 = eng.readback()
-        _render(eng, mk(), range(2 * N, 4 * N))
+        render_passes(eng, mk(), range(2 * N, 4 * N))
         f4 = eng.readback()
         eng.close()
         e = [denoise.relative_mse(f[..., :3] / f[..., 3:4], ref) for f in (frame, f2, f4)]

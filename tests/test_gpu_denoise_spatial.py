@@ -7,26 +7,18 @@ Which case reaches which path of k_spatial_variance: after one pass every workgr
 edges; 48 x 32: exact tiles); after `below` passes every workgroup takes the early out; the mixed-count frame has both kinds and
 workgroups with spatial and plain pixels side by side."""
 import ctypes as C
-import math
 
 import numpy as np
 import pytest
 
 import oracle_lib
+from device_support import BOTH, denoise_params, engine_with_passes, orbit, render_passes, same, truth
 from heatray_amd import _ffi as ffi
 from heatray_amd import core, denoise, denoise_spatial, history, scenes
 
 pytestmark = pytest.mark.gpu
-F = np.float32
-BOTH = ffi.HR_AOV_SURFACE | ffi.HR_AOV_MOMENTS
 AUTO, PLAIN, TILED = ffi.HR_DENOISE_KERNEL_AUTO, ffi.HR_DENOISE_KERNEL_PLAIN, ffi.HR_DENOISE_KERNEL_TILED
 NONE = {"spatial_pixels": 0, "estimated_pixels": 0, "starved_pixels": 0}
-
-
-def _params(iterations=5, kernel=AUTO, normal_power=7, sigma_l=4.0, sigma_z=4.0):
-    p = denoise.default_params()
-    p.iterations, p.kernel, p.normal_power, p.sigma_l, p.sigma_z = iterations, kernel, normal_power, sigma_l, sigma_z
-    return p
 
 
 def _spatial(below=4, min_taps=6):
@@ -35,42 +27,20 @@ def _spatial(below=4, min_taps=6):
     return s
 
 
-def _render(eng, sc, passes):
-    for s in passes:
-        eng.render_pass(sc.options.pass_params(s))
-
-
-def _engine(sc, passes, mask=BOTH):
-    eng = core.create_engine()
-    sc.apply(eng)
-    if mask:
-        eng.set_aovs(mask)
-    _render(eng, sc, passes)
-    return eng
-
-
-def _same(a, b, what):
-    assert a.shape == b.shape, what
-    if a.tobytes() != b.tobytes():
-        bad = (a.view(np.uint32) != b.view(np.uint32)).reshape(a.shape[0], a.shape[1], -1).any(axis=-1)
-        ys, xs = np.nonzero(bad)
-        raise AssertionError(f"{what}: {int(bad.sum())} pixels differ, first at (x={xs[0]}, y={ys[0]}): {a[ys[0], xs[0]]} vs {b[ys[0], xs[0]]}")
-
-
 def _check(eng, what, iterations=(0, 5), spatial=None):
     """device == reference for the frame the engine holds: variance plane, counters, and the image with both a-trous kernels"""
     frame, planes = eng.readback(), eng.aovs()
     want_v, want_r = denoise_spatial.variance(frame, planes, None, spatial, with_result=True)
     got_v, got_r = eng.denoise_spatial_variance(None, spatial, with_result=True)
     assert got_r == want_r, (what, got_r, want_r)
-    _same(got_v[..., None], want_v[..., None], f"{what}: variance plane")
+    same(got_v[..., None], want_v[..., None], f"{what}: variance plane")
     for it in iterations:
-        want = denoise_spatial.reference(frame, planes, _params(it), spatial)
+        want = denoise_spatial.reference(frame, planes, denoise_params(it), spatial)
         assert np.isfinite(want).all()
         for kernel in (PLAIN, TILED):
-            got, r = eng.denoise_spatial(_params(it, kernel), spatial, with_result=True)
+            got, r = eng.denoise_spatial(denoise_params(it, kernel), spatial, with_result=True)
             assert r == want_r, (what, it, kernel, r, want_r)
-            _same(got, want, f"{what}: {it} iterations, kernel {kernel}")
+            same(got, want, f"{what}: {it} iterations, kernel {kernel}")
     return frame, planes, want_r
 
 
@@ -86,33 +56,33 @@ SCENES = {
 @pytest.mark.parametrize("name", sorted(SCENES))
 def test_device_equals_reference(name):
     mk, n = SCENES[name]
-    eng = _engine(mk(), range(n))
+    eng = engine_with_passes(mk(), range(n))
     frame, _, res = _check(eng, name)
     assert res["spatial_pixels"] == frame.shape[0] * frame.shape[1] and res["estimated_pixels"] > 0
-    _same(eng.denoise_spatial(), denoise_spatial.reference(frame, eng.aovs()), f"{name}, NULL params")
+    same(eng.denoise_spatial(), denoise_spatial.reference(frame, eng.aovs()), f"{name}, NULL params")
     eng.close()
 
 
 def test_no_spatial_pixel_is_the_plain_denoiser():
-    eng = _engine(SCENES["odd_size_1"][0](), range(4))
+    eng = engine_with_passes(SCENES["odd_size_1"][0](), range(4))
     want = eng.denoise()
     got, res = eng.denoise_spatial(with_result=True)
     assert res == NONE
-    _same(got, want, "4 passes, defaults: the early-out path")
+    same(got, want, "4 passes, defaults: the early-out path")
     for it in (0, 1, 2):
-        _same(eng.denoise_spatial(_params(it)), eng.denoise(_params(it)), f"early out, {it} iterations")
+        same(eng.denoise_spatial(denoise_params(it)), eng.denoise(denoise_params(it)), f"early out, {it} iterations")
     frame, planes = eng.readback(), eng.aovs()
-    _same(eng.denoise_spatial_variance()[..., None], denoise.prepare(frame, planes["albedo"], planes["normal_depth"], planes["moments"])[0][..., 3:4], "prepared variance")
+    same(eng.denoise_spatial_variance()[..., None], denoise.prepare(frame, planes["albedo"], planes["normal_depth"], planes["moments"])[0][..., 3:4], "prepared variance")
     eng.close()
 
 
 def test_mixed_sample_counts():
     sc = scenes.multi_material(96, 64, bounces=3, textured=True)
-    eng = _engine(sc, range(1))
+    eng = engine_with_passes(sc, range(1))
     mask = np.ones((64, 96), np.uint8)
     mask[13:43, 21:61] = 0  # (30 x 40: no multiple of the tile, no tile boundary on its edges)
     eng.set_sample_mask(mask)
-    _render(eng, sc, range(1, 16))
+    render_passes(eng, sc, range(1, 16))
     frame, _, res = _check(eng, "mixed counts", iterations=(5,))
     n = frame[..., 3]
     assert (n[mask == 0] == 1).all() and (n[mask == 1] == 16).all()
@@ -139,15 +109,15 @@ def test_interactive_mode():
 
 
 def test_non_default_parameters():
-    eng = _engine(SCENES["cornell"][0](), range(2))
+    eng = engine_with_passes(SCENES["cornell"][0](), range(2))
     frame, planes = eng.readback(), eng.aovs()
     outs = []
-    for p, s in ((_params(sigma_z=0.0, normal_power=0), _spatial(2, 2)), (_params(3, sigma_l=1.5, sigma_z=0.5, normal_power=16), _spatial(64, 49)),
-                 (_params(), _spatial(3, 20))):
+    for p, s in ((denoise_params(sigma_z=0.0, normal_power=0), _spatial(2, 2)), (denoise_params(3, sigma_l=1.5, sigma_z=0.5, normal_power=16), _spatial(64, 49)),
+                 (denoise_params(), _spatial(3, 20))):
         want, wr = denoise_spatial.reference(frame, planes, p, s, with_result=True)
         got, r = eng.denoise_spatial(p, s, with_result=True)
         assert r == wr
-        _same(got, want, f"below {s.below}, min_taps {s.min_taps}")
+        same(got, want, f"below {s.below}, min_taps {s.min_taps}")
         outs.append((want, wr))
     assert outs[0][1] == NONE  # (two passes, below = 2)
     assert outs[1][1]["spatial_pixels"] == 128 * 128
@@ -156,19 +126,19 @@ def test_non_default_parameters():
 
 def test_device_output_on_a_foreign_stream_and_display():
     import torch
-    eng = _engine(SCENES["odd_size_1"][0](), range(1))
+    eng = engine_with_passes(SCENES["odd_size_1"][0](), range(1))
     want = eng.denoise_spatial()
     H, W = want.shape[:2]
     t = torch.zeros((H, W, 4), dtype=torch.float32, device="cuda:0")
     eng.denoise_spatial_to_device(t.data_ptr())  # the ctx stream
     eng.synchronize()
     torch.cuda.synchronize()
-    _same(t.cpu().numpy(), want, "hr_denoise_spatial on the ctx stream")
+    same(t.cpu().numpy(), want, "hr_denoise_spatial on the ctx stream")
     s = torch.cuda.Stream()
     t2 = torch.zeros((H, W, 4), dtype=torch.float32, device="cuda:0")
-    eng.denoise_spatial_to_device(t2.data_ptr(), _params(kernel=PLAIN), stream=s.cuda_stream)
+    eng.denoise_spatial_to_device(t2.data_ptr(), denoise_params(kernel=PLAIN), stream=s.cuda_stream)
     s.synchronize()
-    _same(t2.cpu().numpy(), want, "hr_denoise_spatial on a foreign stream")
+    same(t2.cpu().numpy(), want, "hr_denoise_spatial on a foreign stream")
     # the display resolve of the image = the oracle's display resolve of the read-back image
     ora = oracle_lib.engine()
     ora.resize(W, H)
@@ -186,7 +156,7 @@ def test_device_output_on_a_foreign_stream_and_display():
         ref = ora.display(dp, fmt)
         got = out.cpu().numpy()
         assert got.dtype == ref.dtype
-        _same(got.view(np.uint8).reshape(H, W, -1), ref.view(np.uint8).reshape(H, W, -1), f"display format {fmt}")
+        same(got.view(np.uint8).reshape(H, W, -1), ref.view(np.uint8).reshape(H, W, -1), f"display format {fmt}")
     with pytest.raises(ffi.EngineError, match="display format"):
         eng.denoise_spatial_display(t.data_ptr(), dp, ffi.HR_DISPLAY_RGBA8 | ffi.HR_DISPLAY_PROGRESSIVE)
     ora.close()
@@ -196,26 +166,26 @@ def test_device_output_on_a_foreign_stream_and_display():
 def test_it_changes_neither_the_frame_nor_the_planes_nor_later_passes():
     mk = SCENES["odd_size_1"][0]
     sc = mk()
-    eng = _engine(sc, range(1))
+    eng = engine_with_passes(sc, range(1))
     frame, planes = eng.readback(), eng.aovs()
     eng.denoise_spatial()
     eng.denoise_spatial_variance()
-    eng.denoise_spatial(_params(kernel=PLAIN))
-    _same(eng.readback(), frame, "frame after denoise_spatial")
+    eng.denoise_spatial(denoise_params(kernel=PLAIN))
+    same(eng.readback(), frame, "frame after denoise_spatial")
     after = eng.aovs()
     for name in ("albedo", "normal_depth", "moments"):
-        _same(after[name], planes[name], f"{name} after denoise_spatial")
-    _same(eng.denoise(), denoise.reference(frame, planes), "hr_denoise after hr_denoise_spatial")
-    _render(eng, sc, range(1, 5))
-    plain = _engine(mk(), range(5), mask=0)
-    _same(eng.readback(), plain.readback(), "4 more passes after a denoise_spatial")
+        same(after[name], planes[name], f"{name} after denoise_spatial")
+    same(eng.denoise(), denoise.reference(frame, planes), "hr_denoise after hr_denoise_spatial")
+    render_passes(eng, sc, range(1, 5))
+    plain = engine_with_passes(mk(), range(5), mask=0)
+    same(eng.readback(), plain.readback(), "4 more passes after a denoise_spatial")
     plain.close()
     eng.close()
 
 
 def test_group_of_three_gives_the_plain_contexts_image():
     mk = lambda: scenes.multi_material(100, 70, bounces=3, textured=True)
-    eng = _engine(mk(), range(1))
+    eng = engine_with_passes(mk(), range(1))
     want, wr = eng.denoise_spatial(with_result=True)
     wv = eng.denoise_spatial_variance()
     eng.close()
@@ -223,17 +193,17 @@ def test_group_of_three_gives_the_plain_contexts_image():
     sc = mk()
     sc.apply(grp)
     grp.set_aovs(BOTH)
-    _render(grp, sc, range(1))
+    render_passes(grp, sc, range(1))
     got, r = grp.denoise_spatial(with_result=True)
     assert r == wr and r["spatial_pixels"] == 100 * 70
-    _same(got, want, "group of three")
-    _same(grp.denoise_spatial_variance()[..., None], wv[..., None], "group of three: variance plane")
+    same(got, want, "group of three")
+    same(grp.denoise_spatial_variance()[..., None], wv[..., None], "group of three: variance plane")
     import torch
     t = torch.zeros((70, 100, 4), dtype=torch.float32, device="cuda:0")
     grp.denoise_spatial_to_device(t.data_ptr())
     grp.synchronize()
     torch.cuda.synchronize()
-    _same(t.cpu().numpy(), want, "group: device output")
+    same(t.cpu().numpy(), want, "group: device output")
     grp.close()
 
 
@@ -243,32 +213,32 @@ def test_errors_and_life_cycle():
     eng = core.create_engine(rank=1, world=3, tile_size=16)
     sc.apply(eng)
     eng.set_aovs(BOTH)
-    _render(eng, sc, range(1))
+    render_passes(eng, sc, range(1))
     for call in (eng.denoise_spatial, eng.denoise_spatial_variance):
         with pytest.raises(ffi.EngineError, match="tile-sharded.*world > 1"):
             call()
     eng.close()
     eng = core.create_engine()
     sc.apply(eng)
-    _render(eng, sc, range(1))
+    render_passes(eng, sc, range(1))
     with pytest.raises(ffi.EngineError, match="hr_aov_enable"):      # AOVs off
         eng.denoise_spatial()
     for mask in (ffi.HR_AOV_SURFACE, ffi.HR_AOV_MOMENTS):            # only one mask on
         eng.clear()
         eng.set_aovs(mask)
-        _render(eng, sc, range(1))
+        render_passes(eng, sc, range(1))
         with pytest.raises(ffi.EngineError, match="hr_aov_enable"):
             eng.denoise_spatial()
     eng.set_aovs(0)
     eng.clear()
-    _render(eng, sc, range(1))
+    render_passes(eng, sc, range(1))
     eng.set_aovs(BOTH)                                               # enabled after the first pass
-    _render(eng, sc, range(1, 2))
+    render_passes(eng, sc, range(1, 2))
     with pytest.raises(ffi.EngineError, match="hr_clear.*hr_aov_enable|hr_aov_enable.*hr_clear"):
         eng.denoise_spatial()
     eng.clear()                                                      # ... and after hr_clear it works
-    _render(eng, sc, range(1))
-    _same(eng.denoise_spatial(), denoise_spatial.reference(eng.readback(), eng.aovs()), "after clear")
+    render_passes(eng, sc, range(1))
+    same(eng.denoise_spatial(), denoise_spatial.reference(eng.readback(), eng.aovs()), "after clear")
     for kw, text in ((dict(below=1), "below"), (dict(below=65), "below"), (dict(min_taps=1), "min_taps"), (dict(min_taps=50), "min_taps")):
         for call in (eng.denoise_spatial, eng.denoise_spatial_variance):
             with pytest.raises(ffi.EngineError, match=text):
@@ -280,20 +250,13 @@ def test_errors_and_life_cycle():
     for kw, text in ((dict(iterations=9), "iterations"), (dict(sigma_l=float("nan")), "sigma_l"), (dict(sigma_z=-0.5), "sigma_z"), (dict(normal_power=17), "normal_power"),
                      (dict(kernel=3), "kernel")):                    # what hr_denoise refuses
         with pytest.raises(ffi.EngineError, match=text):
-            eng.denoise_spatial(_params(**kw))
+            eng.denoise_spatial(denoise_params(**kw))
     eng.resize(50, 30)                                               # a resize frees the working planes and the counters: the next call has its own
-    _render(eng, sc, range(1))
+    render_passes(eng, sc, range(1))
     got, r = eng.denoise_spatial(with_result=True)
     assert got.shape == (30, 50, 4) and r["spatial_pixels"] == 50 * 30
-    _same(got, denoise_spatial.reference(eng.readback(), eng.aovs()), "after resize")
+    same(got, denoise_spatial.reference(eng.readback(), eng.aovs()), "after resize")
     eng.close()
-
-
-def _truth(mk, passes=range(64, 64 + 1024)):
-    eng = _engine(mk(), passes, mask=0)
-    f = eng.readback()
-    eng.close()
-    return f[..., :3] / f[..., 3:4]
 
 
 BUYS = {
@@ -305,36 +268,18 @@ BUYS = {
 }
 
 
-def _rot_y(a):
-    c, s = math.cos(a), math.sin(a)
-    return np.array([[c, 0, s, 0], [0, 1, 0, 0], [-s, 0, c, 0], [0, 0, 0, 1.0]])
-
-
-def _shift(v):
-    m = np.eye(4)
-    m[:3, 3] = v
-    return m
-
-
-def _orbit(options, dphi):
-    """the view matrix after an orbit by dphi about the world's y axis through the focus point"""
-    v = np.asarray(options.view_matrix, np.float64)
-    target = v[:3, 3] - v[:3, 2] * options.focus_distance
-    return (_shift(target) @ _rot_y(dphi) @ _shift(-target) @ v).astype(F)
-
-
 @pytest.mark.parametrize("name", sorted(BUYS))
 def test_what_it_buys(name):
     """err = denoise.relative_mse against passes 64 .. 1087 of the same scene.  Asserted for cornell and multi_material: denoise_spatial at
     N = 1 beats the plain frame at 2 passes (the bar the plain denoiser is held to from N = 4 on).  N = 2, N = 3, the factors and the soup
     are printed (lines starting SPATIAL_BUYS; DESIGN.md records them)."""
     mk, asserted = BUYS[name]
-    ref = _truth(mk)
+    ref = truth(mk)
     for N in (1, 2, 3):
-        eng = _engine(mk(), range(N))
+        eng = engine_with_passes(mk(), range(N))
         frame = eng.readback()
         den, sp = eng.denoise(), eng.denoise_spatial()
-        _render(eng, mk(), range(N, 2 * N))
+        render_passes(eng, mk(), range(N, 2 * N))
         f2 = eng.readback()
         eng.close()
         e1, e2 = (denoise.relative_mse(f[..., :3] / f[..., 3:4], ref) for f in (frame, f2))
@@ -351,15 +296,15 @@ def test_what_it_buys_in_a_disocclusion():
     camera."""
     mk = BUYS["cornell"][0]
     sc = mk()
-    eng = _engine(sc, range(256))
-    new_view = _orbit(sc.options, 0.3)
+    eng = engine_with_passes(sc, range(256))
+    new_view = orbit(sc.options, 0.3)
     res = history.move_camera(eng, sc.options, new_view, 1)
     frame = eng.readback()
     rejected = frame[..., 3] == 1
     assert res["rejected_pixels"] > 0 and 0 < rejected.sum() < rejected.size
     den = eng.denoise()
     sp, r = eng.denoise_spatial(with_result=True)
-    _same(sp, denoise_spatial.reference(frame, eng.aovs()), "after a history merge")
+    same(sp, denoise_spatial.reference(frame, eng.aovs()), "after a history merge")
     assert r["spatial_pixels"] >= int(rejected.sum())
     eng.close()
 
@@ -367,7 +312,7 @@ def test_what_it_buys_in_a_disocclusion():
         s = mk()
         s.options.view_matrix = new_view
         return s
-    ref = _truth(mk_new)
+    ref = truth(mk_new)
     sub = lambda img: denoise.relative_mse(img[rejected][None, :, :3], ref[rejected][None])
     inside = [sub(frame[..., :3] / frame[..., 3:4]), sub(den), sub(sp)]
     keep = ~rejected

@@ -10,6 +10,7 @@ import subprocess
 import numpy as np
 import pytest
 
+from device_support import same
 from heatray_amd import _ffi as ffi
 from heatray_amd import core, host, scenes, tiles
 
@@ -36,21 +37,13 @@ def _device_frame(eng):
     return out
 
 
-def _same(a, b, what):
-    assert a.shape == b.shape, what
-    if a.tobytes() != b.tobytes():
-        bad = (a != b).reshape(a.shape[0], a.shape[1], -1).any(axis=-1)
-        ys, xs = np.nonzero(bad)
-        raise AssertionError(f"{what}: {int(bad.sum())} pixels differ, first at (x={xs[0]}, y={ys[0]}): {a[ys[0], xs[0]]} vs {b[ys[0], xs[0]]}")
-
-
 def _compare_all(grp, plain, what):
-    _same(grp.readback(), plain.readback(), what + ": readback")
+    same(grp.readback(), plain.readback(), what + ": readback")
     for fmt in (ffi.HR_DISPLAY_RGBA8, ffi.HR_DISPLAY_HDR_RGBA32F):
         (gi, gn), (pi, pn) = grp.display(fmt=fmt, with_passes=True), plain.display(fmt=fmt, with_passes=True)
-        _same(gi, pi, f"{what}: display format {fmt}")
+        same(gi, pi, f"{what}: display format {fmt}")
         assert gn == pn, (what, gn, pn)
-    _same(_device_frame(grp), _device_frame(plain), what + ": frame_device_ptr")
+    same(_device_frame(grp), _device_frame(plain), what + ": frame_device_ptr")
     gs, ps = grp.stats(), plain.stats()
     assert (gs.paths, gs.rays_closest, gs.rays_any, gs.shaded_hits) == (ps.paths, ps.rays_closest, ps.rays_any, ps.shaded_hits), what
     assert grp.passes_resolved() == plain.passes_resolved(), what
@@ -138,10 +131,10 @@ def test_group_progressive_readback():
     snap, shown = grp.readback_progressive()
     full = grp.readback()
     assert shown == posted and (full[..., 3] == posted).all()
-    _same(snap, full, "progressive snapshot after flush")
+    same(snap, full, "progressive snapshot after flush")
     img, shown = grp.display(fmt=ffi.HR_DISPLAY_RGBA8 | ffi.HR_DISPLAY_PROGRESSIVE, with_passes=True)
     assert shown == posted
-    _same(img, grp.display(fmt=ffi.HR_DISPLAY_RGBA8), "progressive display after flush")
+    same(img, grp.display(fmt=ffi.HR_DISPLAY_RGBA8), "progressive display after flush")
 
 
 def test_group_tree_cache(tmp_path):
@@ -160,8 +153,8 @@ def test_group_tree_cache(tmp_path):
     for e in (first, second, plain):
         _render(e, sc, 0, 2)
     ref = plain.readback()
-    _same(first.readback(), ref, "first cached group")
-    _same(second.readback(), ref, "second cached group")
+    same(first.readback(), ref, "first cached group")
+    same(second.readback(), ref, "second cached group")
 
 
 def test_group_unsupported_calls_and_bad_creation():
@@ -242,4 +235,4 @@ def test_cpp_layer_with_heatray_devices(tmp_path):
     assert "context group" not in outs["plain"][0]
     assert "PassGenerator: context group of 3 members on devices 0,0,0" in outs["group"][0]
     assert (outs["plain"][1][..., 3] == passes).all()
-    _same(outs["group"][1], outs["plain"][1], "C++ layer, HEATRAY_DEVICES=0,0,0")
+    same(outs["group"][1], outs["plain"][1], "C++ layer, HEATRAY_DEVICES=0,0,0")

@@ -7,78 +7,14 @@
 3. the history's life (survives hr_clear; gone after hr_frame_resize and hr_history_drop) and every refusal
 4. the denoiser and the adaptive update on a merged frame
 5. what it buys: the error against 2048 passes at the new camera, with and without history."""
-import math
-
 import numpy as np
 import pytest
 
-import oracle_lib
+from device_support import BOTH, F, device_engine, dolly, host_tables, orbit, render, same
 from heatray_amd import _ffi as ffi
 from heatray_amd import adaptive, core, denoise, history, host, scenes
 
 pytestmark = pytest.mark.gpu
-F = np.float32
-BOTH = ffi.HR_AOV_SURFACE | ffi.HR_AOV_MOMENTS
-
-_TABLE_CACHE = {}
-
-
-def host_tables(sc):
-    """Sample tables made once on the host by the oracle's generators (as tests/test_gpu_adaptive.py does)."""
-    key = (sc.options.sample_mode, sc.options.bokeh_shape, sc.options.max_render_passes, sc.width, sc.height)
-    if key not in _TABLE_CACHE:
-        o = oracle_lib.engine()
-        P = sc.options.max_render_passes
-        seq = np.stack([o.qmc_generate(sc.options.sample_mode, s, P) for s in range(16)])
-        ap = np.stack([o.qmc_generate(ffi.HR_SAMPLE_SOBOL, s, P, radial=True) for s in range(16)])
-        off = o.qmc_generate(ffi.HR_SAMPLE_SOBOL, 0, sc.width * sc.height)
-        o.close()
-        _TABLE_CACHE[key] = (seq, ap, off)
-    return _TABLE_CACHE[key]
-
-
-def _same(a, b, what):
-    a, b = np.ascontiguousarray(a), np.ascontiguousarray(b)
-    assert a.shape == b.shape and a.dtype == b.dtype, (what, a.shape, b.shape, a.dtype, b.dtype)
-    if a.tobytes() != b.tobytes():
-        ua = a.view(np.uint32) if a.dtype == F else a
-        ub = b.view(np.uint32) if b.dtype == F else b
-        bad = (ua != ub).reshape(a.shape[0], a.shape[1], -1).any(axis=-1)
-        ys, xs = np.nonzero(bad)
-        raise AssertionError(f"{what}: {int(bad.sum())} pixels differ, first at (x={xs[0]}, y={ys[0]}): {a[ys[0], xs[0]]} vs {b[ys[0], xs[0]]}")
-
-
-def device_engine(sc, golden, aovs=BOTH, **kw):
-    eng = core.create_engine(**kw)
-    sc.apply(eng, lut=golden["multiscatter_lut"], tables=host_tables(sc))
-    if aovs:
-        eng.set_aovs(aovs)
-    return eng
-
-
-def _rot_y(a):
-    c, s = math.cos(a), math.sin(a)
-    return np.array([[c, 0, s, 0], [0, 1, 0, 0], [-s, 0, c, 0], [0, 0, 0, 1.0]])
-
-
-def _shift(v):
-    m = np.eye(4)
-    m[:3, 3] = v
-    return m
-
-
-def orbit(options, dphi):
-    """the view matrix after an orbit by dphi about the world's y axis through the focus point"""
-    v = np.asarray(options.view_matrix, np.float64)
-    target = v[:3, 3] - v[:3, 2] * options.focus_distance
-    return (_shift(target) @ _rot_y(dphi) @ _shift(-target) @ v).astype(F)
-
-
-def dolly(options, share):
-    v = np.asarray(options.view_matrix, np.float64)
-    return (_shift(-v[:3, 2] * options.focus_distance * share) @ v).astype(F)
-
-
 def move(options, how):
     """apply a camera change to a scene's options"""
     if how == "orbit_0.05":
@@ -102,11 +38,6 @@ SCENES = {
 MOVES = ["none", "orbit_0.05", "orbit_0.3", "dolly", "focal_length"]
 
 
-def render(eng, pps):
-    for pp in pps:
-        eng.render_pass(pp)
-
-
 def check_capture_and_merge(eng, sc, how, old_pps, new_pps_of, what, params=None):
     """render old_pps, capture, clear, change the camera, render new_pps_of(options), merge: everything against the reference.
     Returns (merged frame, merged planes, result, the frame before the merge)."""
@@ -117,15 +48,15 @@ def check_capture_and_merge(eng, sc, how, old_pps, new_pps_of, what, params=None
     hist = eng.history()
     want_hist = history.reference_capture(frame_a, planes_a)
     for k, name in enumerate(("H0", "H1", "H2")):
-        _same(hist[k], want_hist[k], f"{what}: history {name}")
-    _same(eng.readback(), frame_a, f"{what}: the frame after the capture")          # 2. capture writes nothing
+        same(hist[k], want_hist[k], f"{what}: history {name}")
+    same(eng.readback(), frame_a, f"{what}: the frame after the capture")          # 2. capture writes nothing
     after = eng.aovs()
     for k in history.PLANES:
-        _same(after[k], planes_a[k], f"{what}: {k} after the capture")
+        same(after[k], planes_a[k], f"{what}: {k} after the capture")
     assert eng.history_info() == (True, len(old_pps))
     eng.clear()
     assert eng.history_info() == (True, len(old_pps))                               # 3. the history survives hr_clear
-    _same(eng.history(), hist, f"{what}: the history after hr_clear")
+    same(eng.history(), hist, f"{what}: the history after hr_clear")
     move(sc.options, how)
     new_pps = new_pps_of(sc.options)
     render(eng, new_pps)
@@ -133,12 +64,12 @@ def check_capture_and_merge(eng, sc, how, old_pps, new_pps_of, what, params=None
     res = eng.history_merge(new_pps[0], params)
     frame_m, planes_m = eng.readback(), eng.aovs()
     want_frame, want_planes, want = history.reference_merge(want_hist, old_cam, frame_b, planes_b, new_pps[0], params)
-    _same(frame_m, want_frame, f"{what}: merged frame")
+    same(frame_m, want_frame, f"{what}: merged frame")
     for k in history.PLANES:
-        _same(planes_m[k], want_planes[k], f"{what}: merged {k}")
+        same(planes_m[k], want_planes[k], f"{what}: merged {k}")
     assert res == {"reused_pixels": want["reused_pixels"], "rejected_pixels": want["rejected_pixels"], "history_samples": want["history_samples"],
                    "history_passes": len(old_pps), "passes": len(new_pps)}, (what, res, {k: v for k, v in want.items() if k != "nh"})
-    _same(frame_m[..., 3], planes_m["moments"][..., 3], f"{what}: F.a against M.a")
+    same(frame_m[..., 3], planes_m["moments"][..., 3], f"{what}: F.a against M.a")
     assert (frame_m[..., 3] == np.floor(frame_m[..., 3])).all()
     return frame_m, planes_m, res, frame_b
 
@@ -288,13 +219,13 @@ def test_the_history_goes_with_resize_and_drop_and_every_refusal(golden):
                      (dict(min_weight=1.5), "min_weight"), (dict(min_weight=nan), "min_weight")):
         with pytest.raises(ffi.EngineError, match=text):
             eng.history_merge(pp(0), P(**kw))
-    _same(eng.readback(), frame, "the frame after the refused merges")
-    _same(eng.history(), hist, "the history after the refused merges")
+    same(eng.readback(), frame, "the frame after the refused merges")
+    same(eng.history(), hist, "the history after the refused merges")
     # a second capture replaces the first
     render(eng, [pp(k) for k in range(4, 6)])
     eng.history_capture(pp(0))
     assert eng.history_info() == (True, 6)
-    _same(eng.history(), history.reference_capture(eng.readback(), eng.aovs()), "the second capture")
+    same(eng.history(), history.reference_capture(eng.readback(), eng.aovs()), "the second capture")
     # merging into the frame it was captured from is allowed once (the same camera: the frame takes over its own samples) ...
     r = eng.history_merge(pp(0))
     assert r["reused_pixels"] > 0 and (r["history_passes"], r["passes"]) == (6, 6)
@@ -341,7 +272,7 @@ def test_the_denoiser_and_the_adaptive_update_on_a_merged_frame(golden):
     plain.render_pass(sc.options.pass_params(0))
     f1, p1 = plain.readback(), plain.aovs()
     d1 = plain.denoise()
-    _same(d1, denoise.reference(f1, p1), "denoise of one pass")
+    same(d1, denoise.reference(f1, p1), "denoise of one pass")
     share_plain = moved(d1, denoise.reference(f1, p1, own)).mean()
     plain.close()
     # with history
@@ -351,20 +282,20 @@ def test_the_denoiser_and_the_adaptive_update_on_a_merged_frame(golden):
     frame, planes = eng.readback(), eng.aovs()
     reused = frame[..., 3] > 1
     assert int(reused.sum()) == r["reused_pixels"]
-    _same(frame[~reused], f1[~reused], "pixels without history are the plain render's")
+    same(frame[~reused], f1[~reused], "pixels without history are the plain render's")
     want = denoise.reference(frame, planes)
     for kernel in (ffi.HR_DENOISE_KERNEL_PLAIN, ffi.HR_DENOISE_KERNEL_TILED):
         p = denoise.default_params()
         p.kernel = kernel
-        _same(eng.denoise(p), want, f"denoise of a merged frame, kernel {kernel}")
+        same(eng.denoise(p), want, f"denoise of a merged frame, kernel {kernel}")
     share_merged = moved(want, denoise.reference(frame, planes, own))[reused].mean()
     print(f"HISTORY_DENOISE share of pixels the filter moves by more than 1e-3: one pass without history {share_plain:.3f}, reused pixels with history {share_merged:.3f}")
     assert share_plain < 0.02 and share_merged > 0.5, (share_plain, share_merged)
     p = adaptive.default_params()
     res = eng.adaptive_update(p)
     err = adaptive.reference_error(frame, planes["moments"], p)
-    _same(eng.adaptive_error(), err, "adaptive error of a merged frame")
-    _same(eng.sample_mask()[0], adaptive.reference_mask(err, p), "mask of a merged frame")
+    same(eng.adaptive_error(), err, "adaptive error of a merged frame")
+    same(eng.sample_mask()[0], adaptive.reference_mask(err, p), "mask of a merged frame")
     w = adaptive.reference_result(err, p, passes=1)
     assert (res.unconverged_pixels, res.active_pixels, res.passes) == (w["unconverged_pixels"], w["active_pixels"], 1)
     assert np.isfinite(err[reused & (frame[..., 3] >= 16)]).all() and np.isposinf(err[~reused]).all()  # reused pixels have an estimate at the first pass

@@ -8,6 +8,7 @@ import numpy as np
 import pytest
 
 import oracle_lib
+from device_support import host_tables
 from heatray_amd import _ffi as ffi
 from heatray_amd import core, host, scenes
 
@@ -23,23 +24,6 @@ def rel_l2(a, b):
 @pytest.fixture(scope="module")
 def gpu():
     return core.create_engine()
-
-
-_TABLE_CACHE = {}
-
-
-def host_tables(sc):
-    """Sample tables generated ONCE on the host (by the oracle's generators, themselves pinned to the
-    reference's Random.h) and uploaded to both engines, as PassGenerator does with its uniform blocks."""
-    key = (sc.options.sample_mode, sc.options.bokeh_shape, sc.options.max_render_passes, sc.width, sc.height)
-    if key not in _TABLE_CACHE:
-        o = oracle_lib.engine()
-        P = sc.options.max_render_passes
-        seq = np.stack([o.qmc_generate(sc.options.sample_mode, s, P) for s in range(16)])
-        ap = np.stack([o.qmc_generate(ffi.HR_SAMPLE_SOBOL, s, P, radial=True) for s in range(16)])
-        off = o.qmc_generate(ffi.HR_SAMPLE_SOBOL, 0, sc.width * sc.height)
-        _TABLE_CACHE[key] = (seq, ap, off)
-    return _TABLE_CACHE[key]
 
 
 def render_both(sc, passes, lut=None, gpu_kw=None, ora_kw=None, device_tables=False):

@@ -2,46 +2,17 @@
 against its numpy restatement heatray_amd.history.reference_capture / reference_merge, bit for bit, every pixel, on synthetic frames,
 planes and cameras; and properties of the reference itself on constructed inputs whose answers are known (include/hrcore_history.h is
 the contract).  tests/test_gpu_history.py holds the device to the same reference."""
-import ctypes as C
 import math
-import os
-import subprocess
 
 import numpy as np
 import pytest
 
-from heatray_amd import _ffi as ffi
+import cpu_header
+import synthetic_frames
 from heatray_amd import history, scenes
+from synthetic_frames import F, camera, flat, merge_input, plane_view, rot_x, rot_y, same_bits, translate, uniform
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-F = np.float32
 U = 2.0 ** -24  # unit roundoff of binary32
-
-
-def camera(view=None, fov=0.24, aspect=None, W=1, H=1):
-    """A PassParams that holds a camera: view = camera -> world as m[row, col]"""
-    p = ffi.PassParams()
-    m = np.eye(4) if view is None else np.asarray(view, np.float64)
-    p.view_matrix = (C.c_float * 16)(*m.astype(F).T.reshape(-1))
-    p.fov_tan = fov
-    p.aspect_ratio = aspect if aspect is not None else W / H
-    return p
-
-
-def rot_y(a):
-    c, s = math.cos(a), math.sin(a)
-    return np.array([[c, 0, s, 0], [0, 1, 0, 0], [-s, 0, c, 0], [0, 0, 0, 1.0]])
-
-
-def rot_x(a):
-    c, s = math.cos(a), math.sin(a)
-    return np.array([[1, 0, 0, 0], [0, c, -s, 0], [0, s, c, 0], [0, 0, 0, 1.0]])
-
-
-def translate(x, y, z):
-    m = np.eye(4)
-    m[:3, 3] = (x, y, z)
-    return m
 
 
 def params(max_history=32, normal_cos=0.9, plane_tol=0.02, min_weight=0.25):
@@ -52,29 +23,11 @@ def params(max_history=32, normal_cos=0.9, plane_tol=0.02, min_weight=0.25):
 
 @pytest.fixture(scope="module")
 def cpu(tmp_path_factory):
-    d = tmp_path_factory.mktemp("history_cpu")
-    exe = d / "history_cpu"
-    # -ffp-contract=off like the library: the header's float lines must mean the same on both sides
-    subprocess.check_call(["g++", "-std=c++17", "-O1", "-ffp-contract=off", "-Wall", "-I" + os.path.join(ROOT, "heatray_amd", "csrc"),
-                           os.path.join(ROOT, "tests", "host", "history_cpu.cpp"), "-o", str(exe)])
-
-    def cam_floats(pp):
-        return np.array(list(pp.view_matrix) + [pp.aspect_ratio, pp.fov_tan], F)
+    exe = cpu_header.build("history", tmp_path_factory.mktemp("history_cpu"))
 
     def run(old, old_cam, new, new_cam, p):
         H, W = old[0].shape[:2]
-        with open(d / "in.bin", "wb") as f:
-            f.write(np.array([W, H, p.max_history, 0], np.int32).tobytes())
-            f.write(np.array([p.normal_cos, p.plane_tol, p.min_weight, 0], F).tobytes())
-            f.write(cam_floats(old_cam).tobytes())
-            f.write(cam_floats(new_cam).tobytes())
-            for frame, planes in (old, new):
-                f.write(np.ascontiguousarray(frame, F).tobytes())
-                for k in history.PLANES:
-                    f.write(np.ascontiguousarray(planes[k], F).tobytes())
-        out = subprocess.run([str(exe), str(d / "in.bin"), str(d / "out.bin")], capture_output=True, text=True)
-        assert out.returncode == 0 and "history cpu: ok" in out.stdout, (out.returncode, out.stderr)
-        raw = np.fromfile(d / "out.bin", np.uint8)
+        raw = np.frombuffer(cpu_header.run(exe, merge_input(old, old_cam, new, new_cam, p)), np.uint8)
         n = W * H * 16
         hist = raw[:3 * n].view(F).reshape(3, H, W, 4)
         planes = [raw[(3 + k) * n:(4 + k) * n].view(F).reshape(H, W, 4) for k in range(4)]
@@ -83,90 +36,28 @@ def cpu(tmp_path_factory):
     return run
 
 
-def _same_bits(got, want, what):
-    g, w = np.ascontiguousarray(got), np.ascontiguousarray(want)
-    assert g.shape == w.shape and g.dtype == w.dtype, what
-    if g.tobytes() != w.tobytes():
-        bad = np.argwhere(g.view(np.uint32) != w.view(np.uint32))
-        raise AssertionError(f"{what}: {len(bad)} values differ, first at {tuple(bad[0])}: {g[tuple(bad[0])]} against {w[tuple(bad[0])]}")
-
-
 def _check(cpu, old, old_cam, new, new_cam, p, what):
     """the CPU build of the header against the numpy reference, bit for bit; returns the reference's answer"""
     hist = history.reference_capture(*old)
     frame, planes, res = history.reference_merge(hist, old_cam, new[0], new[1], new_cam, p)
     chist, cframe, cplanes, cres = cpu(old, old_cam, new, new_cam, p)
-    _same_bits(chist, hist, what + ": history")
-    _same_bits(cframe, frame, what + ": frame")
+    same_bits(chist, hist, what + ": history")
+    same_bits(cframe, frame, what + ": frame")
     for k in history.PLANES:
-        _same_bits(cplanes[k], planes[k], f"{what}: {k}")
+        same_bits(cplanes[k], planes[k], f"{what}: {k}")
     assert cres == {k: res[k] for k in cres}, (what, cres, res)
     # what holds for every merge
-    _same_bits(frame[..., 3], planes["moments"][..., 3], what + ": F.a against M.a")
+    same_bits(frame[..., 3], planes["moments"][..., 3], what + ": F.a against M.a")
     assert (frame[..., 3] == np.floor(frame[..., 3])).all(), what
     empty = ~(new[0][..., 3] > 0)
-    _same_bits(frame[empty], new[0][empty], what + ": a pixel with n = 0 is untouched (frame)")
+    same_bits(frame[empty], new[0][empty], what + ": a pixel with n = 0 is untouched (frame)")
     for k in history.PLANES:
-        _same_bits(planes[k][empty], new[1][k][empty], f"{what}: a pixel with n = 0 is untouched ({k})")
+        same_bits(planes[k][empty], new[1][k][empty], f"{what}: a pixel with n = 0 is untouched ({k})")
     assert res["reused_pixels"] + res["rejected_pixels"] == int((new[0][..., 3] > 0).sum()), what
     return hist, frame, planes, res
 
 
-def _uniform(rng, shape):
-    """SplitMix64 content -> float32 in [0, 1)"""
-    n = int(np.prod(shape))
-    return ((rng.u64(n) >> np.uint64(40)).astype(np.float64) / float(1 << 24)).astype(F).reshape(shape)
-
-
-def plane_view(W, H, cam, seed, depth=6.0, max_n=40, holes=True, sky=True, noise=True):
-    """A frame and its planes as a renderer would leave them in front of the world plane z = -depth (normal 0 0 1), seen with `cam`:
-    per-pixel sample counts (some 0), coverage between 0 and 1 (sky patches, half-covered pixels), normals and depths disturbed at some
-    pixels (what the tap tests must reject), colours and moments from SplitMix64."""
-    rng = scenes.SplitMix64(seed)
-    v = np.array(list(cam.view_matrix), np.float64).reshape(4, 4).T
-    y, x = np.mgrid[0:H, 0:W]
-    cx = (2 * (x + 0.5) / W - 1) * cam.aspect_ratio * cam.fov_tan
-    cy = (2 * (y + 0.5) / H - 1) * cam.fov_tan
-    d = cx[..., None] * v[:3, 0] + cy[..., None] * v[:3, 1] - v[:3, 2]
-    with np.errstate(all="ignore"):
-        s = (-depth - v[2, 3]) / d[..., 2]
-    hit = np.isfinite(s) & (s > 0)
-    u = _uniform(rng, (8, H, W))
-    n = np.floor(u[0] * (max_n + 1)) if holes else np.full((H, W), float(max_n))
-    if holes:
-        n[u[1] < 0.05] = 0
-    cov = np.where(hit, 1.0, 0.0)
-    if sky:
-        blocks = _uniform(rng, ((H + 7) // 8, (W + 7) // 8))[y // 8, x // 8]
-        cov = np.where(blocks < 0.2, 0.0, cov)                         # sky patches
-        cov = np.where((u[2] < 0.1) & hit, np.round(u[3] * 4) / 4, cov)  # partly covered pixels: 0, 1/4 .. 1
-    hits = np.floor(n * cov)
-    normal = np.zeros((H, W, 3))
-    normal[..., 2] = 1.0
-    dep = np.where(hit, s, 0.0)
-    if noise:
-        turn = u[4] < 0.1
-        ang = u[5] * 1.2
-        normal[turn] = np.stack([np.sin(ang), np.zeros_like(ang), np.cos(ang)], -1)[turn]
-        dep = np.where(u[6] < 0.1, dep * (1 + 0.2 * (u[7] - 0.5)), dep)
-    col = _uniform(rng, (H, W, 3)) * F(1.5) + F(0.02)
-    frame, planes = np.zeros((H, W, 4), F), {k: np.zeros((H, W, 4), F) for k in history.PLANES}
-    frame[..., :3], frame[..., 3] = col * n[..., None], n
-    planes["moments"][..., :3], planes["moments"][..., 3] = (col * col * F(1.3)) * n[..., None], n
-    planes["albedo"][..., :3], planes["albedo"][..., 3] = _uniform(rng, (H, W, 3)) * hits[..., None], hits
-    planes["normal_depth"][..., :3], planes["normal_depth"][..., 3] = normal * hits[..., None], dep * hits
-    return frame, planes
-
-
-MOVES = {
-    "none": lambda: (np.eye(4), 0.24),
-    "yaw": lambda: (rot_y(0.05), 0.24),
-    "orbit": lambda: (translate(0, 0, -6) @ rot_y(0.3) @ translate(0, 0, 6), 0.24),
-    "pitch_shift": lambda: (translate(0.3, -0.2, 0.1) @ rot_x(-0.07), 0.24),
-    "dolly": lambda: (translate(0, 0, -0.6), 0.24),
-    "zoom": lambda: (np.eye(4), 0.31),
-    "behind": lambda: (rot_y(math.pi), 0.24),
-}
+MOVES = {**synthetic_frames.MOVES, "behind": lambda: (rot_y(math.pi), 0.24)}
 CASES = [(67, 41, "none", 1), (67, 41, "yaw", 2), (67, 41, "orbit", 3), (131, 19, "pitch_shift", 4), (5, 300, "dolly", 5), (64, 16, "zoom", 6),
          (1, 1, "none", 7), (33, 33, "behind", 8), (96, 54, "orbit", 9)]
 
@@ -208,18 +99,6 @@ def test_parameters_at_both_ends_of_their_ranges(cpu, p):
         assert res["reused_pixels"] >= ref["reused_pixels"]
     if p.normal_cos == 1.0 or p.plane_tol < 1e-3 or p.min_weight == 1.0:  # a tighter one never gains one
         assert res["reused_pixels"] <= ref["reused_pixels"]
-
-
-def flat(W, H, n, colour=(0.5, 0.25, 0.125), depth=6.0, cov=1.0, normal=(0.0, 0.0, 1.0)):
-    """n samples of one colour everywhere on a surface of one depth and normal (cov = 0: sky)"""
-    frame, planes = np.zeros((H, W, 4), F), {k: np.zeros((H, W, 4), F) for k in history.PLANES}
-    c = np.asarray(colour, F)
-    frame[..., :3], frame[..., 3] = c * F(n), n
-    planes["moments"][..., :3], planes["moments"][..., 3] = (c * c) * F(n), n
-    hits = F(n * cov)
-    planes["albedo"][..., :3], planes["albedo"][..., 3] = F(0.5) * hits, hits
-    planes["normal_depth"][..., :3], planes["normal_depth"][..., 3] = np.asarray(normal, F) * hits, F(depth) * hits
-    return frame, planes
 
 
 def test_a_constant_history_comes_back_as_that_constant(cpu):
@@ -270,7 +149,7 @@ def test_a_sideways_shift_by_whole_pixels_shifts_the_history(cpu):
     aspect = W / H
     step = 2 * aspect * fov * depth / W  # the width of a pixel on the plane
     old_cam, new_cam = camera(np.eye(4), fov, W=W, H=H), camera(translate(k * step, 0, 0), fov, W=W, H=H)
-    col = _uniform(scenes.SplitMix64(3), (W, 3))  # a colour per column
+    col = uniform(scenes.SplitMix64(3), (W, 3))  # a colour per column
     old = flat(W, H, 32)
     old[0][..., :3] = col[None] * F(32)
     new = flat(W, H, 1, colour=(0, 0, 0))
@@ -333,7 +212,7 @@ def test_behind_the_old_camera_and_outside_the_old_image(cpu, sky):
     for what, m in (("behind", rot_y(math.pi)), ("outside", rot_y(math.pi / 2)), ("outside, near", rot_y(1.2 * 2 * math.atan(0.24 * W / H)))):
         _, frame, _, res = _check(cpu, old, old_cam, new, camera(base @ m, 0.24, W=W, H=H), params(), what)
         assert res["reused_pixels"] == 0 and res["rejected_pixels"] == W * H, what
-        _same_bits(frame, new[0], what + ": nothing changed")
+        same_bits(frame, new[0], what + ": nothing changed")
 
 
 def test_default_params_are_the_documented_ones():

@@ -3,34 +3,11 @@ test_history_kernel_resources.py (no GPU needed: hipcc cross-compiles gfx950).  
 the waves per SIMD and the LDS are pinned at what the build gives (DESIGN.md has them): k_reproject_merge is k_history_merge with the
 examined word in front — its own pixel and the twelve gathered float4 of the four taps held at once, the same occupancy —;
 k_reproject_preview holds eight gathered float4 and stages the 36 x 12 guide records of its tile (a float4 and a class byte each) in LDS."""
-import os
-import re
-import subprocess
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(ROOT, "heatray_amd", "csrc")
-
-
-def _resources(src):
-    flags = subprocess.run(["make", "-s", "-C", CSRC, "print-flags"], capture_output=True, text=True, check=True).stdout.split()
-    out = subprocess.run(["/opt/rocm/bin/hipcc", *flags, "-c", os.path.join(CSRC, src), "-o", os.devnull, "-Rpass-analysis=kernel-resource-usage"],
-                         capture_output=True, text=True, cwd=CSRC)
-    assert out.returncode == 0, out.stderr[-2000:]
-    res, name = {}, None
-    for line in out.stderr.splitlines():
-        m = re.search(r"remark:\s+Function Name: (\S+)", line)
-        if m:
-            name = subprocess.run(["c++filt", m.group(1)], capture_output=True, text=True).stdout.strip()
-            res[name] = {}
-            continue
-        m = re.search(r"remark:\s+([A-Za-z ]+?)(?: \[[^\]]*\])?: (\d+)", line)
-        if m and name:
-            res[name][m.group(1).strip()] = int(m.group(2))
-    return res
+from kernel_resources import resources
 
 
 def test_reproject_kernels_use_no_scratch_and_keep_their_registers():
-    res = _resources("hr_reproject.hip")
+    res = resources("hr_reproject.hip")
     kernels = {k.split("(")[0].replace("void ", "").replace("hr::", ""): v for k, v in res.items() if "k_" in k}
     assert sorted(kernels) == ["k_reproject_merge", "k_reproject_preview"], sorted(kernels)
     for name, r in kernels.items():

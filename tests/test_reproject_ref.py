@@ -2,123 +2,14 @@
 (tests/host/reproject_cpu.cpp) against its numpy restatement heatray_amd.reproject.reference_merge_progressive / reference_preview, bit
 for bit, every pixel, on synthetic frames, planes and cameras; and properties of the reference itself on constructed inputs whose answers
 are known (include/hrcore_reproject.h is the contract).  tests/test_gpu_reproject.py holds the device to the same reference."""
-import ctypes as C
-import math
-import os
-import subprocess
-
 import numpy as np
 import pytest
 
-from heatray_amd import _ffi as ffi
+import cpu_header
 from heatray_amd import history, reproject, scenes
+from synthetic_frames import F, MOVES, camera, flat, merge_input, plane_view, rot_x, rot_y, same_bits, translate, uniform
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-F = np.float32
 U = 2.0 ** -24  # unit roundoff of binary32
-
-
-# ---- the small helpers of tests/test_history_ref.py
-def camera(view=None, fov=0.24, aspect=None, W=1, H=1):
-    """A PassParams that holds a camera: view = camera -> world as m[row, col]"""
-    p = ffi.PassParams()
-    m = np.eye(4) if view is None else np.asarray(view, np.float64)
-    p.view_matrix = (C.c_float * 16)(*m.astype(F).T.reshape(-1))
-    p.fov_tan = fov
-    p.aspect_ratio = aspect if aspect is not None else W / H
-    return p
-
-
-def rot_y(a):
-    c, s = math.cos(a), math.sin(a)
-    return np.array([[c, 0, s, 0], [0, 1, 0, 0], [-s, 0, c, 0], [0, 0, 0, 1.0]])
-
-
-def rot_x(a):
-    c, s = math.cos(a), math.sin(a)
-    return np.array([[1, 0, 0, 0], [0, c, -s, 0], [0, s, c, 0], [0, 0, 0, 1.0]])
-
-
-def translate(x, y, z):
-    m = np.eye(4)
-    m[:3, 3] = (x, y, z)
-    return m
-
-
-def _uniform(rng, shape):
-    """SplitMix64 content -> float32 in [0, 1)"""
-    n = int(np.prod(shape))
-    return ((rng.u64(n) >> np.uint64(40)).astype(np.float64) / float(1 << 24)).astype(F).reshape(shape)
-
-
-def plane_view(W, H, cam, seed, depth=6.0, max_n=40, holes=True, sky=True, noise=True):
-    """A frame and its planes as a renderer would leave them in front of the world plane z = -depth (normal 0 0 1), seen with `cam`:
-    per-pixel sample counts (some 0), coverage between 0 and 1 (sky patches, half-covered pixels), normals and depths disturbed at some
-    pixels (what the tap tests must reject), colours and moments from SplitMix64."""
-    rng = scenes.SplitMix64(seed)
-    v = np.array(list(cam.view_matrix), np.float64).reshape(4, 4).T
-    y, x = np.mgrid[0:H, 0:W]
-    cx = (2 * (x + 0.5) / W - 1) * cam.aspect_ratio * cam.fov_tan
-    cy = (2 * (y + 0.5) / H - 1) * cam.fov_tan
-    d = cx[..., None] * v[:3, 0] + cy[..., None] * v[:3, 1] - v[:3, 2]
-    with np.errstate(all="ignore"):
-        s = (-depth - v[2, 3]) / d[..., 2]
-    hit = np.isfinite(s) & (s > 0)
-    u = _uniform(rng, (8, H, W))
-    n = np.floor(u[0] * (max_n + 1)) if holes else np.full((H, W), float(max_n))
-    if holes:
-        n[u[1] < 0.05] = 0
-    cov = np.where(hit, 1.0, 0.0)
-    if sky:
-        blocks = _uniform(rng, ((H + 7) // 8, (W + 7) // 8))[y // 8, x // 8]
-        cov = np.where(blocks < 0.2, 0.0, cov)                         # sky patches
-        cov = np.where((u[2] < 0.1) & hit, np.round(u[3] * 4) / 4, cov)  # partly covered pixels: 0, 1/4 .. 1
-    hits = np.floor(n * cov)
-    normal = np.zeros((H, W, 3))
-    normal[..., 2] = 1.0
-    dep = np.where(hit, s, 0.0)
-    if noise:
-        turn = u[4] < 0.1
-        ang = u[5] * 1.2
-        normal[turn] = np.stack([np.sin(ang), np.zeros_like(ang), np.cos(ang)], -1)[turn]
-        dep = np.where(u[6] < 0.1, dep * (1 + 0.2 * (u[7] - 0.5)), dep)
-    col = _uniform(rng, (H, W, 3)) * F(1.5) + F(0.02)
-    frame, planes = np.zeros((H, W, 4), F), {k: np.zeros((H, W, 4), F) for k in history.PLANES}
-    frame[..., :3], frame[..., 3] = col * n[..., None], n
-    planes["moments"][..., :3], planes["moments"][..., 3] = (col * col * F(1.3)) * n[..., None], n
-    planes["albedo"][..., :3], planes["albedo"][..., 3] = _uniform(rng, (H, W, 3)) * hits[..., None], hits
-    planes["normal_depth"][..., :3], planes["normal_depth"][..., 3] = normal * hits[..., None], dep * hits
-    return frame, planes
-
-
-def flat(W, H, n, colour=(0.5, 0.25, 0.125), depth=6.0, cov=1.0, normal=(0.0, 0.0, 1.0)):
-    """n samples of one colour everywhere on a surface of one depth and normal (cov = 0: sky)"""
-    frame, planes = np.zeros((H, W, 4), F), {k: np.zeros((H, W, 4), F) for k in history.PLANES}
-    c = np.asarray(colour, F)
-    frame[..., :3], frame[..., 3] = c * F(n), n
-    planes["moments"][..., :3], planes["moments"][..., 3] = (c * c) * F(n), n
-    hits = F(n * cov)
-    planes["albedo"][..., :3], planes["albedo"][..., 3] = F(0.5) * hits, hits
-    planes["normal_depth"][..., :3], planes["normal_depth"][..., 3] = np.asarray(normal, F) * hits, F(depth) * hits
-    return frame, planes
-
-
-MOVES = {
-    "none": lambda: (np.eye(4), 0.24),
-    "yaw": lambda: (rot_y(0.05), 0.24),
-    "orbit": lambda: (translate(0, 0, -6) @ rot_y(0.3) @ translate(0, 0, 6), 0.24),
-    "pitch_shift": lambda: (translate(0.3, -0.2, 0.1) @ rot_x(-0.07), 0.24),
-    "dolly": lambda: (translate(0, 0, -0.6), 0.24),
-    "zoom": lambda: (np.eye(4), 0.31),
-}
-
-
-def _same_bits(got, want, what):
-    g, w = np.ascontiguousarray(got), np.ascontiguousarray(want)
-    assert g.shape == w.shape and g.dtype == w.dtype, what
-    if g.tobytes() != w.tobytes():
-        bad = np.argwhere(g.view(np.uint32 if g.dtype == F else g.dtype) != w.view(np.uint32 if w.dtype == F else w.dtype))
-        raise AssertionError(f"{what}: {len(bad)} values differ, first at {tuple(bad[0])}: {g[tuple(bad[0])]} against {w[tuple(bad[0])]}")
 
 
 def keep(view, mask):
@@ -137,30 +28,11 @@ def sub_pass_mask(W, H, k):
 
 @pytest.fixture(scope="module")
 def cpu(tmp_path_factory):
-    d = tmp_path_factory.mktemp("reproject_cpu")
-    exe = d / "reproject_cpu"
-    # -ffp-contract=off like the library: the header's float lines must mean the same on both sides
-    subprocess.check_call(["g++", "-std=c++17", "-O1", "-ffp-contract=off", "-Wall", "-I" + os.path.join(ROOT, "heatray_amd", "csrc"),
-                           os.path.join(ROOT, "tests", "host", "reproject_cpu.cpp"), "-o", str(exe)])
-
-    def cam_floats(pp):
-        return np.array(list(pp.view_matrix) + [pp.aspect_ratio, pp.fov_tan], F)
+    exe = cpu_header.build("reproject", tmp_path_factory.mktemp("reproject_cpu"))
 
     def run(old, old_cam, new, new_cam, examined, p):
         H, W = old[0].shape[:2]
-        with open(d / "in.bin", "wb") as f:
-            f.write(np.array([W, H, p.max_history, 0], np.int32).tobytes())
-            f.write(np.array([p.normal_cos, p.plane_tol, p.min_weight, 0], F).tobytes())
-            f.write(cam_floats(old_cam).tobytes())
-            f.write(cam_floats(new_cam).tobytes())
-            for frame, planes in (old, new):
-                f.write(np.ascontiguousarray(frame, F).tobytes())
-                for k in history.PLANES:
-                    f.write(np.ascontiguousarray(planes[k], F).tobytes())
-            f.write(np.ascontiguousarray(examined, np.uint8).tobytes())
-        out = subprocess.run([str(exe), str(d / "in.bin"), str(d / "out.bin")], capture_output=True, text=True)
-        assert out.returncode == 0 and "reproject cpu: ok" in out.stdout, (out.returncode, out.stderr)
-        raw = np.fromfile(d / "out.bin", np.uint8)
+        raw = np.frombuffer(cpu_header.run(exe, merge_input(old, old_cam, new, new_cam, p) + np.ascontiguousarray(examined, np.uint8).tobytes()), np.uint8)
         n = W * H * 16
         img = lambda k: raw[k * n:(k + 1) * n].view(F).reshape(H, W, 4)
         E = raw[8 * n:8 * n + W * H].reshape(H, W).astype(bool)
@@ -178,13 +50,13 @@ def _check(cpu, old, old_cam, new, new_cam, examined, p, what):
     image, counts = reproject.reference_preview(hist, old_cam, new[0], new[1], new_cam, p)
     frame, planes, E, res = reproject.reference_merge_progressive(hist, old_cam, new[0], new[1], new_cam, examined, p)
     got = cpu(old, old_cam, new, new_cam, examined, p)
-    _same_bits(got["history"], hist, what + ": history")
-    _same_bits(got["preview"], image, what + ": preview")
+    same_bits(got["history"], hist, what + ": history")
+    same_bits(got["preview"], image, what + ": preview")
     assert got["counts"] == counts, (what, got["counts"], counts)
-    _same_bits(got["frame"], frame, what + ": frame")
+    same_bits(got["frame"], frame, what + ": frame")
     for k in history.PLANES:
-        _same_bits(got["planes"][k], planes[k], f"{what}: {k}")
-    _same_bits(got["examined"], E, what + ": examined")
+        same_bits(got["planes"][k], planes[k], f"{what}: {k}")
+    same_bits(got["examined"], E, what + ": examined")
     assert got["merge"] == {k: res[k] for k in got["merge"]}, (what, got["merge"], res)
     H, W = image.shape[:2]
     assert counts["own_pixels"] + counts["previewed_pixels"] + counts["empty_pixels"] == W * H
@@ -206,7 +78,7 @@ def test_cpu_header_equals_numpy_reference_bit_for_bit(cpu, case):
     new_cam = camera(base @ m, fov_new, W=W, H=H)
     old = plane_view(W, H, old_cam, seed)
     rng = scenes.SplitMix64(seed + 1000)
-    u = _uniform(rng, (2, H, W))
+    u = uniform(rng, (2, H, W))
     sampled = {"ninth": sub_pass_mask(W, H, seed % 9), "third": sub_pass_mask(W, H, 0) | sub_pass_mask(W, H, 4) | sub_pass_mask(W, H, 8), "random": u[0] < 0.5}[sampling]
     new = keep(plane_view(W, H, new_cam, seed + 100), sampled)
     examined = u[1] < 0.3  # (some pixels have been examined by an earlier call, sampled or not)
@@ -238,7 +110,7 @@ def test_any_partition_of_the_sampled_pixels_gives_one_merge(split):
     elif split == "nine":
         parts = [sub_pass_mask(W, H, k) for k in range(9)]
     else:
-        pick = (_uniform(scenes.SplitMix64(5), (H, W)) * 4).astype(int)
+        pick = (uniform(scenes.SplitMix64(5), (H, W)) * 4).astype(int)
         parts = [pick == k for k in range(4)]
     assert np.sum(parts, axis=0).min() == 1 == np.sum(parts, axis=0).max()
     frame, planes = keep(new, np.zeros((H, W), bool))
@@ -251,18 +123,18 @@ def test_any_partition_of_the_sampled_pixels_gives_one_merge(split):
         for k in total:
             total[k] += res[k]
         assert res["examined_pixels"] == int(E.sum()) and res["pending_pixels"] == W * H - int(E.sum())
-    _same_bits(frame, want_frame, "frame")
+    same_bits(frame, want_frame, "frame")
     for k in history.PLANES:
-        _same_bits(planes[k], want_planes[k], k)
+        same_bits(planes[k], want_planes[k], k)
     assert total == {k: want[k] for k in total}
     sampled = new[0][..., 3] > 0
-    _same_bits(E, sampled, "examined = sampled")
+    same_bits(E, sampled, "examined = sampled")
     # a further call changes nothing and counts nothing
     frame2, planes2, E2, res2 = reproject.reference_merge_progressive(hist, old_cam, frame, planes, new_cam, E)
-    _same_bits(frame2, frame, "second call: frame")
+    same_bits(frame2, frame, "second call: frame")
     for k in history.PLANES:
-        _same_bits(planes2[k], planes[k], "second call: " + k)
-    _same_bits(E2, E, "second call: examined")
+        same_bits(planes2[k], planes[k], "second call: " + k)
+    same_bits(E2, E, "second call: examined")
     assert (res2["reused_pixels"], res2["rejected_pixels"], res2["history_samples"]) == (0, 0, 0)
     assert (res2["pending_pixels"], res2["examined_pixels"]) == (int((~sampled).sum()), int(sampled.sum()))
 
@@ -275,10 +147,10 @@ def test_a_second_call_changes_nothing_and_counts_nothing_on_the_cpu_build(cpu):
     frame, planes, E, res, _, _ = _check(cpu, old, old_cam, new, new_cam, np.zeros((H, W), bool), p, "first")
     assert res["reused_pixels"] > 0
     frame2, planes2, E2, res2, _, _ = _check(cpu, old, old_cam, (frame, planes), new_cam, E, p, "second")
-    _same_bits(frame2, frame, "frame")
+    same_bits(frame2, frame, "frame")
     for k in history.PLANES:
-        _same_bits(planes2[k], planes[k], k)
-    _same_bits(E2, E, "examined")
+        same_bits(planes2[k], planes[k], k)
+    same_bits(E2, E, "examined")
     assert (res2["reused_pixels"], res2["rejected_pixels"], res2["history_samples"]) == (0, 0, 0)
 
 
@@ -288,7 +160,7 @@ def test_the_preview_of_a_fully_sampled_frame_is_every_pixels_own_mean(cpu):
     new = plane_view(W, H, new_cam, 32, holes=False)
     _, _, _, _, image, counts = _check(cpu, old, old_cam, new, new_cam, np.zeros((H, W), bool), history.default_params(), "full")
     assert counts == {"own_pixels": W * H, "previewed_pixels": 0, "empty_pixels": 0}
-    _same_bits(image[..., :3], new[0][..., :3] / new[0][..., 3:], "own mean")
+    same_bits(image[..., :3], new[0][..., :3] / new[0][..., 3:], "own mean")
     assert (image[..., 3] == 1).all()
 
 
