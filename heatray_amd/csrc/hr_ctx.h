@@ -190,7 +190,7 @@ struct hr_ctx {
         unsigned long long *dSeq = nullptr;
         hipStream_t streamB = nullptr;                 // HR_TUNE corun=1: the fused packet kernel of a step runs here, beside k_trace (experiment)
         hipEvent_t evFork = nullptr, evJoin = nullptr;
-        volatile unsigned long long *hProbe = nullptr; // [kTableRing][3], pinned: the packet probe's totals as of that step's k_trace (packet selector below)
+        volatile unsigned long long *hProbe = nullptr; // [kTableRing][8] (five used), pinned: the packet probe's totals as of that step's k_trace (packet selector below)
         unsigned long long *dProbeHost = nullptr;      // ... as the device addresses it
         int countN[4] = {0, 0, 0, 0};                  // entries of the step table that went with ring entry r
         int countSlot[4][HR_MAX_SEGS];                 // ... their pass slots
@@ -330,6 +330,15 @@ struct hr_ctx {
     int tuneCorun = 1;       // HR_TUNE="corun=0|1|2": never (the packet kernel in front of k_trace on the group's stream) / by the probe / always
     int tuneCorunMin = 50;   // HR_TUNE="cmin=N": beside k_trace when a probed camera ray enters at least N child boxes
     int tunePacketSwizzle = 1; // HR_TUNE="pswz=0|1": k_raygen_packets deals whole 32x32 tiles to the XCDs (workgroup index -> XCD is round robin) instead of consecutive 16-pixel patches: a tile's part of the tree goes through ONE L2 (+0.3-0.7 % on c3 / c2 / c5, profiles/r5ak_packet_xcd.txt)
+    // The packet kernel tests a node's child boxes ONCE per packet against the packet's bounds (the interval step, hr_packet_interval.h,
+    // DESIGN §2) instead of once per ray.  That walk enters a superset of the children; how much more is the scene's and the camera's:
+    // the selector's probe walks both ways and reports F = children entered by the interval step / by the per-ray step (c3 1.05,
+    // c3d 1.02, c2 1.01: +3..7 %; terrain 1.2, its short walks mostly leaves, where every extra child is a triangle test: -3.7 %).
+    int tunePacketStep = 1;  // HR_TUNE="pstep=0|1": the per-ray step of rounds 4-5 / the interval step where F allows it (default)
+    int tunePacketStepF = 110; // HR_TUNE="pstepf=N": the interval step while F < N / 100 (0: whatever F is); no report yet: the interval step
+    double lastLooseness = 0.0; // F of the last probe (0: none has reported)
+    bool useIntervalStep() const { return tunePacketStep != 0 && (tunePacketStepF <= 0 || lastLooseness == 0.0 || lastLooseness * 100.0 < (double)tunePacketStepF); }
+    int tuneProbeStep = 0;   // HR_TUNE="pprobe=1" (measurement only): the probe's four totals come from a walk with the interval step, so packet_union is what that step enters; decisions are meant to be taken at 0
     int tuneProbeLog2 = -1;  // HR_TUNE="plog=N" (measurement only): the selector's probe walks packets of 2^N passes x 64 >> N pixels instead of the shape in use
     int tuneCorunBlocks = 0; // HR_TUNE="cblocks=N": fix k_trace's workgroups per CU in such a step (0: 3 or 4 by the step's mix)
     int tunePacketUnion = 220; // HR_TUNE="punion=N": packets while U < N / 100 (measured break-even ~2.3: terrain at 1.97 +7..11 %, c5 at 2.07 +3..4 %)
@@ -338,12 +347,12 @@ struct hr_ctx {
     int probeCountdown = 0;              // injecting steps until the next probe
     bool probePending = false;
     unsigned long long probeStep = 0;    // step (of group 0) that carried the pending probe
-    unsigned long long probeSeen[4] = {0, 0, 0, 0}; // totals of the report the last decision was taken on
+    unsigned long long probeSeen[5] = {0, 0, 0, 0, 0}; // totals of the report the last decision was taken on
     double lastOwnPerRay = 0.0;         // child boxes a probed camera ray entered: how long the scene's traversals are
     unsigned long long probeWaves = 0;   // waves of the pending probe: it is complete when the third total has grown by as many
     double lastUnion = 0.0;              // U of the last probe (HR_DEBUG_PIPE prints it)
     float probeCamera[21] = {0};         // fov, aspect, focus distance, aperture, view matrix, interactive mode of the probed pass
-    unsigned long long *dProbe = nullptr; // three device counters the probe launches add to (never reset)
+    unsigned long long *dProbe = nullptr; // five device counters (of eight words) the probe launches add to (never reset)
     hipStream_t probeStream = nullptr;   // the probe runs beside the pipeline: it makes its own camera rays and writes only the counters
     hipEvent_t evProbeA = nullptr, evProbeB = nullptr; // scene and tables as the group's stream sees them -> probe may start; probe done
     bool probeGuard = false;             // evProbeB has not been waited for yet (drainPipeline does: the scene may change afterwards)
@@ -496,7 +505,7 @@ struct hr_ctx {
     GroupState *grp = nullptr;
     LaunchCfg cfg(hipStream_t st) const
     {
-        return LaunchCfg{st, numCUs, tuneBlocks, tuneShadeBlocks, collectStats, textureLodUsed, allLightsUsed, hasGlass, tunePacketSwizzle, (aovMask & HR_AOV_SURFACE) != 0};
+        return LaunchCfg{st, numCUs, tuneBlocks, tuneShadeBlocks, collectStats, textureLodUsed, allLightsUsed, hasGlass, tunePacketSwizzle, useIntervalStep() ? 1 : 0, (aovMask & HR_AOV_SURFACE) != 0};
     }
 };
 

@@ -41,6 +41,7 @@ struct LaunchCfg {
     bool allLights;  // some pass has asked for HR_ESTIMATOR_ALL_LIGHTS: the shading kernel that can emit two occlusion rays per vertex
     bool hasGlass;   // some material of the scene is glass: the glass shading kernel is launched too
     int packetSwizzle = 0; // k_raygen_packets deals whole 32x32 tiles to the XCDs instead of consecutive 16-pixel patches (HR_TUNE pswz)
+    int packetStep = 1;    // k_raygen_packets tests a node's children once per packet against the packet's bounds (hr_ctx::useIntervalStep; hr_packet_interval.h)
     bool aovSurface = false; // HR_AOV_SURFACE is enabled: launch the shading kernel that records the first visible surface (include/hrcore_aov.h)
 };
 
@@ -170,7 +171,7 @@ void launchTrace(const LaunchCfg &cfg, const SceneDev *S, const int *leafKeys, c
 void launchRaygenPackets(const LaunchCfg &cfg, const SceneDev *S, const Node4 *nodes, const Tri *tris, const StepTable *tbl, const SegList &segs,
                          const FrameDev &fr, Stats *stats, bool uniformParams); // segs.n: a power of two; uniformParams: the passes differ in sample_index only
 int launchPacketProbe(hipStream_t stream, const SceneDev *S, const Node4 *nodes, const Tri *tris, const hr_pass_params &pp, int passesLog2, const FrameDev &fr,
-                      unsigned long long *probe);
+                      unsigned long long *probe, bool intervalStep);
 void launchShadowProbe(hipStream_t stream, const SceneDev *S, const Node4 *nodes, const Tri *tris, const StepTable *tbl, const SegList &segs, uint32_t maxRays,
                        unsigned long long *probe); // measurement only (HR_TUNE sprobe=)
 void launchShade(const LaunchCfg &cfg, const SceneDev *S, const StepTable *tbl, Stats *stats);

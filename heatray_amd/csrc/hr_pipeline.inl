@@ -322,16 +322,17 @@ static int macroStep(hr_ctx *c, int g, int nInject)
             int rc = waitCounts(c, G, prev, stepIdx); // (step stepIdx - 1 wrote stepIdx: its number + 1)
             if (rc) return rc;
             if (g == 0 && c->probePending && stepIdx > c->probeStep) { // (steps from the probe's own on report the totals) complete once every wave of the probe has counted itself
-                const unsigned long long pk = G.hProbe[4 * prev], ry = G.hProbe[4 * prev + 1], done = G.hProbe[4 * prev + 2], nr = G.hProbe[4 * prev + 3];
+                const unsigned long long pk = G.hProbe[8 * prev], ry = G.hProbe[8 * prev + 1], done = G.hProbe[8 * prev + 2], nr = G.hProbe[8 * prev + 3], iv = G.hProbe[8 * prev + 4];
                 if (done - c->probeSeen[2] >= c->probeWaves) {
-                    const unsigned long long dPk = pk - c->probeSeen[0], dRy = ry - c->probeSeen[1], dNr = nr - c->probeSeen[3];
-                    c->probePending = false, c->probeSeen[0] = pk, c->probeSeen[1] = ry, c->probeSeen[2] = done, c->probeSeen[3] = nr;
+                    const unsigned long long dPk = pk - c->probeSeen[0], dRy = ry - c->probeSeen[1], dNr = nr - c->probeSeen[3], dIv = iv - c->probeSeen[4];
+                    c->probePending = false, c->probeSeen[0] = pk, c->probeSeen[1] = ry, c->probeSeen[2] = done, c->probeSeen[3] = nr, c->probeSeen[4] = iv;
+                    if (dPk > 0) c->lastLooseness = (double)dIv / (double)dPk; // F: children entered, interval step / per-ray step
                     if (dRy > 0) {
                         c->lastUnion = (double)dPk / (double)dRy;
                         c->packetsOn = c->lastUnion * 100.0 < (double)c->tunePacketUnion;
                         c->lastOwnPerRay = dNr ? (double)dRy / (double)dNr : 0.0;
                     }
-                    if (getenv("HR_DEBUG_PIPE")) fprintf(stderr, "packet probe of step %llu (seen at step %llu): union %.3f, %.1f child boxes entered per ray -> packets %s\n", c->probeStep, stepIdx, c->lastUnion, c->lastOwnPerRay, c->packetsOn ? "on" : "off");
+                    if (getenv("HR_DEBUG_PIPE")) fprintf(stderr, "packet probe of step %llu (seen at step %llu): union %.3f, %.1f child boxes entered per ray -> packets %s; interval step F %.3f -> %s\n", c->probeStep, stepIdx, c->lastUnion, c->lastOwnPerRay, c->packetsOn ? "on" : "off", c->lastLooseness, c->useIntervalStep() ? "on" : "off");
                 }
             }
             for (int i = 0; i < kMaxSlots; ++i) idxOfSlot[i] = -1;
@@ -486,7 +487,7 @@ static int macroStep(hr_ctx *c, int g, int nInject)
     for (int j = 0; j < nInjectedSegs; ++j)
         if (packetsNow) tbl.seg[injectedSegs[j]].packets = corunNow ? 2 : 1;
     tbl.hostCameraCount = corunNow ? G.dCounts + (size_t)kTableRing * kMaxSegs : nullptr;
-    tbl.probe = c->dProbe, tbl.hostProbe = (g == 0 && (c->probePending || probeSeg >= 0)) ? G.dProbeHost + 4 * ring : nullptr; // (reported only while a probe is awaited)
+    tbl.probe = c->dProbe, tbl.hostProbe = (g == 0 && (c->probePending || probeSeg >= 0)) ? G.dProbeHost + 8 * ring : nullptr; // (reported only while a probe is awaited)
     G.countN[ring] = n;
     tbl.hostCounts = G.dCounts + (size_t)ring * kMaxSegs, tbl.hostSeq = G.dSeq + ring, tbl.seqValue = stepIdx + 1ull;
     tbl.stepLog = c->dStepLog, tbl.nInjectedNow = (uint32_t)nInjected, tbl.group = (uint32_t)g;
@@ -521,8 +522,11 @@ static int macroStep(hr_ctx *c, int g, int nInject)
             a.sample_index = b.sample_index = 0;
             uniformParams = std::memcmp(&a, &b, sizeof(a)) == 0;
         }
+        LaunchCfg cfgP = cfg; // (a pass with a lens: none of its packets has one origin, none can take the interval step)
+        for (int j = 0; j < segs.n; ++j)
+            if (tbl.seg[segs.seg[j]].pp.aperture_radius > 1e-30f) cfgP.packetStep = 0;
         if (corunNow) { // beside k_trace: fork after the table copy, join before the shading kernels
-            LaunchCfg cb = cfg;
+            LaunchCfg cb = cfgP;
             cb.stream = G.streamB;
             if (!forked) {
                 HIP_TRY(c, hipEventRecord(G.evFork, G.stream));
@@ -538,7 +542,7 @@ static int macroStep(hr_ctx *c, int g, int nInject)
             c->timeBegin(HR_KERNEL_RAYGEN, G.stream);
         timing = true;
         if (packetsNow)
-            launchRaygenPackets(cfg, c->dScene, c->nodes, c->tris, dTbl, segs, fr, c->dStats, uniformParams);
+            launchRaygenPackets(cfgP, c->dScene, c->nodes, c->tris, dTbl, segs, fr, c->dStats, uniformParams);
         else
             launchRaygen(cfg, c->dScene, dTbl, segs, fr, c->dStats);
     }
@@ -564,7 +568,7 @@ static int macroStep(hr_ctx *c, int g, int nInject)
         // (probeSeen holds the totals of the report the previous decision was taken on: probes never overlap, that probe was complete)
         HIP_TRY(c, hipEventRecord(c->evProbeA, G.stream));
         HIP_TRY(c, hipStreamWaitEvent(c->probeStream, c->evProbeA, 0));
-        c->probeWaves = (unsigned long long)launchPacketProbe(c->probeStream, c->dScene, c->nodes, c->tris, tbl.seg[probeSeg].pp, c->tuneProbeLog2 >= 0 ? c->tuneProbeLog2 : packetLog2(c), fr, c->dProbe);
+        c->probeWaves = (unsigned long long)launchPacketProbe(c->probeStream, c->dScene, c->nodes, c->tris, tbl.seg[probeSeg].pp, c->tuneProbeLog2 >= 0 ? c->tuneProbeLog2 : packetLog2(c), fr, c->dProbe, c->tuneProbeStep != 0);
         HIP_TRY(c, hipEventRecord(c->evProbeB, c->probeStream));
         c->probeGuard = true, c->probePending = true, c->probeStep = stepIdx, c->probeCountdown = kProbeEvery;
     }
