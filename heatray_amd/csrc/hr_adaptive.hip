@@ -1,8 +1,8 @@
 // hr_adaptive.hip — the kernels of adaptive sampling (include/hrcore_adaptive.h is the contract, hr_adaptive.h the per-pixel arithmetic,
-// hr_adaptive.inl the entry points).  A translation unit of its own: nothing here touches the register budgets of hr_render.hip.
+// hr_adaptive.inl the entry points).  A translation unit of its own: nothing here touches the register budgets of the render stages (hr_raygen.hip, hr_trace.hip, hr_shade.hip).
 //
 // The sample mask lives on the device as row-major 32-bit words, (W + 31) / 32 per row, bit (x & 31) of word (x >> 5) of row y = pixel
-// (x, y); bits beyond W are 0.  cameraLane (hr_render.hip) reads it: a wave of k_raygen covers an 8 x 8 block, eight words.
+// (x, y); bits beyond W are 0.  cameraLane (hr_raygen.hip) reads it: a wave of k_raygen covers an 8 x 8 block, eight words.
 //
 //   k_adaptive_error   one lane per pixel: the frame's and the MOMENTS plane's float4 (32 B, coalesced) -> the pixel's error (4 B)
 //   k_adaptive_mask    a workgroup owns a tile of 64 x 16 pixels: it stages the unconverged flags of the tile and a halo of `radius`

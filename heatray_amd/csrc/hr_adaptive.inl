@@ -1,5 +1,5 @@
 // hr_adaptive.inl — a section of hr_core.hip (included at its end): the entry points of include/hrcore_adaptive.h.  The kernels are in
-// hr_adaptive.hip; cameraLane (hr_render.hip) reads the mask through FrameDev::mask.
+// hr_adaptive.hip; cameraLane (hr_raygen.hip) reads the mask through FrameDev::mask.
 //
 // Ordering.  The mask words are rewritten in place on the context's stream after drainPipeline: every enqueued pass has been given its
 // resolve there by then, and a resolve waits for its pass's last stage, so the write comes after every ray generation that read the

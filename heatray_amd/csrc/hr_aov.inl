@@ -1,5 +1,5 @@
 // hr_aov.inl — a section of hr_core.hip (included at its end): the entry points of include/hrcore_aov.h.  The device side is in
-// hr_render.hip (k_shade_hit<MODE | 4, CLS> records a pass's first visible surface in the pass slot's AOV record, k_resolve_aov folds
+// hr_shade.hip and hr_frame.hip (k_shade_hit<MODE | 4, CLS> records a pass's first visible surface in the pass slot's AOV record, k_resolve_aov folds
 // the records and the samples' squares into the frame's planes); the planes' life follows the frame's (hr_clear, hr_frame_resize).
 
 static const char *const kAovPlaneNames[3] = {"ALBEDO", "NORMAL_DEPTH", "MOMENTS"};

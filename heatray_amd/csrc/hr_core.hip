@@ -17,11 +17,13 @@
 //   hr_history.inl    history reprojection across a camera change (include/hrcore_history.h)
 //   hr_reproject.inl  its progressive form and the preview of unsampled pixels (include/hrcore_reproject.h)
 // (one translation unit: the .inl files are sections of this one, included below)
+// The kernels it launches are units of their own (declared in hr_kernels.h): the render stages hr_raygen.hip, hr_trace.hip, hr_shade.hip and
+// hr_frame.hip (resolve, shard exchange, display) over what they share in hr_wave.h; hr_build.hip; one unit per post-process feature.
 #include "hr_ctx.h"
 
 static const int kTableRing = 4;
 static int drainPipeline(hr_ctx *c);
-// A kernel found a ray queue longer than its capacity (hr_render.hip: queueOverflow): rays were dropped, the frame is not the render
+// A kernel found a ray queue longer than its capacity (hr_wave.h: queueOverflow): rays were dropped, the frame is not the render
 // that was asked for.  Sticky until hr_clear; every call that hands finished work to the caller reports it.
 static int overflowCheck(hr_ctx *c)
 {

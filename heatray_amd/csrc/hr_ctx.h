@@ -117,7 +117,7 @@ struct hr_ctx {
     size_t displayBytes = 0;
     FrameDev frame{};
     uint32_t queueCapacity = 0;
-    // Pipeline of in-flight passes (hr_render.hip header): every slot owns the queues, hit records, counters and
+    // Pipeline of in-flight passes (hr_trace.hip header): every slot owns the queues, hit records, counters and
     // the pass buffer of one pass.
     struct PassSlot {
         bool allocated = false, active = false;
@@ -217,7 +217,7 @@ struct hr_ctx {
     uint32_t *dZero = nullptr;    // a zero word (occlusion count of a pass's first step)
     Counters *dCounters = nullptr; // one per pass slot, contiguous (copied to the host in one piece in pass-through scenes)
     unsigned long long *dStepLog = nullptr; // kStepLogCap records of three words (StepTable::stepLog)
-    // Sticky report of a ray queue that turned out longer than its capacity (hr_render.hip: queueOverflow): four pinned, coherent words
+    // Sticky report of a ray queue that turned out longer than its capacity (hr_wave.h: queueOverflow): four pinned, coherent words
     // the kernels write — kind of queue, step, table entry, count.  Checked wherever the caller learns about finished work.
     volatile uint32_t *hOverflow = nullptr;
     uint32_t *dOverflowHost = nullptr; // ... as the device addresses them
@@ -310,7 +310,7 @@ struct hr_ctx {
     // pipeline diagnostics (HR_DEBUG_PIPE=1 prints them when the context is destroyed)
     unsigned long long dbgGrowths = 0, dbgGrowBytes = 0, dbgWaits = 0, dbgWaitNs = 0, dbgWaitSpun = 0;
     // ---- packet selector.  The camera rays of the passes injected together can be traced one ray per lane by k_trace, or 64 at a time as a
-    // packet by k_raygen_packets (hr_render.hip): 2^k passes of 64 >> k neighbouring pixels per wave.  The packet walks the UNION of its
+    // packet by k_raygen_packets (hr_raygen.hip): 2^k passes of 64 >> k neighbouring pixels per wave.  The packet walks the UNION of its
     // rays' node sets: it wins where that union is small against the sum — meshes, and since a pixel's rays in consecutive passes differ by
     // the jitter only, even the benchmark's triangle fog at 16 passes per packet (1.8 x; one pass of an 8x8 patch: 3.0 x, which loses).
     // Which it is depends on scene, camera and resolution, so it is measured: every kProbeEvery-th injecting step — and the first after a

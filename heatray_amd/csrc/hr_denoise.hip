@@ -1,5 +1,5 @@
 // hr_denoise.hip — the kernels of the denoiser (include/hrcore_denoise.h is the contract, hr_denoise.h the per-pixel arithmetic, hr_denoise.inl
-// the entry points).  A translation unit of its own: nothing here touches the register budgets of hr_render.hip.
+// the entry points).  A translation unit of its own: nothing here touches the register budgets of the render stages (hr_raygen.hip, hr_trace.hip, hr_shade.hip).
 //
 //   k_denoise_prepare    one pass over the frame and the three AOV planes (four coalesced 16-byte loads per pixel) -> the working planes
 //                        cv (demodulated colour + variance), nd (unit normal + depth), ac (effective albedo + coverage; -1 marks a pixel

@@ -1,5 +1,5 @@
 // hr_history.hip — the kernels of history reprojection (include/hrcore_history.h is the contract, hr_history.h the per-pixel arithmetic,
-// hr_history.inl the entry points).  A translation unit of its own: nothing here touches the register budgets of hr_render.hip.
+// hr_history.inl the entry points).  A translation unit of its own: nothing here touches the register budgets of the render stages (hr_raygen.hip, hr_trace.hip, hr_shade.hip).
 //
 // The history lives on the device as three planes of W x H float4 one after the other: H0, H1, H2.
 //

@@ -1,4 +1,4 @@
-// hr_kernels.h — host-visible declarations of the kernel launchers (hr_render.hip, hr_build.hip).
+// hr_kernels.h — host-visible declarations of the kernel launchers (the render stages hr_frame.hip, hr_raygen.hip, hr_trace.hip and hr_shade.hip; hr_build.hip; the post-process units).
 #pragma once
 
 #include "hr_types.h"
@@ -67,7 +67,7 @@ struct SegDev {
     int32_t closestEnabled; // 0 in a pass's last step (only its occlusion rays remain)
     // Capacities of the queues beside hitCap (which also bounds hits / hitIdx / qout): every append compares its slot with them and every
     // reader clamps the counter it reads — a bound that turns out wrong drops rays and raises StepTable::hostOverflow instead of
-    // writing past an arena (hr_render.hip: queueOverflow)
+    // writing past an arena (hr_wave.h: queueOverflow)
     uint32_t qinCap;  // rays qin can hold
     uint32_t sInCap;  // occlusion rays sqIn can hold
     uint32_t sOutCap; // occlusion rays sqOut can hold
@@ -126,13 +126,15 @@ struct StepTable {
 };
 static_assert(offsetof(StepTable, heads) % 128 == 0 && offsetof(StepTable, seg) % 128 == 0, "k_trace's work cursors own their cache lines");
 
-// ---- hr_render.hip
+// ---- the render stages (what their units share on the device: hr_wave.h)
 // Several passes per launch (a small shard injects / resolves a batch of passes per macro step: one launch instead of 8 + 8)
 static const int kMaxBatch = 16;
 struct SegList {
     int32_t n;
     int32_t seg[kMaxBatch]; // indices into StepTable::seg, one per blockIdx.y
 };
+
+// ---- hr_frame.hip
 struct PassBufList {
     int32_t n;
     const float *buf[kMaxBatch]; // pass samples, added to the frame in this order
@@ -146,7 +148,6 @@ struct CounterList {
 };
 void launchZeroCounters(const LaunchCfg &cfg, const CounterList &list);
 void launchFetchTable(hipStream_t stream, const void *hostMapped, void *dst, size_t bytes);
-void launchRaygen(const LaunchCfg &cfg, const SceneDev *S, const StepTable *tbl, const SegList &segs, const FrameDev &fr, Stats *stats);
 void launchResolve(const LaunchCfg &cfg, const FrameDev &fr, const PassBufList &bufs);
 // AOVs (include/hrcore_aov.h): the frame's planes (null when not enabled) and each pass's AOV planes (null without HR_AOV_SURFACE), in
 // the order of PassBufList.  The resolve that adds the passes to the frame folds them into the planes and zeroes the passes' planes.
@@ -167,17 +168,24 @@ struct GatherList {
 int gatherBlock(); // workgroup size of k_gather_members (slots per padded workgroup)
 void launchGatherMembers(const LaunchCfg &cfg, const FrameDev &fr, const GatherList &list, float *full);
 void launchDisplay(const LaunchCfg &cfg, const FrameDev &fr, const hr_display_params &P, int format, void *out);
-void launchTrace(const LaunchCfg &cfg, const SceneDev *S, const int *leafKeys, const Node32 *nodes32, const Tri *tris, StepTable *tbl, Stats *stats);
+
+// ---- hr_raygen.hip
+void launchRaygen(const LaunchCfg &cfg, const SceneDev *S, const StepTable *tbl, const SegList &segs, const FrameDev &fr, Stats *stats);
 void launchRaygenPackets(const LaunchCfg &cfg, const SceneDev *S, const Node4 *nodes, const Tri *tris, const StepTable *tbl, const SegList &segs,
                          const FrameDev &fr, Stats *stats, bool uniformParams); // segs.n: a power of two; uniformParams: the passes differ in sample_index only
 int launchPacketProbe(hipStream_t stream, const SceneDev *S, const Node4 *nodes, const Tri *tris, const hr_pass_params &pp, int passesLog2, const FrameDev &fr,
                       unsigned long long *probe, bool intervalStep);
 void launchShadowProbe(hipStream_t stream, const SceneDev *S, const Node4 *nodes, const Tri *tris, const StepTable *tbl, const SegList &segs, uint32_t maxRays,
                        unsigned long long *probe); // measurement only (HR_TUNE sprobe=)
-void launchShade(const LaunchCfg &cfg, const SceneDev *S, const StepTable *tbl, Stats *stats);
+
+// ---- hr_trace.hip
+void launchTrace(const LaunchCfg &cfg, const SceneDev *S, const int *leafKeys, const Node32 *nodes32, const Tri *tris, StepTable *tbl, Stats *stats);
 void launchDebugTrace(const LaunchCfg &cfg, const SceneDev *S, int n, const float *o, const float *d, const float *tmax, const int *skip,
                       int anyHit, hr_hit *out);
 size_t hitRecordSize();
+
+// ---- hr_shade.hip
+void launchShade(const LaunchCfg &cfg, const SceneDev *S, const StepTable *tbl, Stats *stats);
 
 // ---- hr_denoise.hip (include/hrcore_denoise.h)
 // the working planes of the denoiser, W x H each: cv = demodulated colour + variance (ping-pong), nd = unit normal + depth,

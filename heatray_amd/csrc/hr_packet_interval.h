@@ -1,5 +1,5 @@
 // hr_packet_interval.h — the arithmetic of the camera-ray packet's INTERVAL box test (DESIGN.md §2 "Camera-ray packets: one interval
-// box test per node").  Pure float32 functions, no memory of their own, compiled by the packet kernel (hr_render.hip: packetTraverseInterval)
+// box test per node").  Pure float32 functions, no memory of their own, compiled by the packet kernel (hr_raygen.hip: packetTraverseInterval)
 // and by the CPU test (tests/host/packet_interval_cpu.cpp) from the same lines.
 //
 // The packet kernel enters a child of a node when ANY of its 64 rays' own slab tests enters it.  Each of those tests computes, per axis

@@ -657,7 +657,7 @@ static int injectBatch(hr_ctx *c, int n, int perGroupLimit)
     return macroStep(c, g, n);
 }
 
-// Passes injected together when their camera rays travel as packets: a wave holds 2^k passes of 64 >> k pixels (hr_render.hip:
+// Passes injected together when their camera rays travel as packets: a wave holds 2^k passes of 64 >> k pixels (hr_raygen.hip:
 // k_raygen_packets), so the batch is the power of two next to the usual one (12 -> 16, 3 -> 4, 5 -> 4), sixteen per launch at most.
 static int packetBatch(const hr_ctx *c)
 {

@@ -5,19 +5,12 @@
 #pragma once
 #include "hr_math.h"    // HRD, G
 #include "hr_denoise.h" // dn4
+#include "hr_wave_sum.h" // waveSum (shared with the render stages)
 
 namespace hr {
 
 // lanes of the wave for which `p` holds; the same number in every lane
 HRD uint32_t waveCount(bool p) { return (uint32_t)__popcll(__ballot(p)); }
-
-// the wave's sum of `v`, in every lane (the caller sees to it that it fits 32 bits)
-HRD uint32_t waveSum(uint32_t v)
-{
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += (uint32_t)__shfl_xor((int)v, o);
-    return v;
-}
 
 // (no barrier: the caller has one between this and the first add)
 template <int N> HRD void wgCountersZero(uint32_t *sRed)

@@ -1,6 +1,6 @@
 // hr_reproject.hip — the kernels of the progressive history merge and the preview (include/hrcore_reproject.h is the contract,
 // hr_reproject.h the per-pixel arithmetic, hr_reproject.inl the entry points).  A translation unit of its own: nothing here touches the
-// register budgets of hr_history.hip or hr_render.hip.
+// register budgets of hr_history.hip or the render stages (hr_raygen.hip, hr_trace.hip, hr_shade.hip).
 //
 //   k_reproject_merge    k_history_merge's shape: one lane per pixel, a wave = an 8 x 8 block of pixels, a workgroup four of them side by
 //                        side (32 x 8).  The examined bits are one 64-bit word per 8 x 8 block, bit = the lane: a wave reads its word

@@ -1,6 +1,6 @@
 // heatray_amd/csrc/hr_packet_interval.h on the CPU (tests/test_packet_interval_ref.py): a fuzz of (node, packet) pairs that holds the
 // interval box test of the camera-ray packets against the per-ray test it replaces.  The per-ray lines below restate packetTraverse's
-// (hr_render.hip) and safeInv / rayFrame (hr_trace.h), operation for operation; the interval side calls the header the kernel compiles.
+// (hr_raygen.hip) and safeInv / rayFrame (hr_trace.h), operation for operation; the interval side calls the header the kernel compiles.
 // Input: uint32 seed, pairs.  Output: uint64 counters, see `Out`.
 #include "hr_packet_interval.h"
 

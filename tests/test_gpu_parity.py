@@ -1495,7 +1495,7 @@ def test_memory_budget_bounds_the_batch_and_the_frame_stays_the_same(golden):
 @pytest.mark.parametrize("packets", [0, 1])
 def test_a_wrong_queue_bound_is_an_error_not_a_fault(golden, monkeypatch, ovf, kind, packets):
     # Every append to a ray queue compares its slot with the queue's capacity and every reader clamps the counter it reads
-    # (hr_render.hip: queueOverflow).  HR_TUNE ovf= hands the kernels HALF (an eighth) of what a bound should be — the mistake that
+    # (hr_wave.h: queueOverflow).  HR_TUNE ovf= hands the kernels HALF (an eighth) of what a bound should be — the mistake that
     # was a memory fault in round 4 —: rays are dropped, the device reports the queue, and the calls that hand work back fail with it.
     monkeypatch.setenv("HR_TUNE", f"ovf={ovf},packets={packets}")
     sc = scenes.triangle_soup(20000, width=320, height=192, bounces=4, passes=64, env=True, room=True)

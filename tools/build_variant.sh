@@ -1,13 +1,18 @@
 #!/bin/bash
 # tools/build_variant.sh NAME "<extra hipcc flags>"  ->  build_variants/libhrcore_NAME.so  (A/B experiments; load with HRCORE_LIB)
+# The units and the flags are the Makefile's (SRCS, print-flags); the objects go to a directory of their own.
 set -e
 name="$1"; extra="$2"
 root="$(cd "$(dirname "$0")/.." && pwd)"
+csrc="$root/heatray_amd/csrc"
 tmp="$(mktemp -d)"; mkdir -p "$root/build_variants"
-FLAGS="--offload-arch=gfx950 -O3 -std=c++17 -fPIC -ffp-contract=off -fno-fast-math -fno-gpu-flush-denormals-to-zero -Wno-unused-function -Wno-unused-result -Wno-unused-value -I$root/include $extra"
-for f in hr_core hr_render hr_build; do
-  /opt/rocm/bin/hipcc $FLAGS -c "$root/heatray_amd/csrc/$f.hip" -o "$tmp/$f.o" &
+FLAGS="$(make -s -C "$csrc" print-flags EXTRA="$extra")"
+srcs="$(sed -n 's/^SRCS := //p' "$csrc/Makefile")"
+cd "$csrc"
+pids=""
+for f in $srcs; do
+  /opt/rocm/bin/hipcc $FLAGS -c "$f" -o "$tmp/${f%.hip}.o" & pids="$pids $!"
 done
-wait
+for p in $pids; do wait "$p"; done
 /opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -fPIC -o "$root/build_variants/libhrcore_$name.so" "$tmp"/*.o
 rm -rf "$tmp"; echo "built build_variants/libhrcore_$name.so"

@@ -21,8 +21,10 @@ FAST = {"v_fma_f32", "v_fmac_f32", "v_mul_f32", "v_add_f32", "v_sub_f32", "v_sub
         "v_mov_b32", "v_cndmask_b32", "v_mac_f32", "v_madak_f32", "v_madmk_f32", "v_fmaak_f32", "v_fmamk_f32", "v_not_b32"}
 TRANS = {"v_rcp_f32", "v_rsq_f32", "v_sqrt_f32", "v_exp_f32", "v_log_f32", "v_sin_f32", "v_cos_f32", "v_rcp_iflag_f32", "v_mul_lo_u32", "v_mul_hi_u32", "v_mul_hi_i32", "v_mad_u64_u32", "v_mad_i64_i32"}
 COST = {"fast": 2.3, "slow": 4.0, "trans": 8.0}  # cycles per wave64 instruction (calib_ops.hip / calib_valu.hip at ~2.3 GHz: 1.0 / 1.72 / 3.4 ns)
-KERNELS = {"k_trace": "_ZN2hr7k_traceILb0EE", "k_raygen_packets": "_ZN2hr16k_raygen_packetsILb0ELb1EE", "k_shade_hit": "_ZN2hr11k_shade_hitILi0ELi0EE",
-           "k_shade_sort": "_ZN2hr12k_shade_sortE", "k_raygen": "_ZN2hr8k_raygenE"}
+# kernel -> (the unit that holds it, the start of its mangled name)
+KERNELS = {"k_trace": ("hr_trace.hip", "_ZN2hr7k_traceILb0EE"), "k_raygen_packets": ("hr_raygen.hip", "_ZN2hr16k_raygen_packetsILb0ELb1EE"),
+           "k_shade_hit": ("hr_shade.hip", "_ZN2hr11k_shade_hitILi0ELi0EE"), "k_shade_sort": ("hr_shade.hip", "_ZN2hr12k_shade_sortE"),
+           "k_raygen": ("hr_raygen.hip", "_ZN2hr8k_raygenE")}
 
 
 def classify(line):
@@ -47,13 +49,16 @@ def classify(line):
 def main():
     out_path = sys.argv[1] if len(sys.argv) > 1 else os.path.join(ROOT, "profiles", "r5_valu_mix.json")
     flags = subprocess.run(["make", "-s", "-C", CSRC, "print-flags"], capture_output=True, text=True, check=True).stdout.split()
+    texts = {}
     with tempfile.TemporaryDirectory() as td:
-        asm = os.path.join(td, "hr_render.s")
-        subprocess.run(["/opt/rocm/bin/hipcc", *flags, "-S", "--cuda-device-only", os.path.join(CSRC, "hr_render.hip"), "-o", asm], check=True, capture_output=True, cwd=CSRC)
-        text = open(asm).read().splitlines()
-    res = {"cost_cycles": COST, "source": "static instruction mix of hr_render.hip's gfx950 ISA, priced with tools/calib_ops.hip's measured issue costs",
+        for unit in sorted({u for u, _ in KERNELS.values()}):
+            asm = os.path.join(td, unit + ".s")
+            subprocess.run(["/opt/rocm/bin/hipcc", *flags, "-S", "--cuda-device-only", os.path.join(CSRC, unit), "-o", asm], check=True, capture_output=True, cwd=CSRC)
+            texts[unit] = open(asm).read().splitlines()
+    res = {"cost_cycles": COST, "source": "static instruction mix of the render units' gfx950 ISA, priced with tools/calib_ops.hip's measured issue costs",
            "kernels": {}}
-    for name, prefix in KERNELS.items():
+    for name, (unit, prefix) in KERNELS.items():
+        text = texts[unit]
         start = next((i for i, l in enumerate(text) if l.startswith(prefix) and l.split(";")[0].rstrip().endswith(":")), None)
         if start is None:
             continue
