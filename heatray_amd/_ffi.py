@@ -321,7 +321,7 @@ class Engine:
         rc = self._fn("ctx_create")(C.byref(desc), C.byref(self._ctx))
         if rc != HR_OK:
             self._ctx = C.c_void_p()
-            raise EngineError(f"{prefix}ctx_create failed with status {rc} (no usable HIP device?)")
+            raise EngineError(f"{prefix}ctx_create failed with status {rc} (no usable HIP device, a bad descriptor, or a malformed HR_TUNE: see stderr)")
         self.width = self.height = 0
 
     # -- plumbing

@@ -59,7 +59,7 @@ static int completeForSlowCaller(hr_ctx *c)
 {
     if (c->oldestWaitingNs == 0 || (c->pendingInject.empty() && occupiedSlots(c) == 0)) return HR_OK;
     const unsigned long long now = (unsigned long long)std::chrono::duration_cast<std::chrono::nanoseconds>(std::chrono::steady_clock::now().time_since_epoch()).count();
-    if (c->tuneSlowMs <= 0 || now - c->oldestWaitingNs <= 1000000ull * (unsigned long long)c->tuneSlowMs) return HR_OK; // (HR_TUNE slow=0: never, for tests of the lag itself)
+    if (c->tune.slow <= 0 || now - c->oldestWaitingNs <= 1000000ull * (unsigned long long)c->tune.slow) return HR_OK; // (HR_TUNE slow=0: never, for tests of the lag itself)
     for (int g = 0; g < c->nGroups; ++g) {
         const hipError_t q = hipStreamQuery(c->groups[g].stream);
         if (q == hipErrorNotReady) return HR_OK; // work in flight: the pipeline is being fed
@@ -259,9 +259,15 @@ int hr_ctx_create(const hr_ctx_desc *desc, hr_ctx **out)
 {
     if (!out) return HR_ERR_INVALID;
     *out = nullptr;
+    Tune tune; // (before any HIP call: a malformed HR_TUNE never touches the device)
+    std::string bad;
+    const char *text = getenv("HR_TUNE");
+    if (text && !parseTune(text, tune, bad)) return fprintf(stderr, "hr_ctx_create: HR_TUNE: %s\n", bad.c_str()), HR_ERR_INVALID;
+    tune.debugPipe = getenv("HR_DEBUG_PIPE") != nullptr, tune.debugStepTimes = getenv("HR_DEBUG_STEPTIMES") != nullptr;
     int nDev = 0;
     if (hipGetDeviceCount(&nDev) != hipSuccess || nDev <= 0) return HR_ERR_DEVICE;
     hr_ctx *c = new hr_ctx();
+    c->tune = tune, c->traceBlocks = tune.blocks;
     if (desc) {
         c->device = desc->device_id;
         c->rank = desc->rank;
@@ -282,22 +288,6 @@ int hr_ctx_create(const hr_ctx_desc *desc, hr_ctx **out)
         return HR_ERR_DEVICE;
     }
     c->numCUs = prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
-    if (const char *t = getenv("HR_TUNE")) {
-        auto find = [&](const char *key) -> const char * { // key at the start of the string or right after a comma
-            for (const char *p = strstr(t, key); p; p = strstr(p + 1, key))
-                if (p == t || p[-1] == ',') return p;
-            return nullptr;
-        };
-        auto get = [&](const char *key, int &dst) {
-            if (const char *p = find(key)) dst = atoi(p + strlen(key));
-        };
-        get("tri=", c->tuneTri), get("refill=", c->tuneRefill), get("blocks=", c->tuneBlocks), get("depth=", c->tuneDepth);
-        get("sblocks=", c->tuneShadeBlocks), get("batch=", c->tuneBatch), get("fmax=", c->tuneFetchMax), get("fmin=", c->tuneFetchMin);
-        get("groups=", c->tuneGroups), get("prio=", c->tunePrio), get("refit=", c->tuneRefit), get("sdeal=", c->tuneStaticDeal), get("guard=", c->tuneGuardPct), get("ploc=", c->tunePloc), get("packets=", c->tunePackets), get("corun=", c->tuneCorun), get("cmin=", c->tuneCorunMin), get("cblocks=", c->tuneCorunBlocks), get("plog=", c->tuneProbeLog2), get("pswz=", c->tunePacketSwizzle), get("pstep=", c->tunePacketStep), get("pstepf=", c->tunePacketStepF), get("pprobe=", c->tuneProbeStep), get("punion=", c->tunePacketUnion), get("plocr=", c->tunePlocRadius), get("fprim=", c->tuneFetchPrimary), get("fgate=", c->tuneFetchGate), get("heads=", c->tuneHeads), get("slow=", c->tuneSlowMs), get("ovf=", c->tuneOverflowTest), get("sprobe=", c->tuneShadowProbe), get("tblk=", c->tuneTableKernel);
-        c->tuneBlocksSet = find("blocks=") != nullptr;
-        if (c->tuneDepth < 1 || c->tuneDepth > kMaxSlots) c->tuneDepth = kMaxSlots;
-        if (c->tuneGroups < 0 || c->tuneGroups > kMaxGroups) c->tuneGroups = 0;
-    }
     // Memory the host READS WHILE A KERNEL THAT WRITES IT IS RUNNING (queue lengths, probe totals, the overflow report): coherent
     // (uncached on the device side, fine-grained) whatever HIP_HOST_COHERENT says — hipHostMallocDefault leaves that to the environment
     const unsigned kHostSpun = hipHostMallocCoherent | hipHostMallocMapped;
@@ -312,8 +302,8 @@ int hr_ctx_create(const hr_ctx_desc *desc, hr_ctx **out)
         {
             int least = 0, greatest = 0;
             groupsOk = groupsOk && hipDeviceGetStreamPriorityRange(&least, &greatest) == hipSuccess;
-            groupsOk = groupsOk && hipStreamCreateWithPriority(&G.stream, hipStreamNonBlocking, c->tunePrio ? greatest : 0) == hipSuccess;
-            groupsOk = groupsOk && hipStreamCreateWithPriority(&G.streamB, hipStreamNonBlocking, c->tunePrio ? greatest : 0) == hipSuccess &&
+            groupsOk = groupsOk && hipStreamCreateWithPriority(&G.stream, hipStreamNonBlocking, c->tune.prio ? greatest : 0) == hipSuccess;
+            groupsOk = groupsOk && hipStreamCreateWithPriority(&G.streamB, hipStreamNonBlocking, c->tune.prio ? greatest : 0) == hipSuccess &&
                        hipEventCreateWithFlags(&G.evFork, hipEventDisableTiming) == hipSuccess && hipEventCreateWithFlags(&G.evJoin, hipEventDisableTiming) == hipSuccess;
         }
         groupsOk = groupsOk && hipMalloc(&G.dTables, sizeof(StepTable) * kTableRing) == hipSuccess;
@@ -358,19 +348,11 @@ int hr_ctx_destroy(hr_ctx *c)
     if (!c) return HR_OK;
     if (c->grp) return groupDestroy(c);
     hipSetDevice(c->device);
-    if (getenv("HR_DEBUG_PIPE"))
+    if (c->tune.debugPipe)
         fprintf(stderr, "hr_ctx %p: ray-memory growths %llu (last sizes summed %.1f MiB); queue-length waits %llu, of which %llu had to spin, %.2f ms in total\n", (void *)c,
                 c->dbgGrowths, (double)c->dbgGrowBytes / 1048576.0, c->dbgWaits, c->dbgWaitSpun, (double)c->dbgWaitNs * 1e-6);
     drainPipeline(c);
     hipStreamSynchronize(c->stream);
-    if (c->dShadowProbe) {
-        unsigned long long t[4] = {0, 0, 0, 0};
-        hipDeviceSynchronize();
-        hipMemcpy(t, c->dShadowProbe, sizeof(t), hipMemcpyDeviceToHost);
-        fprintf(stderr, "shadow probe (%s): %llu occlusion rays in %llu packets of 64 consecutive queue entries: union factor U = %.3f, %.1f child boxes entered per ray\n",
-                c->tuneShadowProbe == 2 ? "every stage" : "first bounce", t[3], t[2], t[1] ? (double)t[0] / (double)t[1] : 0.0, t[3] ? (double)t[1] / (double)t[3] : 0.0);
-        hipFree(c->dShadowProbe);
-    }
     if (c->probeStream) hipStreamSynchronize(c->probeStream), hipStreamDestroy(c->probeStream);
     if (c->evProbeA) hipEventDestroy(c->evProbeA);
     if (c->evProbeB) hipEventDestroy(c->evProbeB);
@@ -631,14 +613,14 @@ int hr_frame_resize(hr_ctx *c, int32_t w, int32_t h)
         const long long own = c->queueCapacity ? c->queueCapacity : 1;
         long long b = (target + own - 1) / own;
         c->injectBatch = (int)(b < 1 ? 1 : (b > HR_BATCH_CAP ? HR_BATCH_CAP : b));
-        if (c->tuneBatch > 0) c->injectBatch = c->tuneBatch;
+        if (c->tune.batch > 0) c->injectBatch = c->tune.batch;
         // Two pipeline groups (their steps alternate on two streams, so one group's trace tail and its shade / raygen run
         // under the other group's trace) pay off only while a launch carries little work: +11..14 % on a 1080p frame at one pass
         // per step; with several passes per step one group (five trace workgroups per CU) is as fast or faster (1697 vs 1696
         // Mrays/s at 8 passes per step) and needs half the pass slots.
-        c->nGroups = c->tuneGroups > 0 ? c->tuneGroups : (c->injectBatch >= 4 || c->queueCapacity > 4200000u ? 1 : 2);
+        c->nGroups = c->tune.groups > 0 ? c->tune.groups : (c->injectBatch >= 4 || c->queueCapacity > 4200000u ? 1 : 2);
         c->nextGroup = 0;
-        if (!c->tuneBlocksSet) c->tuneBlocks = c->nGroups > 1 ? 3 : 5;
+        c->traceBlocks = c->tune.blocksSet ? c->tune.blocks : (c->nGroups > 1 ? 3 : 5);
         c->pendingInject.clear();
     }
     return HR_OK;

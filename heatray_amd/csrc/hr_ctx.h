@@ -4,6 +4,7 @@
 #pragma once
 #include "hr_kernels.h"
 #include "hr_trace.h"
+#include "hr_tune.h"
 
 #include <algorithm>
 #include <atomic>
@@ -53,8 +54,7 @@ struct Geom {
 
 struct GroupState; // hr_group.inl: what a context group owns beside its hr_ctx
 
-static const int kMaxGroups = 3;
-static const int kMaxSlots = 2 * kMaxSegs; // passes in flight over all groups
+static_assert(kMaxSlots == 2 * kMaxSegs, "hr_tune.h bounds depth= by the step table's size"); // (kMaxGroups, kMaxSlots: hr_tune.h)
 #ifndef HR_BATCH_CAP
 #define HR_BATCH_CAP 32 // most passes injected per macro step (small frames / tile shards reach it: 1/8 of a 1080p frame runs 6.6 % faster with 32 than with 12, profiles/r2p_shard_batch.txt)
 #endif
@@ -201,9 +201,7 @@ struct hr_ctx {
     };
     Group groups[kMaxGroups];
     int nGroups = 2;      // groups in use: chosen per frame size in hr_frame_resize unless HR_TUNE fixes it
-    int tuneGroups = 0;   // HR_TUNE="groups=N" (0 = automatic)
-    int tunePrio = 1;     // HR_TUNE="prio=0": worker streams at normal priority
-    int tuneBlocksSet = 0; // HR_TUNE="blocks=N" given
+    int traceBlocks = 5;  // k_trace's workgroups per CU: tune.blocks where HR_TUNE gives it, else chosen with nGroups
     int nextGroup = 0;
     unsigned long long nextResolveOrder = 0;
     unsigned long long resolvedAtClear = 0; // value of nextResolveOrder at the last hr_clear
@@ -229,10 +227,6 @@ struct hr_ctx {
     // seen so far (0: that stage has not been seen since the last resize / commit: it counts as long as it can possibly get)
     double stageArenaSeen[kMaxBounceSlots] = {0}, stageScratchSeen[kMaxBounceSlots] = {0};
     bool stageSeen[kMaxBounceSlots] = {false};
-    int tuneTableKernel = 1;  // HR_TUNE="tblk=0": the step table goes to the device by hipMemcpyAsync instead of a fetch kernel reading its pinned entry (0.2-0.7 % slower: profiles/r5k_table_fetch.txt)
-    int tuneShadowProbe = 0;  // HR_TUNE="sprobe=1|2" (measurement): walk the occlusion queues of the first bounce (1) / of every stage (2) as packets of 64 consecutive rays and print their union factor when the context goes
-    unsigned long long *dShadowProbe = nullptr;
-    int tuneOverflowTest = 0;          // HR_TUNE="ovf=1|2|3": TEST ONLY — halve one bound so that a queue overflows (1: camera rays, 2: a stage's closest-hit bound, 3: occlusion rays)
 
     // Mesh blocks come out of an arena of 64 MB chunks (bump allocation inside a chunk): a hipMalloc per submesh is a device-wide
     // synchronisation of ~0.1 ms each, which adds up for the scenes the reference loads (hundreds of submeshes).  A chunk whose last
@@ -306,7 +300,6 @@ struct hr_ctx {
     // change of transforms only (Scene::applyTransform while the user drags a slider) REFITS it — same topology, every box
     // recomputed bottom-up on the device, no allocation, one synchronisation at the end.
     bool topologyDirty = true, transformDirty = false;
-    int tuneRefit = 1;        // HR_TUNE="refit=0": always rebuild
     // pipeline diagnostics (HR_DEBUG_PIPE=1 prints them when the context is destroyed)
     unsigned long long dbgGrowths = 0, dbgGrowBytes = 0, dbgWaits = 0, dbgWaitNs = 0, dbgWaitSpun = 0;
     // ---- packet selector.  The camera rays of the passes injected together can be traced one ray per lane by k_trace, or 64 at a time as a
@@ -317,31 +310,21 @@ struct hr_ctx {
     // commit, a resize or a change of camera — a probe kernel on a side stream makes the camera rays of every 32nd group of pixels of
     // one injected pass and its companions itself and walks them as packets of the shape in use, writing nothing but
     //     U = (children the packet entered x its rays) / (children the rays' own box tests entered)
-    // and how many child boxes a ray enters.  Packets are used while U < punion / 100 (profiles/r4u_packets.txt).  The totals come back
-    // with the queue lengths k_trace reports (no synchronisation).  Either way the hits are the same bits.
-    int tunePackets = 2;   // HR_TUNE="packets=0|1|2": never / always / by the probe (default)
+    // and how many child boxes a ray enters.  Packets are used while U < tune.punion / 100 (profiles/r4u_packets.txt).  The totals come back
+    // with the queue lengths k_trace reports (no synchronisation).  Either way the hits are the same bits (tune.packets = 0 | 1 pins the mode).
     // The packet kernel is VALU-bound and leaves the texture addressers idle (busy 1.0 / 0.16); k_trace without the camera rays is the
     // other way round (0.70 / 0.94).  So a step's packet kernel runs BESIDE its k_trace, on a second stream (fork after the table copy,
     // join before the shading kernels), and k_trace leaves it room: 3 workgroups per CU instead of 5 when the camera rays are a good part
     // of the step's work, 4 when they are little (a step that injects few passes beside many in flight); c3 2100 -> 2390 Mrays/s at 128
     // passes, 2025 -> 2150 at 20 (profiles/r4v_corun.txt).
     // Only where k_trace IS bound by the addressers, i.e. where rays walk far: the probe also reports how many child boxes a camera ray
-    // enters (c3 76, c5 75, c3d 162: +8..13 %; c2 35: no difference; terrain 10, c1 5: k_trace is VALU-bound itself there and loses 6 %).
-    int tuneCorun = 1;       // HR_TUNE="corun=0|1|2": never (the packet kernel in front of k_trace on the group's stream) / by the probe / always
-    int tuneCorunMin = 50;   // HR_TUNE="cmin=N": beside k_trace when a probed camera ray enters at least N child boxes
-    int tunePacketSwizzle = 1; // HR_TUNE="pswz=0|1": k_raygen_packets deals whole 32x32 tiles to the XCDs (workgroup index -> XCD is round robin) instead of consecutive 16-pixel patches: a tile's part of the tree goes through ONE L2 (+0.3-0.7 % on c3 / c2 / c5, profiles/r5ak_packet_xcd.txt)
+    // enters (c3 76, c5 75, c3d 162: +8..13 %; c2 35: no difference; terrain 10, c1 5: k_trace is VALU-bound itself there and loses 6 %): tune.corun, tune.cmin.
     // The packet kernel tests a node's child boxes ONCE per packet against the packet's bounds (the interval step, hr_packet_interval.h,
     // DESIGN §2) instead of once per ray.  That walk enters a superset of the children; how much more is the scene's and the camera's:
     // the selector's probe walks both ways and reports F = children entered by the interval step / by the per-ray step (c3 1.05,
-    // c3d 1.02, c2 1.01: +3..7 %; terrain 1.2, its short walks mostly leaves, where every extra child is a triangle test: -3.7 %).
-    int tunePacketStep = 1;  // HR_TUNE="pstep=0|1": the per-ray step of rounds 4-5 / the interval step where F allows it (default)
-    int tunePacketStepF = 110; // HR_TUNE="pstepf=N": the interval step while F < N / 100 (0: whatever F is); no report yet: the interval step
+    // c3d 1.02, c2 1.01: +3..7 %; terrain 1.2, its short walks mostly leaves, where every extra child is a triangle test: -3.7 %): tune.pstep, tune.pstepf.
     double lastLooseness = 0.0; // F of the last probe (0: none has reported)
-    bool useIntervalStep() const { return tunePacketStep != 0 && (tunePacketStepF <= 0 || lastLooseness == 0.0 || lastLooseness * 100.0 < (double)tunePacketStepF); }
-    int tuneProbeStep = 0;   // HR_TUNE="pprobe=1" (measurement only): the probe's four totals come from a walk with the interval step, so packet_union is what that step enters; decisions are meant to be taken at 0
-    int tuneProbeLog2 = -1;  // HR_TUNE="plog=N" (measurement only): the selector's probe walks packets of 2^N passes x 64 >> N pixels instead of the shape in use
-    int tuneCorunBlocks = 0; // HR_TUNE="cblocks=N": fix k_trace's workgroups per CU in such a step (0: 3 or 4 by the step's mix)
-    int tunePacketUnion = 220; // HR_TUNE="punion=N": packets while U < N / 100 (measured break-even ~2.3: terrain at 1.97 +7..11 %, c5 at 2.07 +3..4 %)
+    bool useIntervalStep() const { return tune.pstep != 0 && (tune.pstepf <= 0 || lastLooseness == 0.0 || lastLooseness * 100.0 < (double)tune.pstepf); }
     bool packetsOn = false;
     uint32_t lastCameraCount = 0; // camera rays per pass behind the root cull, as last reported
     int probeCountdown = 0;              // injecting steps until the next probe
@@ -356,8 +339,6 @@ struct hr_ctx {
     hipStream_t probeStream = nullptr;   // the probe runs beside the pipeline: it makes its own camera rays and writes only the counters
     hipEvent_t evProbeA = nullptr, evProbeB = nullptr; // scene and tables as the group's stream sees them -> probe may start; probe done
     bool probeGuard = false;             // evProbeB has not been waited for yet (drainPipeline does: the scene may change afterwards)
-    int tunePloc = 1, tunePlocRadius = 16; // HR_TUNE="ploc=0|1|2,plocr=N": tree builder (hr_build.hip: buildLBVH keeps the cheaper of the radix tree and PLOC)
-    int tuneGuardPct = 125;   // HR_TUNE="guard=N": a refit whose boxes' area exceeds N % of the built tree's rebuilds instead (profiles/r3j_instanced_refit.txt)
     // persistent device arrays of the committed scene (grow-only capacities, reused across commits)
     GeomDev *dG = nullptr;
     size_t dGCap = 0;
@@ -457,8 +438,7 @@ struct hr_ctx {
     }
 
     float *fb() const { return fbExternal ? fbExternal : fbInternal; }
-    // tuning knobs (defaults measured on MI355X; HR_TUNE="tri=4,refill=8,blocks=6,depth=12,batch=2,groups=2" overrides for experiments)
-    int tuneTri = 2, tuneRefill = 16, tuneBlocks = 5, tuneShadeBlocks = 4, tuneDepth = kMaxSlots, tuneBatch = 0, tuneFetchMax = 64, tuneFetchMin = 64, tuneStaticDeal = 256, tuneFetchPrimary = 128, tuneFetchGate = 8, tuneHeads = 5, tuneSlowMs = 4;
+    Tune tune; // the HR_TUNE knobs (hr_tune.h), parsed by hr_ctx_create and never written afterwards
     // AOVs (include/hrcore_aov.h): the frame's planes, summed by k_resolve_aov in pass order beside the frame.  With HR_AOV_SURFACE every
     // pass slot also holds the pass's AOV record (PassSlot::aov) and the shading kernel variant with MODE & 4 writes it.
     uint32_t aovMask = 0;
@@ -505,7 +485,7 @@ struct hr_ctx {
     GroupState *grp = nullptr;
     LaunchCfg cfg(hipStream_t st) const
     {
-        return LaunchCfg{st, numCUs, tuneBlocks, tuneShadeBlocks, collectStats, textureLodUsed, allLightsUsed, hasGlass, tunePacketSwizzle, useIntervalStep() ? 1 : 0, (aovMask & HR_AOV_SURFACE) != 0};
+        return LaunchCfg{st, numCUs, traceBlocks, tune.sblocks, collectStats, textureLodUsed, allLightsUsed, hasGlass, tune.pswz, useIntervalStep() ? 1 : 0, (aovMask & HR_AOV_SURFACE) != 0};
     }
 };
 

@@ -9,9 +9,8 @@
 //
 // Process-wide mutable state of the library, audited before members ran concurrently: the device counters of k_trace's tail profile
 // (g_tailprof, HR_TAILPROF builds only — members on one device add into the same counters, so such a measurement is of the device, not
-// of a member); the HR_DEBUG_STEPTIMES flag of macroStep (a function-local static const: initialised once, thread-safe, read-only
-// afterwards); getenv reads at context creation and in diagnostics (nothing in the library sets the environment).  Everything else
-// lives in the hr_ctx.
+// of a member); getenv reads at context creation only (HR_TUNE and the HR_DEBUG_* flags go into the member's own hr_ctx::tune; nothing
+// in the library sets the environment).  Everything else lives in the hr_ctx.
 //
 // Devices and ordering.  Members never wait on one another on the device.  Assembly: each member packs its owned pixels on its own stream
 // (hr_frame_pack_owned: after the resolves enqueued so far, before the next one), a member on another device copies the packed bytes to a

@@ -175,8 +175,6 @@ void launchRaygenPackets(const LaunchCfg &cfg, const SceneDev *S, const Node4 *n
                          const FrameDev &fr, Stats *stats, bool uniformParams); // segs.n: a power of two; uniformParams: the passes differ in sample_index only
 int launchPacketProbe(hipStream_t stream, const SceneDev *S, const Node4 *nodes, const Tri *tris, const hr_pass_params &pp, int passesLog2, const FrameDev &fr,
                       unsigned long long *probe, bool intervalStep);
-void launchShadowProbe(hipStream_t stream, const SceneDev *S, const Node4 *nodes, const Tri *tris, const StepTable *tbl, const SegList &segs, uint32_t maxRays,
-                       unsigned long long *probe); // measurement only (HR_TUNE sprobe=)
 
 // ---- hr_trace.hip
 void launchTrace(const LaunchCfg &cfg, const SceneDev *S, const int *leafKeys, const Node32 *nodes32, const Tri *tris, StepTable *tbl, Stats *stats);

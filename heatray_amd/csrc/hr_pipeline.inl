@@ -20,7 +20,7 @@ int hr_clear(hr_ctx *c)
     c->hsMerged = false;     // (include/hrcore_history.h: ... and may take over a captured history once)
     c->rpMerged = false, c->rpStale = true; // (include/hrcore_reproject.h: ... or progressively: no pixel of the new frame has been examined)
     c->snapshotEpoch++;
-    if (getenv("HR_DEBUG_PIPE")) fprintf(stderr, "hr_clear %p: ray-memory growths so far %llu, waits %llu (%.2f ms)\n", (void *)c, c->dbgGrowths, c->dbgWaits, (double)c->dbgWaitNs * 1e-6);
+    if (c->tune.debugPipe) fprintf(stderr, "hr_clear %p: ray-memory growths so far %llu, waits %llu (%.2f ms)\n", (void *)c, c->dbgGrowths, c->dbgWaits, (double)c->dbgWaitNs * 1e-6);
     c->drainTimes();
     for (int k = 0; k < HR_KERNEL_COUNT; ++k) c->kernelMs[k] = 0.0f, c->kernelLaunches[k] = 0;
     return HR_OK;
@@ -80,7 +80,7 @@ static int ensureRegion(hr_ctx *c, hr_ctx::Group &G, hr_ctx::Group::Region &r, s
 {
     if (need <= r.cap) return HR_OK;
     c->dbgGrowths++, c->dbgGrowBytes += need;
-    if (getenv("HR_DEBUG_PIPE")) fprintf(stderr, "  grow %s: need %.1f MiB, had %.1f MiB (step %llu)\n", what, (double)need / 1048576.0, (double)r.cap / 1048576.0, G.stepCounter);
+    if (c->tune.debugPipe) fprintf(stderr, "  grow %s: need %.1f MiB, had %.1f MiB (step %llu)\n", what, (double)need / 1048576.0, (double)r.cap / 1048576.0, G.stepCounter);
     HIP_TRY(c, hipStreamSynchronize(G.stream));
     const size_t hadCap = r.cap;
     hipFree(r.base);
@@ -210,7 +210,7 @@ static int packetLog2(const hr_ctx *c);
 static bool packetsInUse(const hr_ctx *c);
 static int macroStep(hr_ctx *c, int g, int nInject)
 {
-    static const bool dbgT = getenv("HR_DEBUG_STEPTIMES") != nullptr;
+    const bool dbgT = c->tune.debugStepTimes;
     auto nowUs = [] { return (double)std::chrono::duration_cast<std::chrono::nanoseconds>(std::chrono::steady_clock::now().time_since_epoch()).count() * 1e-3; };
     const double tA = dbgT ? nowUs() : 0.0;
     double tB = 0, tC = 0, tD = 0, tE = 0;
@@ -310,7 +310,7 @@ static int macroStep(hr_ctx *c, int g, int nInject)
     const int ring = (int)(stepIdx % kTableRing);
     if (G.tableUsed[ring]) HIP_TRY(c, hipEventSynchronize(G.tableCopied[ring])); // staging entry free again (4 steps old)
     // ---- ray memory of this step (Group::arena): every queue sized by an upper bound of what can arrive in it
-    const uint32_t P = c->tuneOverflowTest == 1 ? c->queueCapacity / 8u + 1u : (c->queueCapacity ? c->queueCapacity : 1u); // (ovf=1, TEST ONLY: camera rays do not fit)
+    const uint32_t P = c->tune.ovf == 1 ? c->queueCapacity / 8u + 1u : (c->queueCapacity ? c->queueCapacity : 1u); // (ovf=1, TEST ONLY: camera rays do not fit)
     const size_t kS = c->allLightsUsed ? 4 : 1;
     uint32_t boundIn[kMaxSegs];
     {
@@ -329,10 +329,10 @@ static int macroStep(hr_ctx *c, int g, int nInject)
                     if (dPk > 0) c->lastLooseness = (double)dIv / (double)dPk; // F: children entered, interval step / per-ray step
                     if (dRy > 0) {
                         c->lastUnion = (double)dPk / (double)dRy;
-                        c->packetsOn = c->lastUnion * 100.0 < (double)c->tunePacketUnion;
+                        c->packetsOn = c->lastUnion * 100.0 < (double)c->tune.punion;
                         c->lastOwnPerRay = dNr ? (double)dRy / (double)dNr : 0.0;
                     }
-                    if (getenv("HR_DEBUG_PIPE")) fprintf(stderr, "packet probe of step %llu (seen at step %llu): union %.3f, %.1f child boxes entered per ray -> packets %s; interval step F %.3f -> %s\n", c->probeStep, stepIdx, c->lastUnion, c->lastOwnPerRay, c->packetsOn ? "on" : "off", c->lastLooseness, c->useIntervalStep() ? "on" : "off");
+                    if (c->tune.debugPipe) fprintf(stderr, "packet probe of step %llu (seen at step %llu): union %.3f, %.1f child boxes entered per ray -> packets %s; interval step F %.3f -> %s\n", c->probeStep, stepIdx, c->lastUnion, c->lastOwnPerRay, c->packetsOn ? "on" : "off", c->lastLooseness, c->useIntervalStep() ? "on" : "off");
                 }
             }
             for (int i = 0; i < kMaxSlots; ++i) idxOfSlot[i] = -1;
@@ -351,7 +351,7 @@ static int macroStep(hr_ctx *c, int g, int nInject)
                 }
             }
             // TEST ONLY (HR_TUNE="ovf=": tests/test_gpu_parity.py forces every kind of overflow once): half of what the bound should be
-            if (c->tuneOverflowTest == 2 && ps.step == 1) b = b / 2u + 1u;
+            if (c->tune.ovf == 2 && ps.step == 1) b = b / 2u + 1u;
             boundIn[k] = b;
         }
     }
@@ -411,12 +411,12 @@ static int macroStep(hr_ctx *c, int g, int nInject)
     StepTable &tbl = G.hTables[ring];
     std::memset(tbl.heads, 0, sizeof(tbl.heads));
     std::memset(tbl.clkStart, 0xFF, sizeof(tbl.clkStart)), std::memset(tbl.clkEnd, 0, sizeof(tbl.clkEnd));
-    tbl.headsLog2 = (uint32_t)(c->tuneHeads < 0 ? 0 : (c->tuneHeads > 6 ? 6 : c->tuneHeads));
+    tbl.headsLog2 = (uint32_t)c->tune.heads;
     tbl.nSeg = n;
-    tbl.refillLanes = c->tuneRefill, tbl.triPhaseLanes = c->tuneTri;
-    tbl.fetchMax = c->tuneFetchMax > 0 ? c->tuneFetchMax : 1, tbl.fetchMin = c->tuneFetchMin > 0 ? c->tuneFetchMin : 1;
-    tbl.staticPerWave = c->tuneStaticDeal, tbl.hasGlass = c->hasGlass ? 1 : 0;
-    tbl.primaryFromSeg = n, tbl.fetchMaxPrimary = ((c->tuneFetchPrimary > 0 ? c->tuneFetchPrimary : 1) & 0xFFFF) | ((c->tuneFetchGate & 0xFFFF) << 16); // (primaryFromSeg is set below, once the injected passes' places in the table are known)
+    tbl.refillLanes = c->tune.refill, tbl.triPhaseLanes = c->tune.tri;
+    tbl.fetchMax = c->tune.fmax, tbl.fetchMin = c->tune.fmin;
+    tbl.staticPerWave = c->tune.sdeal, tbl.hasGlass = c->hasGlass ? 1 : 0;
+    tbl.primaryFromSeg = n, tbl.fetchMaxPrimary = (c->tune.fprim & 0xFFFF) | ((c->tune.fgate & 0xFFFF) << 16); // (primaryFromSeg is set below, once the injected passes' places in the table are known)
     int injectedSegs[kMaxSegs];
     int nInjectedSegs = 0;
     for (int k = 0; k < n; ++k) {
@@ -435,7 +435,7 @@ static int macroStep(hr_ctx *c, int g, int nInject)
             sg.sqOut = carveShadowQueue(pArena, (size_t)boundIn[k] * kS);
             ps.qcur = sg.qout, ps.scur = sg.sqOut, ps.capCur = boundIn[k];
             sg.sOutCap = (uint32_t)((size_t)boundIn[k] * kS);
-            if (c->tuneOverflowTest == 3 && st == 0) sg.sOutCap = sg.sOutCap / 8u + 1u; // TEST ONLY: the first hits' occlusion rays do not fit
+            if (c->tune.ovf == 3 && st == 0) sg.sOutCap = sg.sOutCap / 8u + 1u; // TEST ONLY: the first hits' occlusion rays do not fit
             ps.sCapCur = sg.sOutCap;
         }
         sg.passbuf = ps.passbuf;
@@ -469,7 +469,7 @@ static int macroStep(hr_ctx *c, int g, int nInject)
     // packet selector (above): do the injected passes' camera rays travel as packets (k_raygen_packets), beside k_trace or in front of it, and does this step carry a probe?
     int probeSeg = -1;
     bool packetsNow = packetsInUse(c) && nInjectedSegs > 0 && tbl.seg[injectedSegs[0]].pp.interactive_mode == 0; // (interactive sub-passes of one sample share no pixels)
-    if (c->tunePackets == 2 && g == 0 && nInjectedSegs > 0 && !c->probePending && tbl.seg[injectedSegs[0]].pp.interactive_mode == 0) {
+    if (c->tune.packets == 2 && g == 0 && nInjectedSegs > 0 && !c->probePending && tbl.seg[injectedSegs[0]].pp.interactive_mode == 0) {
         const hr_pass_params &pp = tbl.seg[injectedSegs[0]].pp;
         float cam[21] = {pp.fov_tan, pp.aspect_ratio, pp.focus_distance, pp.aperture_radius};
         std::memcpy(cam + 4, pp.view_matrix, sizeof(pp.view_matrix));
@@ -483,7 +483,7 @@ static int macroStep(hr_ctx *c, int g, int nInject)
             c->probeCountdown--;
         }
     }
-    const bool corunNow = packetsNow && (c->tuneCorun == 2 || (c->tuneCorun == 1 && c->lastOwnPerRay >= (double)c->tuneCorunMin));
+    const bool corunNow = packetsNow && (c->tune.corun == 2 || (c->tune.corun == 1 && c->lastOwnPerRay >= (double)c->tune.cmin));
     for (int j = 0; j < nInjectedSegs; ++j)
         if (packetsNow) tbl.seg[injectedSegs[j]].packets = corunNow ? 2 : 1;
     tbl.hostCameraCount = corunNow ? G.dCounts + (size_t)kTableRing * kMaxSegs : nullptr;
@@ -495,10 +495,7 @@ static int macroStep(hr_ctx *c, int g, int nInject)
     StepTable *dTbl = G.dTables + ring;
     const size_t tblBytes = offsetof(StepTable, seg) + (size_t)n * sizeof(SegDev);
     if (dbgT) tD = nowUs();
-    if (c->tuneTableKernel)
-        launchFetchTable(G.stream, G.dTablesHost + ring, dTbl, (tblBytes + 15) & ~(size_t)15);
-    else
-        HIP_TRY(c, hipMemcpyAsync(dTbl, &tbl, tblBytes, hipMemcpyHostToDevice, G.stream));
+    launchFetchTable(G.stream, G.dTablesHost + ring, dTbl, (tblBytes + 15) & ~(size_t)15);
     if (dbgT) tE = nowUs();
     HIP_TRY(c, hipEventRecord(G.tableCopied[ring], G.stream));
     G.tableUsed[ring] = true;
@@ -546,19 +543,6 @@ static int macroStep(hr_ctx *c, int g, int nInject)
         else
             launchRaygen(cfg, c->dScene, dTbl, segs, fr, c->dStats);
     }
-    if (c->tuneShadowProbe) { // measurement only: the coherence of the occlusion rays this step's k_trace is about to trace
-        if (!c->dShadowProbe) {
-            HIP_TRY(c, hipMalloc(&c->dShadowProbe, 64));
-            HIP_TRY(c, hipMemsetAsync(c->dShadowProbe, 0, 64, G.stream));
-        }
-        SegList sl{};
-        uint32_t most = 0;
-        for (int k = 0; k < n; ++k) {
-            const hr_ctx::PassSlot &ps = c->slots[order[k]];
-            if (ps.step >= 1 && (c->tuneShadowProbe == 2 || ps.step == 1) && sl.n < kMaxBatch) sl.seg[sl.n++] = k, most = tbl.seg[k].sInCap > most ? tbl.seg[k].sInCap : most;
-        }
-        launchShadowProbe(G.stream, c->dScene, c->nodes, c->tris, dTbl, sl, most, c->dShadowProbe);
-    }
     if (forked) HIP_TRY(c, hipEventRecord(G.evJoin, G.streamB));
     if (timing)
         c->timeNext(HR_KERNEL_TRACE, G.stream);
@@ -568,7 +552,7 @@ static int macroStep(hr_ctx *c, int g, int nInject)
         // (probeSeen holds the totals of the report the previous decision was taken on: probes never overlap, that probe was complete)
         HIP_TRY(c, hipEventRecord(c->evProbeA, G.stream));
         HIP_TRY(c, hipStreamWaitEvent(c->probeStream, c->evProbeA, 0));
-        c->probeWaves = (unsigned long long)launchPacketProbe(c->probeStream, c->dScene, c->nodes, c->tris, tbl.seg[probeSeg].pp, c->tuneProbeLog2 >= 0 ? c->tuneProbeLog2 : packetLog2(c), fr, c->dProbe, c->tuneProbeStep != 0);
+        c->probeWaves = (unsigned long long)launchPacketProbe(c->probeStream, c->dScene, c->nodes, c->tris, tbl.seg[probeSeg].pp, c->tune.plog >= 0 ? c->tune.plog : packetLog2(c), fr, c->dProbe, c->tune.pprobe != 0);
         HIP_TRY(c, hipEventRecord(c->evProbeB, c->probeStream));
         c->probeGuard = true, c->probePending = true, c->probeStep = stepIdx, c->probeCountdown = kProbeEvery;
     }
@@ -584,7 +568,7 @@ static int macroStep(hr_ctx *c, int g, int nInject)
             if (late) c->lastCameraCount = late;
             const double cam = (double)nInjectedSegs * (double)(c->lastCameraCount ? c->lastCameraCount : P / 2u);
             int blocks = cam > 0.2 * others ? 3 : 4;
-            if (c->tuneCorunBlocks > 0) blocks = c->tuneCorunBlocks;
+            if (c->tune.cblocks > 0) blocks = c->tune.cblocks;
             if (blocks < ct.traceBlocksPerCU) ct.traceBlocksPerCU = blocks;
         }
         launchTrace(ct, c->dScene, c->tree.leafKeys, c->tree.nodes32, c->tris, dTbl, c->dStats);
@@ -637,11 +621,7 @@ static int stepOldest(hr_ctx *c)
     return macroStep(c, oldest->group, 0);
 }
 
-static int slotLimit(const hr_ctx *c)
-{
-    int limit = c->maxSlots < c->tuneDepth ? c->maxSlots : c->tuneDepth; // passes in flight, all groups
-    return limit < 1 ? 1 : (limit > kMaxSlots ? kMaxSlots : limit);
-}
+static int slotLimit(const hr_ctx *c) { return c->maxSlots < c->tune.depth ? c->maxSlots : c->tune.depth; } // passes in flight, all groups (both within 1..kMaxSlots)
 
 // Inject n pending passes into the next group (round robin), first making room for them.
 static int injectBatch(hr_ctx *c, int n, int perGroupLimit)
@@ -672,7 +652,7 @@ static int packetLog2(const hr_ctx *c)
     while ((2 << k) <= packetBatch(c) && k < 4) ++k;
     return k;
 }
-static bool packetsInUse(const hr_ctx *c) { return c->tunePackets == 1 || (c->tunePackets == 2 && c->packetsOn); }
+static bool packetsInUse(const hr_ctx *c) { return c->tune.packets == 1 || (c->tune.packets == 2 && c->packetsOn); }
 
 // hr_ctx_desc::memory_budget: how many passes per step fit.  A pass of the batch holds, over the `stages` steps of its life, a pass buffer
 // (S + 2 of them per batch pass are kept: the pipeline's depth and the resolve lag), its camera rays and hit records (scratch), and

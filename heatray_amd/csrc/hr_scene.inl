@@ -270,7 +270,7 @@ static int sceneKey(hr_ctx *c, unsigned long long *key)
     hipFree(dKey);
     HIP_TRY(c, e);
     // (which tree a build produces also depends on the builder options: a file made with other ones is another scene's as far as the cache goes)
-    mix(&c->tunePloc, sizeof(c->tunePloc)), mix(&c->tunePlocRadius, sizeof(c->tunePlocRadius));
+    mix(&c->tune.ploc, sizeof(c->tune.ploc)), mix(&c->tune.plocr, sizeof(c->tune.plocr));
     *key = host ^ (dev * 0x9E3779B97F4A7C15ull);
     return HR_OK;
 }
@@ -406,7 +406,7 @@ int hr_scene_commit(hr_ctx *c)
         // A commit after transform edits only keeps the tree's topology: triangles are re-assembled straight into their leaf
         // slots and every level is refitted bottom-up.  No allocation, no host round trip before the last kernel.
         bool cacheHit = false;
-        bool refit = c->tuneRefit && !c->topologyDirty && c->tree.nodes && c->treeTris == nTris && c->tree.rootLeafCount == 0;
+        bool refit = c->tune.refit && !c->topologyDirty && c->tree.nodes && c->treeTris == nTris && c->tree.rootLeafCount == 0;
         if (refit) {
             launchAssemble(c->stream, c->dG, (int)gd.size(), nTris, c->tree.tris, c->tree.slotOfPrim, c->attrs, ext, c->dScratch);
             launchSceneConsts(c->stream, c->dScratch, c->dConsts, nullptr);
@@ -424,7 +424,7 @@ int hr_scene_commit(hr_ctx *c)
             // object grows the diagonal too, so that guard never fired.)  A rebuild of 1 M triangles costs 4.7 ms, a refit 0.3 ms.
             const SceneConsts &k = *c->hConsts;
             const float nowQ = k.triAreaSum > 0.0f ? k.areaSum / k.triAreaSum : 0.0f;
-            if (c->builtAreaSum > 0.0f && nowQ > 0.01f * (float)c->tuneGuardPct * c->builtAreaSum) refit = false;
+            if (c->builtAreaSum > 0.0f && nowQ > 0.01f * (float)c->tune.guard * c->builtAreaSum) refit = false;
         }
         if (!refit) {
             rc = ensureCap(c, &c->trisPrim, &c->trisPrimCap, (size_t)nTris);
@@ -446,7 +446,7 @@ int hr_scene_commit(hr_ctx *c)
                 launchSceneConsts(c->stream, c->dScratch, c->dConsts, nullptr);
                 cacheHit = true;
             } else {
-                const BuildOptions bo{c->tunePloc, c->tunePlocRadius, (kStackLDS + kStackOvf) / 3};
+                const BuildOptions bo{c->tune.ploc, c->tune.plocr, (kStackLDS + kStackOvf) / 3};
                 const int brc = buildLBVH(c->stream, c->trisPrim, nTris, k.lo, k.hi, k.pad, c->dConsts, &cs.br, bo);
                 if (brc != 0) FAIL(c, HR_ERR_DEVICE, brc == 3 ? "LBVH refit did not reach the root" : "LBVH build failed");
                 if (!c->cachePath.empty()) saveTree(c, key, nTris, cs.br);

@@ -76,7 +76,8 @@ typedef struct hr_ctx_desc {
 #define HR_CTX_COLLECT_STATS 1u /* count node visits / triangle tests per pass (slower) */
 #define HR_CTX_TIME_KERNELS 2u  /* bracket every kernel launch with HIP events (hr_get_kernel_times) */
 
-/* replaces OpenRLCreateContext / OpenRLSetCurrentContext (PassGenerator.cpp:164-165) */
+/* replaces OpenRLCreateContext / OpenRLSetCurrentContext (PassGenerator.cpp:164-165).  A malformed HR_TUNE in the environment (an unknown
+ * key, a value that is no integer or outside its knob's range: heatray_amd/csrc/hr_tune.h) is HR_ERR_INVALID, with one line on stderr. */
 int hr_ctx_create(const hr_ctx_desc *desc, hr_ctx **out);
 /* replaces OpenRLDestroyContext (PassGenerator.cpp:432) */
 int hr_ctx_destroy(hr_ctx *ctx);

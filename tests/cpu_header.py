@@ -6,11 +6,11 @@ import subprocess
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
-def build(name, tmp_dir):
-    """tests/host/NAME_cpu.cpp compiled into tmp_dir; returns the program's path"""
+def build(name, tmp_dir, flags=()):
+    """tests/host/NAME_cpu.cpp compiled into tmp_dir (with further compiler flags, e.g. a sanitizer's); returns the program's path"""
     exe = tmp_dir / (name + "_cpu")
     # -ffp-contract=off like the library: the header's float lines must mean the same on both sides
-    subprocess.check_call(["g++", "-std=c++17", "-O1", "-ffp-contract=off", "-Wall", "-I" + os.path.join(ROOT, "heatray_amd", "csrc"),
+    subprocess.check_call(["g++", "-std=c++17", "-O1", "-ffp-contract=off", "-Wall", *flags, "-I" + os.path.join(ROOT, "heatray_amd", "csrc"),
                            os.path.join(ROOT, "tests", "host", name + "_cpu.cpp"), "-o", str(exe)])
     return exe
 
