@@ -276,6 +276,17 @@ class ReprojectPreviewResult(C.Structure):
         return {k: getattr(self, k) for k, _ in self._fields_}
 
 
+# every symbol include/hrcore_tree.h declares (what the last tree build did to the radix tree's bottom subtrees)
+HR_TREE_API_VERSION = 1
+TREE_SYMBOLS = ["tree_api_version", "scene_get_tree_info"]
+
+
+class TreeInfo(C.Structure):
+    """hr_tree_info"""
+    _fields_ = [("cost_before", C.c_float), ("cost_after", C.c_float), ("subtrees_found", C.c_uint32), ("subtrees_replaced", C.c_uint32),
+                ("max_triangles", C.c_uint32), ("reserved", C.c_uint32 * 3)]
+
+
 # The optional headers: feature -> (its symbols, the version the binding was written against, what "this library has no ..." calls it);
 # the version function is <feature>_api_version.  Engine._feature_call checks a feature on its first call
 FEATURES = {
@@ -285,6 +296,7 @@ FEATURES = {
     "adaptive": (ADAPTIVE_SYMBOLS, HR_ADAPTIVE_API_VERSION, "adaptive sampling"),
     "history": (HISTORY_SYMBOLS, HR_HISTORY_API_VERSION, "history reprojection"),
     "reproject": (REPROJECT_SYMBOLS, HR_REPROJECT_API_VERSION, "progressive history merge"),
+    "tree": (TREE_SYMBOLS, HR_TREE_API_VERSION, "tree build report"),
 }
 
 
@@ -444,6 +456,12 @@ class Engine:
         s = SceneInfo()
         self._call("scene_get_info", C.byref(s))
         return s
+
+    def tree_info(self):
+        """hr_tree_info of the last commit that built the tree (include/hrcore_tree.h)"""
+        t = TreeInfo()
+        self._feature_call("tree", "scene_get_tree_info", C.byref(t))
+        return t
 
     # -- textures / materials / lights
     def create_texture(self, pixels, wrap=HR_WRAP_REPEAT, filter=HR_FILTER_LINEAR):

@@ -327,6 +327,7 @@ HRD int deltaKey(const uint32_t *keys, int n, int i, int j)
 #ifndef HR_ROTATE_SWEEPS
 #define HR_ROTATE_SWEEPS 0 // tree-rotation sweeps over the binary tree before the collapse (experiment knob)
 #endif
+#include "hr_sah_subtree.h"
 struct KNode {
     int left, right; // >= 0: internal node, < 0: leaf ~index
     int first, last; // covered range of sorted triangles
@@ -797,6 +798,95 @@ void launchTriAreaSum(hipStream_t st, const Tri *leafTris, uint32_t nSlots, Scen
     if (nSlots) hipLaunchKernelGGL(k_tri_area_sum, dim3((nSlots + 255) / 256), dim3(256), 0, st, leafTris, nSlots, consts);
 }
 
+// ------------------------------------------------------------------------------- SAH subtrees
+// The radix tree splits by Morton prefix, blind to the boxes.  Its bottom subtrees (at most T <= 64 triangles under a node of more) are
+// rebuilt top-down by full-sweep SAH, one wave per subtree with a triangle per lane (hr_sah_subtree.h has the arithmetic and the CPU
+// test), into the node slots the radix subtree owned.  The leaves keep their names (~sorted index): leafBox, the sorted triangles and
+// with them PLOC's input stay as they are.  The rebuild runs AFTER the first bottom-up refit: a subtree's collapse cost C1 and its
+// height (its stamp) are then known, the scene's cost before the rebuild can be reported, and the sweep's version is kept only where
+// its C1 is lower and it is not deeper — the scene's cost never rises and the radix tree's 58-level bound holds.  The nodes above the
+// subtrees are then refitted once more (k_sah_find clears their stamps).  tools/tree_proto.py: -5.1 % summed node area on the soup.
+struct SahWork {
+    int child, parent, side; // the subtree's root, the node above it, 0 / 1: it is the parent's left / right child
+};
+
+// one thread per radix node of more than T triangles: its stamp is cleared, its inner children of 3..T triangles are work items
+__global__ __launch_bounds__(256) void k_sah_find(const KNode *__restrict__ nodes, int nInternal, int T, uint32_t *__restrict__ stamp,
+                                                  SahWork *__restrict__ work, uint32_t maxWork, uint32_t *__restrict__ counters)
+{
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= nInternal) return;
+    const KNode k = nodes[i];
+    if (k.last - k.first + 1 <= T) return;
+    stamp[i] = 0u;
+    for (int side = 0; side < 2; ++side) {
+        const int ch = side ? k.right : k.left;
+        if (ch < 0) continue;
+        const int m = nodes[ch].last - nodes[ch].first + 1;
+        if (m > T || m < 3) continue;
+        const uint32_t at = atomicAdd(counters, 1u);
+        if (at < maxWork) work[at] = SahWork{ch, i, side}; // (always: the items' triangles are disjoint and each has three)
+    }
+}
+
+__global__ __launch_bounds__(64) void k_sah_subtrees(KNode *__restrict__ nodes, const Box6 *__restrict__ leafBox, Box6 *__restrict__ nodeBox,
+                                                     float4 *__restrict__ cost, uint32_t *__restrict__ stamp, const SahWork *__restrict__ work,
+                                                     uint32_t *__restrict__ counters)
+{
+    __shared__ SahSub s;
+    const SahWork item = work[blockIdx.x];
+    const int lane = (int)threadIdx.x;
+    const int first = nodes[item.child].first, last = nodes[item.child].last;
+    const int m = last - first + 1; // 3 .. 64 (k_sah_find)
+    const int radixDepth = (int)stamp[item.child]; // (the round of the refit that finished it = its height)
+    const float radixC1 = cost[item.child].x;
+    if (lane == 0) s.m = m;
+    if (lane < m) {
+        const Box6 b = leafBox[first + lane];
+        for (int q = 0; q < 3; ++q) s.lo[q][lane] = b.lo[q], s.hi[q][lane] = b.hi[q];
+    }
+    __syncthreads();
+    sahInit(s, lane);
+    __syncthreads();
+    int levels = 0;
+    for (;;) {
+        sahCandidate(s, lane, levels & 1);
+        __syncthreads();
+        const bool more = sahPartition(s, lane, levels & 1, levels);
+        ++levels;
+        if (!__syncthreads_or(more ? 1 : 0)) break;
+        if (levels >= radixDepth) return; // deeper than the radix subtree: that one stays (uniform: both values are the wave's)
+    }
+    for (int lv = levels - 1; lv >= 0; --lv) {
+        sahEvaluate(s, lane, lv);
+        __syncthreads();
+    }
+    if (!sahKeep(s.cost[0].c1, levels, radixC1, radixDepth)) return;
+    const int base = sahOwnedBase(first, last, item.child);
+    if (lane < m - 1) {
+        const int l = s.left[lane], r = s.right[lane];
+        KNode k;
+        k.left = l < 0 ? ~(first + ~l) : base + l, k.right = r < 0 ? ~(first + ~r) : base + r;
+        k.first = 0, k.last = 0; // (as PLOC's nodes: nothing reads a range after k_sah_find)
+        Box6 b;
+        for (int q = 0; q < 3; ++q) b.lo[q] = s.nlo[q][lane], b.hi[q] = s.nhi[q][lane];
+        const SahCost c = s.cost[lane];
+        nodes[base + lane] = k;
+        nodeBox[base + lane] = b;
+        cost[base + lane] = make_float4(c.c1, c.c2, c.c3, c.c4);
+        stamp[base + lane] = 1u; // finished before every round of the refit that follows
+    }
+    if (lane == 0) {
+        if (base != item.child) { // the root moved to the first owned slot: the parent's link follows
+            if (item.side)
+                nodes[item.parent].right = base;
+            else
+                nodes[item.parent].left = base;
+        }
+        atomicAdd(counters + 1, 1u);
+    }
+}
+
 // ------------------------------------------------------------------------------------------- PLOC
 // Parallel locally-ordered clustering (Meister & Bittner 2018) over the Morton-ordered triangle boxes: in every iteration each cluster
 // looks for its nearest neighbour (smallest surface area of the merged box) among the r clusters before and behind it in the array,
@@ -1095,6 +1185,7 @@ int buildLBVH(hipStream_t st, const Tri *trisPrim, uint32_t n, const float lo[3]
     out->nodes = nullptr, out->nodes32 = nullptr, out->leafKeys = nullptr, out->tris = nullptr, out->nodeBox = nullptr, out->slotOfPrim = nullptr;
     out->nNodes = 0, out->rootLeafCount = 0, out->levels = 0, out->triSlots = 0;
     out->builder = 0, out->costRadix = out->costPloc = 0.0f;
+    out->sahCostBefore = out->sahCostAfter = 0.0f, out->sahFound = out->sahReplaced = 0u;
     for (uint32_t &v : out->levelStart) v = 0;
     if (n == 0) return 0;
     if (n >= (1u << 28)) return 2;
@@ -1176,6 +1267,49 @@ int buildLBVH(hipStream_t st, const Tri *trisPrim, uint32_t n, const float lo[3]
             if (rootStamp == 0) rc = 3;
         }
 #endif
+        // ---- the radix tree's bottom subtrees rebuilt by full-sweep SAH (k_sah_subtrees), then the nodes above them refitted again
+        const int sahT = opt.sahSub > kSahMax ? kSahMax : opt.sahSub;
+        if (rc == 0 && dpCost && sahT >= 3 && n > (uint32_t)sahT) {
+            const uint32_t maxWork = n / 3u + 1u;
+            SahWork *work = nullptr;
+            uint32_t *counters = nullptr; // [0] subtrees found, [1] replaced
+            float4 c0{};
+            Box6 rootBox{};
+            uint32_t found[2] = {0u, 0u};
+            bool ok = hipMalloc(&work, sizeof(SahWork) * (size_t)maxWork) == hipSuccess && hipMalloc(&counters, 8) == hipSuccess &&
+                      hipMemsetAsync(counters, 0, 8, st) == hipSuccess;
+            if (ok) {
+                hipLaunchKernelGGL(k_sah_find, dim3(gi), dim3(256), 0, st, knodes, nInternal, sahT, stamp, work, maxWork, counters);
+                ok = hipMemcpyAsync(found, counters, 4, hipMemcpyDeviceToHost, st) == hipSuccess &&
+                     hipMemcpyAsync(&c0, dpCost, sizeof(float4), hipMemcpyDeviceToHost, st) == hipSuccess &&
+                     hipMemcpyAsync(&rootBox, nodeBox, sizeof(Box6), hipMemcpyDeviceToHost, st) == hipSuccess && hipStreamSynchronize(st) == hipSuccess;
+            }
+            if (ok && found[0] > maxWork) ok = false, rc = 8; // (cannot happen: see k_sah_find)
+            if (ok && found[0] > 0u) hipLaunchKernelGGL(k_sah_subtrees, dim3(found[0]), dim3(64), 0, st, knodes, leafBox, nodeBox, dpCost, stamp, work, counters);
+            if (ok) { // (k_sah_find has cleared the stamps of the nodes above: the old stamps below them are <= rootStamp, the new ones 1)
+                const uint32_t r0 = rootStamp + 1u;
+                rootStamp = 0;
+                for (uint32_t round = r0; round < r0 + 64u && rootStamp == 0; ++round) {
+                    hipLaunchKernelGGL(k_refit_round, dim3(gi), dim3(256), 0, st, knodes, nInternal, leafBox, nodeBox, stamp, round, dpCost);
+                    if (((round - r0 + 1u) & 15u) == 0u) {
+                        HR_CHECK(hipMemcpyAsync(&rootStamp, stamp, 4, hipMemcpyDeviceToHost, st));
+                        HR_CHECK(hipStreamSynchronize(st));
+                    }
+                }
+                float4 c1{};
+                HR_CHECK(hipMemcpyAsync(&rootStamp, stamp, 4, hipMemcpyDeviceToHost, st));
+                HR_CHECK(hipMemcpyAsync(found + 1, counters + 1, 4, hipMemcpyDeviceToHost, st));
+                HR_CHECK(hipMemcpyAsync(&c1, dpCost, sizeof(float4), hipMemcpyDeviceToHost, st));
+                HR_CHECK(hipStreamSynchronize(st));
+                if (rootStamp == 0) rc = 3;
+                const float dx = rootBox.hi[0] - rootBox.lo[0], dy = rootBox.hi[1] - rootBox.lo[1], dz = rootBox.hi[2] - rootBox.lo[2];
+                const float ra = dx * dy + dy * dz + dz * dx;
+                out->sahCostBefore = ra > 0.0f ? c0.x / ra : 0.0f, out->sahCostAfter = ra > 0.0f ? c1.x / ra : 0.0f;
+                out->sahFound = found[0], out->sahReplaced = found[1];
+            }
+            hipFree(work), hipFree(counters);
+            if (!ok && rc == 0) rc = 1; // (the stamps may be cleared: no tree to go on with)
+        }
         // ---- the second candidate: the PLOC tree over the same sorted triangles; the one whose collapse costs less (summed surface area
         // of the 4-wide nodes = expected node visits of a random ray) is kept
         KNode *pKnodes = nullptr;

@@ -357,6 +357,7 @@ struct hr_ctx {
     bool stageBusy[2] = {false, false};
     int stageTurn = 0;
     hr_scene_info info{};
+    hr_tree_info treeInfo{}; // include/hrcore_tree.h: of the last commit that built the tree
 
     // scene (device); nodes / tris alias tree.nodes / tree.tris
     Node4 *nodes = nullptr;

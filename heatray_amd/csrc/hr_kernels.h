@@ -9,6 +9,7 @@
 #include "../../include/hrcore_adaptive.h"
 #include "../../include/hrcore_history.h"
 #include "../../include/hrcore_reproject.h"
+#include "../../include/hrcore_tree.h"
 
 #include <cstddef>
 
@@ -280,11 +281,14 @@ struct BuildResult {
     uint32_t levelStart[kMaxLevels + 1]; // nodes of level L are [levelStart[L], levelStart[L + 1]) (breadth-first allocation)
     int32_t builder;            // which binary tree was collapsed: 0 the radix tree over Morton codes (LBVH), 1 PLOC
     float costRadix, costPloc;  // summed surface area of the 4-wide nodes over the root's, per candidate (0: not built)
+    float sahCostBefore, sahCostAfter; // ... of the radix tree before and after its bottom subtrees were rebuilt (0: no rebuild ran)
+    uint32_t sahFound, sahReplaced;    // bottom subtrees of 3..T triangles; those whose full-sweep SAH version was kept
 };
 struct BuildOptions {
     int ploc;       // 0: radix tree only; 1: build both, keep the cheaper collapse; 2: PLOC whenever it fits the traversal stack
     int plocRadius; // search radius of the nearest-neighbour step
     int maxLevels;  // levels of 4-wide nodes the traversal stack can hold (a PLOC tree deeper than that is not used)
+    int sahSub;     // T: the radix tree's subtrees of at most T <= 64 triangles are rebuilt by full-sweep SAH (0: off)
 };
 
 // scene bounds as float-ordered uints: lo.xyz, hi.xyz.  slotOfPrim != null: triangles go to their leaf slot (refit), else prim order.

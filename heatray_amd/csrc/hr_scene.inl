@@ -271,6 +271,7 @@ static int sceneKey(hr_ctx *c, unsigned long long *key)
     HIP_TRY(c, e);
     // (which tree a build produces also depends on the builder options: a file made with other ones is another scene's as far as the cache goes)
     mix(&c->tune.ploc, sizeof(c->tune.ploc)), mix(&c->tune.plocr, sizeof(c->tune.plocr));
+    if (c->tune.sahsub != 0) mix(&c->tune.sahsub, sizeof(c->tune.sahsub)); // (0 keeps the key of the files written before the knob existed: the same tree)
     *key = host ^ (dev * 0x9E3779B97F4A7C15ull);
     return HR_OK;
 }
@@ -446,7 +447,7 @@ int hr_scene_commit(hr_ctx *c)
                 launchSceneConsts(c->stream, c->dScratch, c->dConsts, nullptr);
                 cacheHit = true;
             } else {
-                const BuildOptions bo{c->tune.ploc, c->tune.plocr, (kStackLDS + kStackOvf) / 3};
+                const BuildOptions bo{c->tune.ploc, c->tune.plocr, (kStackLDS + kStackOvf) / 3, c->tune.sahsub};
                 const int brc = buildLBVH(c->stream, c->trisPrim, nTris, k.lo, k.hi, k.pad, c->dConsts, &cs.br, bo);
                 if (brc != 0) FAIL(c, HR_ERR_DEVICE, brc == 3 ? "LBVH refit did not reach the root" : "LBVH build failed");
                 if (!c->cachePath.empty()) saveTree(c, key, nTris, cs.br);
@@ -458,6 +459,12 @@ int hr_scene_commit(hr_ctx *c)
             if ((unsigned long long)cs.br.nNodes >= (1ull << 25)) FAIL(c, HR_ERR_UNSUPPORTED, "scene too large: a 32-byte node holds its children's base index in 25 bits (2^25 nodes, ~95 M triangles)");
             freeTree(c);
             c->tree = cs.br, cs.keepBuild = true;
+            c->treeInfo = hr_tree_info{};
+            if (!cacheHit) {
+                c->treeInfo.cost_before = cs.br.sahCostBefore, c->treeInfo.cost_after = cs.br.sahCostAfter;
+                c->treeInfo.subtrees_found = cs.br.sahFound, c->treeInfo.subtrees_replaced = cs.br.sahReplaced;
+                c->treeInfo.max_triangles = (uint32_t)(c->tune.sahsub > 0 ? c->tune.sahsub : 0);
+            }
             c->treeTris = nTris;
             launchAreaSum(c->stream, c->tree.nodeBox, (uint32_t)c->tree.nNodes, c->dConsts);
             launchTriAreaSum(c->stream, c->tree.tris, c->tree.triSlots, c->dConsts);
@@ -505,6 +512,17 @@ int hr_scene_get_info(hr_ctx *c, hr_scene_info *out)
     if (c->grp) return groupOne(c, 0, [&](hr_ctx *m) { return hr_scene_get_info(m, out); });
     if (!c->committed || !out) FAIL(c, HR_ERR_INVALID, "scene not committed");
     *out = c->info;
+    return HR_OK;
+}
+
+// include/hrcore_tree.h
+uint32_t hr_tree_api_version(void) { return HR_TREE_API_VERSION; }
+int hr_scene_get_tree_info(hr_ctx *c, hr_tree_info *out)
+{
+    ENTER(c);
+    if (c->grp) return groupOne(c, 0, [&](hr_ctx *m) { return hr_scene_get_tree_info(m, out); });
+    if (!c->committed || !out) FAIL(c, HR_ERR_INVALID, "scene not committed");
+    *out = c->treeInfo;
     return HR_OK;
 }
 

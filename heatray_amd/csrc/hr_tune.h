@@ -1,4 +1,4 @@
-// hr_tune.h — the HR_TUNE knobs: one struct of integers, ONE table that names, bounds and documents each of them, and the parser of the
+// hr_tune.h — the HR_TUNE knobs: one struct of integers, ONE table that names, bounds and documents each of them (and a second, kTuneBuildKnobs, for the tree builder's later ones), and the parser of the
 // comma-separated key=value string hr_ctx_create reads from the environment.  Host-only C++ without a HIP include, so that
 // tests/host/tune_parse_cpu.cpp checks it without a device.  The defaults were measured on MI355X; the knobs exist for experiments
 // (every A/B in profiles/) and for the tests that force a code path (packets=0|1, ploc=0|2, ovf=1..3, slow=0, ...).
@@ -19,7 +19,7 @@ struct Tune {
     int tri = 2, refill = 16, blocks = 5, sblocks = 4, depth = kMaxSlots, batch = 0, fmax = 64, fmin = 64;
     int groups = 0, prio = 1, refit = 1, sdeal = 256, guard = 125, ploc = 1, plocr = 16;
     int packets = 2, corun = 1, cmin = 50, cblocks = 0, plog = -1, pswz = 1, pstep = 1, pstepf = 110, pprobe = 0, punion = 220;
-    int fprim = 128, fgate = 8, heads = 5, slow = 4, ovf = 0;
+    int fprim = 128, fgate = 8, heads = 5, slow = 4, ovf = 0, sahsub = 64;
     bool blocksSet = false; // blocks= was given: hr_frame_resize then leaves k_trace's workgroups per CU at it (hr_ctx::traceBlocks)
     bool debugPipe = false, debugStepTimes = false; // not knobs: HR_DEBUG_PIPE / HR_DEBUG_STEPTIMES are set in the environment (hr_ctx_create reads them once, beside HR_TUNE)
 };
@@ -61,11 +61,18 @@ static const TuneKnob kTuneKnobs[] = {
 };
 static const size_t kTuneKnobCount = sizeof(kTuneKnobs) / sizeof(kTuneKnobs[0]);
 
+// The tree builder's knobs added after the table above was pinned (tests/host/tune_parse_cpu.cpp holds its 30 rows, their order and
+// defaults): same row type, same parser, same rules; a key is looked up in kTuneKnobs first, then here.
+static const TuneKnob kTuneBuildKnobs[] = {
+    {"sahsub", &Tune::sahsub, 0, 64, "sahsub=0|T: the radix tree's bottom subtrees of at most T triangles are rebuilt by full-sweep SAH (hr_build.hip: k_sah_subtrees; 0: off, one wave holds 64)"},
+};
+static const size_t kTuneBuildKnobCount = sizeof(kTuneBuildKnobs) / sizeof(kTuneBuildKnobs[0]);
+
 // Items are key=integer (optional sign, decimal digits, nothing after); empty items and an empty string are fine.  An unknown key, a missing
 // '=', a value that is no integer or lies outside its row's range is an error: false, with `err` naming the item, and `out` is not to be used.
 static bool parseTune(const char *text, Tune &out, std::string &err)
 {
-    bool seen[kTuneKnobCount] = {};
+    bool seen[kTuneKnobCount + kTuneBuildKnobCount] = {};
     for (const char *p = text; *p;) {
         const std::string item(p, strcspn(p, ","));
         p += item.size() + (p[item.size()] == ',' ? 1 : 0);
@@ -73,13 +80,14 @@ static bool parseTune(const char *text, Tune &out, std::string &err)
         const size_t eq = item.find('=');
         if (eq == std::string::npos) return err = "'" + item + "' is not key=value", false;
         size_t k = 0;
-        while (k < kTuneKnobCount && item.compare(0, eq, kTuneKnobs[k].key) != 0) ++k;
-        if (k == kTuneKnobCount) return err = "unknown key in '" + item + "'", false;
+        auto rowOf = [](size_t i) -> const TuneKnob & { return i < kTuneKnobCount ? kTuneKnobs[i] : kTuneBuildKnobs[i - kTuneKnobCount]; };
+        while (k < kTuneKnobCount + kTuneBuildKnobCount && item.compare(0, eq, rowOf(k).key) != 0) ++k;
+        if (k == kTuneKnobCount + kTuneBuildKnobCount) return err = "unknown key in '" + item + "'", false;
         const char *v = item.c_str() + eq + 1, *digits = v + (*v == '+' || *v == '-' ? 1 : 0);
         if (!*digits || strspn(digits, "0123456789") != strlen(digits)) return err = "the value in '" + item + "' is not an integer", false;
         errno = 0;
         const long value = strtol(v, nullptr, 10);
-        const TuneKnob &row = kTuneKnobs[k];
+        const TuneKnob &row = rowOf(k);
         if (errno == ERANGE || value < row.lo || value > row.hi)
             return err = "the value in '" + item + "' is outside " + std::to_string(row.lo) + ".." + std::to_string(row.hi), false;
         // A repeated key keeps its FIRST value and is no error, as with the strstr parser before this one: bench.py appends
