@@ -287,6 +287,30 @@ class TreeInfo(C.Structure):
                 ("max_triangles", C.c_uint32), ("reserved", C.c_uint32 * 3)]
 
 
+# every symbol include/hrcore_exposure.h declares (auto-exposure: the luminance histogram, its reduce and the metered display).  Resolved
+# lazily like the AOV symbols
+HR_EXPOSURE_API_VERSION = 1
+HR_EXPOSURE_BINS = 256
+HR_EXPOSURE_EMPTY, HR_EXPOSURE_CLAMPED_LOW, HR_EXPOSURE_CLAMPED_HIGH, HR_EXPOSURE_ADAPTED = 1, 2, 4, 8
+EXPOSURE_SYMBOLS = ["exposure_api_version", "exposure_default_params", "exposure_meter", "exposure_display", "exposure_last", "exposure_reset"]
+
+
+class ExposureParams(C.Structure):
+    """hr_exposure_params"""
+    _fields_ = [("key", C.c_float), ("low_permille", C.c_int32), ("high_permille", C.c_int32), ("min_scale", C.c_float), ("max_scale", C.c_float),
+                ("adapt", C.c_float), ("window", C.c_int32 * 4), ("reserved", C.c_uint32 * 6)]
+
+
+class ExposureResult(C.Structure):
+    """hr_exposure_result"""
+    _fields_ = [("scale", C.c_float), ("target", C.c_float), ("key_luminance", C.c_float), ("position", C.c_uint32), ("counted", C.c_uint64),
+                ("used", C.c_uint64), ("below", C.c_uint64), ("above", C.c_uint64), ("nonfinite", C.c_uint64), ("invalid", C.c_uint64),
+                ("flags", C.c_uint32), ("reserved", C.c_uint32 * 3)]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_ if k != "reserved"}
+
+
 # The optional headers: feature -> (its symbols, the version the binding was written against, what "this library has no ..." calls it);
 # the version function is <feature>_api_version.  Engine._feature_call checks a feature on its first call
 FEATURES = {
@@ -297,6 +321,7 @@ FEATURES = {
     "history": (HISTORY_SYMBOLS, HR_HISTORY_API_VERSION, "history reprojection"),
     "reproject": (REPROJECT_SYMBOLS, HR_REPROJECT_API_VERSION, "progressive history merge"),
     "tree": (TREE_SYMBOLS, HR_TREE_API_VERSION, "tree build report"),
+    "exposure": (EXPOSURE_SYMBOLS, HR_EXPOSURE_API_VERSION, "auto-exposure"),
 }
 
 
@@ -801,6 +826,35 @@ class Engine:
         """Asynchronous: the preview (W x H float4) into device memory, e.g. a torch tensor; ordered like denoise_to_device."""
         self._feature_call("reproject", "reproject_preview", C.byref(pass_params), C.byref(params) if params is not None else None, C.c_void_p(int(device_ptr)),
                            C.c_void_p(stream or 0), None)
+
+    # -- auto-exposure (include/hrcore_exposure.h)
+    def exposure_meter(self, params=None, image=None):
+        """Meters the frame (completing the enqueued passes), or `image`: the device pointer of a W x H float4 image in accumulation
+        format, e.g. a torch tensor that denoise_to_device filled.  params: an ExposureParams (heatray_amd.exposure.default_params()),
+        None = the defaults.  Returns the ExposureResult as a dict."""
+        r = ExposureResult()
+        self._feature_call("exposure", "exposure_meter", C.byref(params) if params is not None else None, C.c_void_p(int(image) if image else 0), C.byref(r))
+        return r.as_dict()
+
+    def exposure_display(self, device_ptr, display=None, fmt=HR_DISPLAY_RGBA8, params=None, image=None):
+        """Asynchronous: meters like exposure_meter and resolves the metered image, at the metered scale, into device memory (like
+        display_device; fmt may carry HR_DISPLAY_PROGRESSIVE).  Returns the passes shown (0 for an `image`)."""
+        display = display if display is not None else display_params()
+        shown = C.c_uint32()
+        self._feature_call("exposure", "exposure_display", C.byref(params) if params is not None else None, C.byref(display), C.c_int32(fmt),
+                           C.c_void_p(int(image) if image else 0), C.c_void_p(int(device_ptr)), C.byref(shown))
+        return int(shown.value)
+
+    def exposure_last(self, with_bins=False):
+        """The last metering's ExposureResult as a dict (waits for it); with_bins: (the dict, its 256 bins as uint64)."""
+        r = ExposureResult()
+        bins = np.zeros(HR_EXPOSURE_BINS, np.uint64)
+        self._feature_call("exposure", "exposure_last", C.byref(r), bins.ctypes.data_as(C.POINTER(C.c_uint64)) if with_bins else None)
+        return (r.as_dict(), bins) if with_bins else r.as_dict()
+
+    def exposure_reset(self):
+        """Forgets the adaptation state: the next metering's scale is its target."""
+        self._feature_call("exposure", "exposure_reset")
 
     def debug_trace(self, origins, dirs, tmax=None, skip_prim=None, any_hit=False):
         o, d = _f32(origins).reshape(-1, 3), _f32(dirs).reshape(-1, 3)

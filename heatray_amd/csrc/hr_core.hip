@@ -16,6 +16,7 @@
 //   hr_adaptive.inl   the sample mask and the error estimate that builds it (include/hrcore_adaptive.h)
 //   hr_history.inl    history reprojection across a camera change (include/hrcore_history.h)
 //   hr_reproject.inl  its progressive form and the preview of unsampled pixels (include/hrcore_reproject.h)
+//   hr_exposure.inl   auto-exposure: the luminance histogram, its reduce and the metered display (include/hrcore_exposure.h)
 // (one translation unit: the .inl files are sections of this one, included below)
 // The kernels it launches are units of their own (declared in hr_kernels.h): the render stages hr_raygen.hip, hr_trace.hip, hr_shade.hip and
 // hr_frame.hip (resolve, shard exchange, display) over what they share in hr_wave.h; hr_build.hip; one unit per post-process feature.
@@ -206,6 +207,14 @@ static void reprojectFree(hr_ctx *c)
     c->rpStale = true, c->rpMerged = false;
 }
 
+// Auto-exposure (include/hrcore_exposure.h): the last metering and the adaptation state go with the context, not with the frame
+static void exposureFree(hr_ctx *c)
+{
+    hipFree(c->exState);
+    c->ex.free();
+    c->exState = nullptr, c->exMetered = false;
+}
+
 static void freeTree(hr_ctx *c)
 {
     hipFree(c->tree.nodes), hipFree(c->tree.nodes32), hipFree(c->tree.leafKeys), hipFree(c->tree.tris), hipFree(c->tree.nodeBox), hipFree(c->tree.slotOfPrim);
@@ -369,6 +378,7 @@ int hr_ctx_destroy(hr_ctx *c)
     adaptiveFree(c);
     historyFree(c);
     reprojectFree(c);
+    exposureFree(c);
     c->meshReleaseAll();
     for (int k = 0; k < 2; ++k) {
         if (c->stage[k]) hipHostFree(c->stage[k]);
@@ -752,3 +762,6 @@ int hr_debug_trace(hr_ctx *c, int32_t n, const float *o, const float *d, const f
 
 // ------------------------------------------------------------------------------------------ denoiser with the spatial variance estimate
 #include "hr_denoise_spatial.inl"
+
+// ------------------------------------------------------------------------------------------ auto-exposure
+#include "hr_exposure.inl"

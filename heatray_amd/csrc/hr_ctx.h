@@ -480,6 +480,11 @@ struct hr_ctx {
     float *rpOut = nullptr;                   // the preview when it does not go straight to the caller's memory (W x H float4)
     float *rpPinned = nullptr;                // hr_reproject_preview_readback's host buffer
     size_t rpPinnedBytes = 0;
+    // Auto-exposure (include/hrcore_exposure.h).  Nothing here depends on the frame's size: hr_clear and hr_frame_resize leave it alone
+    // (exposureFree: hr_ctx_destroy).
+    ResultCounters<unsigned long long> ex; // kExWords of hr_exposure.h: the last metering's bins, class counters and reduced words
+    uint32_t *exState = nullptr;           // {there is an adaptation state, its scale's bits} on the device: hr_exposure_reset zeroes it
+    bool exMetered = false;                // `ex` holds a metering (hr_exposure_last)
     size_t aovFramesPerSlot() const { return (aovMask & HR_AOV_SURFACE) ? 2 : 0; }
     // Context group (include/hrcore_group.h): non-null when this handle is a group.  Its own fields then describe the ASSEMBLED frame on the
     // group's first device (W, H, frame, fbInternal, the read-back buffers) and `stream` is the assembly stream; no pass pipeline runs on it.

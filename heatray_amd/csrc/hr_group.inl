@@ -186,6 +186,7 @@ static int groupDestroy(hr_ctx *c)
     if (c->pinnedDisplay) hipHostFree(c->pinnedDisplay);
     aovFree(c);
     adaptiveFree(c);
+    exposureFree(c);
     delete g;
     delete c;
     return HR_OK;

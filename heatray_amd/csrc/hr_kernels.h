@@ -10,6 +10,7 @@
 #include "../../include/hrcore_history.h"
 #include "../../include/hrcore_reproject.h"
 #include "../../include/hrcore_tree.h"
+#include "../../include/hrcore_exposure.h"
 
 #include <cstddef>
 
@@ -235,6 +236,15 @@ void launchReprojectMerge(hipStream_t st, int W, int H, const HsCam &cam, const 
 // result = {own pixels, previewed pixels, empty pixels} in the first three of kReprojectResultWords words, zeroed by the caller
 void launchReprojectPreview(hipStream_t st, int W, int H, const HsCam &cam, const HsParams &P, const float *hist, const float *frame, const float *albedo,
                             const float *normalDepth, float *out, unsigned long long *result);
+
+// ---- hr_exposure.hip (include/hrcore_exposure.h)
+struct ExParams; // hr_exposure.h: the reduce's parameters as the kernel takes them
+struct ExWindow; // ... and the metered rectangle
+// image (W x H float4, accumulation format) -> words: kExWords of hr_exposure.h (the 256 bins, the four class counters, what the reduce
+// writes), zeroed by the caller; state: two 32-bit words {there is an adaptation state, its scale's bits}, read and written by the reduce
+void launchExposureMeter(hipStream_t st, int numCUs, int W, int H, const float *image, const ExWindow &win, const ExParams &P, unsigned long long *words, uint32_t *state);
+// launchDisplay of the image whose rgb is multiplied by the scale word of `words`
+void launchExposureDisplay(hipStream_t st, const FrameDev &fr, const hr_display_params &P, int format, const unsigned long long *words, void *out);
 
 // ---- hr_build.hip
 // Per-geometry descriptor for the assemble kernel; all pointers are device pointers.  Attributes are addressed with a stride

@@ -1,5 +1,5 @@
 // hr_postprocess.inl — a section of hr_core.hip (included before the feature sections): the host plumbing that the AOV planes, the
-// denoiser, adaptive sampling, history reprojection and the progressive merge share ("Adding a post-process feature"); the
+// denoiser, adaptive sampling, history reprojection, the progressive merge and auto-exposure share ("Adding a post-process feature"); the
 // result counters' type, ResultCounters, is in hr_ctx.h beside the context's fields of it.
 
 // `bytes` of device memory that is complete on the ctx stream -> dst, on `stream` (null: the ctx stream).  On a foreign stream the copy
@@ -34,7 +34,7 @@ static int growPinned(hr_ctx *c, float *&pinned, size_t &have, size_t bytes)
 
 // ---- "a full-frame post-process wants this frame"
 struct FrameNeed {
-    uint32_t aov;       // the AOV planes it reads (HR_AOV_*): enabled, and zeroed when the frame was, so they hold the frame's passes
+    uint32_t aov;       // the AOV planes it reads (HR_AOV_*): enabled, and zeroed when the frame was, so they hold the frame's passes; 0: none, the planes are not asked about
     const char *name;   // starts its messages: "denoise", "history merge"
     const char *reader; // what reads across the tiles, for the refusals of a sharded frame: "the filter"
     bool group;         // a context group is served: its frame and the planes of `aov` are assembled on its first device
@@ -50,15 +50,15 @@ static int groupAovAssemble(hr_ctx *c, int32_t plane, uint64_t *passes); // hr_a
 // one context's planes (a group's handle, each of its members, a plain context)
 static int framePlanesReady(hr_ctx *c, const FrameNeed &need)
 {
+    if (need.aov == 0) return HR_OK; // (it reads no plane: whether and when they were enabled is not its business)
     if ((c->aovMask & need.aov) != need.aov)
         FAIL(c, HR_ERR_INVALID, need.needs + " before the frame's first pass (enabled mask: " + std::to_string(c->aovMask) + ")");
     if (c->aovZeroedAt != c->frameZeroedAt) FAIL(c, HR_ERR_INVALID, need.late + " the frame's passes: hr_clear, or hr_aov_enable before rendering");
     return HR_OK;
 }
 
-// Checks in this order: the kind of context, a frame, the planes; then completes the enqueued passes (a group: assembles its frame and
-// planes) and reports a ray queue overflow.  *frame: the complete frame on the ctx's device; *passes: the complete passes in it.
-static int frameReady(hr_ctx *c, const FrameNeed &need, const float **frame, uint32_t *passes)
+// the kind of context, then a frame: what frameReady asks first (and all a caller that brings its own image asks)
+static int frameKindReady(hr_ctx *c, const FrameNeed &need)
 {
     if (c->grp && !need.group)
         FAIL(c, HR_ERR_INVALID, std::string(need.name) + ": a context group is not supported (" + need.reader + " reads across the members' tiles): capture and merge on a plain context");
@@ -66,7 +66,15 @@ static int frameReady(hr_ctx *c, const FrameNeed &need, const float **frame, uin
         FAIL(c, HR_ERR_INVALID, std::string(need.name) + ": a tile-sharded context (world > 1) holds only its own tiles and " + need.reader + " reads across them" +
                                     (need.group ? ": use a context group, which assembles the frame" : ""));
     if (c->W <= 0) FAIL(c, HR_ERR_INVALID, "no frame");
-    int rc = framePlanesReady(c, need); // (a group: its own mask, hr_aov_enable on the handle)
+    return HR_OK;
+}
+
+// Checks in this order: the kind of context, a frame, the planes; then completes the enqueued passes (a group: assembles its frame and
+// planes) and reports a ray queue overflow.  *frame: the complete frame on the ctx's device; *passes: the complete passes in it.
+static int frameReady(hr_ctx *c, const FrameNeed &need, const float **frame, uint32_t *passes)
+{
+    int rc = frameKindReady(c, need);
+    if (rc == HR_OK) rc = framePlanesReady(c, need); // (a group: its own mask, hr_aov_enable on the handle)
     if (rc == HR_OK && c->grp) rc = groupAll(c, [&need](hr_ctx *m, int) { return framePlanesReady(m, need); });
     if (rc) return rc;
     if (c->grp) {
