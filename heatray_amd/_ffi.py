@@ -311,6 +311,30 @@ class ExposureResult(C.Structure):
         return {k: getattr(self, k) for k, _ in self._fields_ if k != "reserved"}
 
 
+# every symbol include/hrcore_metric.h declares (the convergence metric: exact relative L2 against a reference, or predicted from the sample
+# moments).  Resolved lazily like the AOV symbols
+HR_METRIC_API_VERSION = 1
+HR_METRIC_BINS = 256
+HR_METRIC_COMPARE, HR_METRIC_ESTIMATE = 0, 1
+HR_METRIC_EMPTY, HR_METRIC_ZERO_DENOMINATOR = 1, 2
+METRIC_SYMBOLS = ["metric_api_version", "metric_default_params", "metric_compare", "metric_estimate", "metric_last"]
+
+
+class MetricParams(C.Structure):
+    """hr_metric_params"""
+    _fields_ = [("window", C.c_int32 * 4), ("reserved", C.c_uint32 * 4)]
+
+
+class MetricResult(C.Structure):
+    """hr_metric_result"""
+    _fields_ = [("num", C.c_double), ("den", C.c_double), ("value", C.c_double), ("mse", C.c_double), ("counted", C.c_uint64), ("differing", C.c_uint64),
+                ("nonfinite", C.c_uint64), ("skipped", C.c_uint64), ("max_abs", C.c_float), ("passes", C.c_uint32), ("kind", C.c_uint32), ("flags", C.c_uint32),
+                ("reserved", C.c_uint32 * 4)]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_ if k != "reserved"}
+
+
 # The optional headers: feature -> (its symbols, the version the binding was written against, what "this library has no ..." calls it);
 # the version function is <feature>_api_version.  Engine._feature_call checks a feature on its first call
 FEATURES = {
@@ -322,6 +346,7 @@ FEATURES = {
     "reproject": (REPROJECT_SYMBOLS, HR_REPROJECT_API_VERSION, "progressive history merge"),
     "tree": (TREE_SYMBOLS, HR_TREE_API_VERSION, "tree build report"),
     "exposure": (EXPOSURE_SYMBOLS, HR_EXPOSURE_API_VERSION, "auto-exposure"),
+    "metric": (METRIC_SYMBOLS, HR_METRIC_API_VERSION, "convergence metric"),
 }
 
 
@@ -855,6 +880,31 @@ class Engine:
     def exposure_reset(self):
         """Forgets the adaptation state: the next metering's scale is its target."""
         self._feature_call("exposure", "exposure_reset")
+
+    # -- the convergence metric (include/hrcore_metric.h)
+    def metric_compare(self, reference, image=None, params=None):
+        """The relative L2 distance of the frame (completing the enqueued passes), or of `image`, from `reference`: device pointers of
+        W x H float4 images in accumulation format, e.g. a torch tensor holding a kept copy of a converged frame.  params: a MetricParams
+        (heatray_amd.metric.default_params()), None = the whole image.  Waits; returns the MetricResult as a dict (`value` is the metric)."""
+        r = MetricResult()
+        self._feature_call("metric", "metric_compare", C.byref(params) if params is not None else None, C.c_void_p(int(image) if image else 0),
+                           C.c_void_p(int(reference) if reference else 0), C.byref(r))
+        return r.as_dict()
+
+    def metric_estimate(self, params=None):
+        """The relative L2 distance the frame's sample moments predict between its luminance image and its own limit (HR_AOV_MOMENTS must
+        be enabled before the frame's first pass).  Waits; returns the MetricResult as a dict."""
+        r = MetricResult()
+        self._feature_call("metric", "metric_estimate", C.byref(params) if params is not None else None, C.byref(r))
+        return r.as_dict()
+
+    def metric_last(self, with_bins=False):
+        """The last measurement's MetricResult as a dict; with_bins: (the dict, the 256 bins of num, those of den, as uint64)."""
+        r = MetricResult()
+        num, den = np.zeros(HR_METRIC_BINS, np.uint64), np.zeros(HR_METRIC_BINS, np.uint64)
+        u64p = C.POINTER(C.c_uint64)
+        self._feature_call("metric", "metric_last", C.byref(r), num.ctypes.data_as(u64p) if with_bins else None, den.ctypes.data_as(u64p) if with_bins else None)
+        return (r.as_dict(), num, den) if with_bins else r.as_dict()
 
     def debug_trace(self, origins, dirs, tmax=None, skip_prim=None, any_hit=False):
         o, d = _f32(origins).reshape(-1, 3), _f32(dirs).reshape(-1, 3)

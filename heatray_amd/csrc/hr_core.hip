@@ -17,6 +17,7 @@
 //   hr_history.inl    history reprojection across a camera change (include/hrcore_history.h)
 //   hr_reproject.inl  its progressive form and the preview of unsampled pixels (include/hrcore_reproject.h)
 //   hr_exposure.inl   auto-exposure: the luminance histogram, its reduce and the metered display (include/hrcore_exposure.h)
+//   hr_metric.inl     the convergence metric: exact relative L2 against a reference, or predicted from the moments (include/hrcore_metric.h)
 // (one translation unit: the .inl files are sections of this one, included below)
 // The kernels it launches are units of their own (declared in hr_kernels.h): the render stages hr_raygen.hip, hr_trace.hip, hr_shade.hip and
 // hr_frame.hip (resolve, shard exchange, display) over what they share in hr_wave.h; hr_build.hip; one unit per post-process feature.
@@ -215,6 +216,13 @@ static void exposureFree(hr_ctx *c)
     c->exState = nullptr, c->exMetered = false;
 }
 
+// The convergence metric (include/hrcore_metric.h): the last measurement goes with the context, not with the frame
+static void metricFree(hr_ctx *c)
+{
+    c->mt.free();
+    c->mtMeasured = false;
+}
+
 static void freeTree(hr_ctx *c)
 {
     hipFree(c->tree.nodes), hipFree(c->tree.nodes32), hipFree(c->tree.leafKeys), hipFree(c->tree.tris), hipFree(c->tree.nodeBox), hipFree(c->tree.slotOfPrim);
@@ -379,6 +387,7 @@ int hr_ctx_destroy(hr_ctx *c)
     historyFree(c);
     reprojectFree(c);
     exposureFree(c);
+    metricFree(c);
     c->meshReleaseAll();
     for (int k = 0; k < 2; ++k) {
         if (c->stage[k]) hipHostFree(c->stage[k]);
@@ -765,3 +774,6 @@ int hr_debug_trace(hr_ctx *c, int32_t n, const float *o, const float *d, const f
 
 // ------------------------------------------------------------------------------------------ auto-exposure
 #include "hr_exposure.inl"
+
+// ------------------------------------------------------------------------------------------ convergence metric
+#include "hr_metric.inl"

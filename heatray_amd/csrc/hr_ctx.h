@@ -485,6 +485,11 @@ struct hr_ctx {
     ResultCounters<unsigned long long> ex; // kExWords of hr_exposure.h: the last metering's bins, class counters and reduced words
     uint32_t *exState = nullptr;           // {there is an adaptation state, its scale's bits} on the device: hr_exposure_reset zeroes it
     bool exMetered = false;                // `ex` holds a metering (hr_exposure_last)
+    // The convergence metric (include/hrcore_metric.h).  Nothing here depends on the frame's size: hr_clear and hr_frame_resize leave it
+    // alone (metricFree: hr_ctx_destroy).
+    ResultCounters<unsigned long long> mt; // kMtWords of hr_metric.h: the last measurement's bins, counters and max_abs bits
+    uint32_t mtKind = 0, mtPasses = 0;     // ... its kind (HR_METRIC_*) and the frame's passes in it
+    bool mtMeasured = false;               // `mt` holds a measurement (hr_metric_last)
     size_t aovFramesPerSlot() const { return (aovMask & HR_AOV_SURFACE) ? 2 : 0; }
     // Context group (include/hrcore_group.h): non-null when this handle is a group.  Its own fields then describe the ASSEMBLED frame on the
     // group's first device (W, H, frame, fbInternal, the read-back buffers) and `stream` is the assembly stream; no pass pipeline runs on it.

@@ -187,6 +187,7 @@ static int groupDestroy(hr_ctx *c)
     aovFree(c);
     adaptiveFree(c);
     exposureFree(c);
+    metricFree(c);
     delete g;
     delete c;
     return HR_OK;

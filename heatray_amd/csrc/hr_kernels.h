@@ -11,6 +11,7 @@
 #include "../../include/hrcore_reproject.h"
 #include "../../include/hrcore_tree.h"
 #include "../../include/hrcore_exposure.h"
+#include "../../include/hrcore_metric.h"
 
 #include <cstddef>
 
@@ -245,6 +246,12 @@ struct ExWindow; // ... and the metered rectangle
 void launchExposureMeter(hipStream_t st, int numCUs, int W, int H, const float *image, const ExWindow &win, const ExParams &P, unsigned long long *words, uint32_t *state);
 // launchDisplay of the image whose rgb is multiplied by the scale word of `words`
 void launchExposureDisplay(hipStream_t st, const FrameDev &fr, const hr_display_params &P, int format, const unsigned long long *words, void *out);
+
+// ---- hr_metric.hip (include/hrcore_metric.h)
+struct MtWindow; // hr_metric.h: the measured rectangle
+// kind 0 (compare): image against other = the reference; kind 1 (estimate): image = the frame, other = its MOMENTS plane; all W x H float4
+// -> words: kMtWords of hr_metric.h (the 256 bins of NUM, those of DEN, the four counters, the bits of max_abs), zeroed by the caller
+void launchMetricAccumulate(hipStream_t st, int numCUs, int W, int H, int kind, const float *image, const float *other, const MtWindow &win, unsigned long long *words);
 
 // ---- hr_build.hip
 // Per-geometry descriptor for the assemble kernel; all pointers are device pointers.  Attributes are addressed with a stride
