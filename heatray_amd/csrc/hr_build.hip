@@ -1,25 +1,24 @@
-// hr_build.hip — scene assembly and LBVH construction on the GPU, plus the sample-table generators.
+// hr_build.hip — scene assembly and BVH construction on the GPU (the table generators are in hr_tables.hip).
 //
 // Replaces what OpenRL does with the buffers of rlDrawElements (/root/reference/Source/HeatrayRenderer/
-// Scene/Mesh.cpp:29-153, Resources/shaders/vertex.rlsl:25-43) — SURVEY §8a row a6 — and the host-side table
-// generators (Source/Utility/Random.h:85-289, Source/HeatrayRenderer/Materials/MultiScatterUtil.cpp:20-139).
+// Scene/Mesh.cpp:29-153, Resources/shaders/vertex.rlsl:25-43) — SURVEY §8a row a6.
 //
 //   assemble : one thread per triangle: world transform, edge form, shading attributes, scene bounds
 //   morton   : 30-bit Morton code of the triangle-AABB centre, normalised by the scene bounds
 //   sort     : LSD radix sort, 4 x 8-bit digits, stable (histogram / scan / ballot-ranked scatter)
 //   karras   : binary radix tree over the sorted (key, index) pairs
-//   refit    : bottom-up boxes in kernel-ordered rounds (no inter-workgroup hand-off inside a launch,
-//              so no reliance on cross-XCD visibility)
-//   emit     : subtrees of <= 4 triangles collapse into leaves; 64-byte two-box nodes
+//   refit    : bottom-up boxes and collapse costs in kernel-ordered rounds (no inter-workgroup hand-off inside a
+//              launch, so no reliance on cross-XCD visibility)
+//   sah      : the radix tree's bottom subtrees rebuilt by full-sweep SAH (hr_sah_subtree.h)
+//   ploc     : the second candidate, by parallel locally-ordered clustering; the cheaper collapse is kept
+//   collapse : the binary tree to 4-wide nodes by minimal summed node area; 64-byte nodes, then the 32-byte encode
 #include "hr_kernels.h"
-#include "hr_tables.h"
+#include <algorithm>
 #include <cstring>
-#include "hr_texture.h"
-
+#include <utility>
 #include <vector>
 
 namespace hr {
-
 
 #define HR_CHECK(expr)                  \
     do {                                \
@@ -321,12 +320,6 @@ HRD int deltaKey(const uint32_t *keys, int n, int i, int j)
     return __clz((int)(a ^ b));
 }
 
-#ifndef HR_COLLAPSE_DP
-#define HR_COLLAPSE_DP 1 // collapse the binary tree to 4-wide nodes by minimal summed node area (0: open the largest child twice, rounds 1-3a)
-#endif
-#ifndef HR_ROTATE_SWEEPS
-#define HR_ROTATE_SWEEPS 0 // tree-rotation sweeps over the binary tree before the collapse (experiment knob)
-#endif
 #include "hr_sah_subtree.h"
 struct KNode {
     int left, right; // >= 0: internal node, < 0: leaf ~index
@@ -360,10 +353,27 @@ __global__ __launch_bounds__(256) void k_karras(const uint32_t *__restrict__ key
     nodes[i] = k;
 }
 
+HRD float boxArea(const Box6 &b)
+{
+    const float dx = b.hi[0] - b.lo[0], dy = b.hi[1] - b.lo[1], dz = b.hi[2] - b.lo[2];
+    return dx * dy + dy * dz + dz * dx;
+}
+
+// (C1, C2, C3, C4) of a binary node from its children's (see k_refit_round); a triangle child (ref < 0) costs nothing
+HRD float4 collapseCost(int left, int right, float area, const float4 *__restrict__ cost)
+{
+    const float4 z = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+    const float4 cl = left < 0 ? z : cost[left], cr = right < 0 ? z : cost[right];
+    const float h2 = cl.x + cr.x;
+    const float h3 = fmin_(cl.x + cr.y, cl.y + cr.x);
+    const float h4 = fmin_(cl.x + cr.z, fmin_(cl.y + cr.y, cl.z + cr.x));
+    const float c1 = area + h4;
+    const float c2 = fmin_(c1, h2), c3 = fmin_(c2, h3), c4 = fmin_(c3, h4);
+    return make_float4(c1, c2, c3, c4);
+}
+
 // One bottom-up round: a node whose children were finished in an EARLIER launch gets its box.
 // stamp[i] = round in which node i was finished (0 = not yet); visibility comes from the kernel boundary.
-HRD float boxArea(const Box6 &b);
-HRD float4 collapseCost(int left, int right, float area, const float4 *__restrict__ cost);
 // ... and the costs of the collapse to a 4-wide tree (k_collapse4): cost[i] = (C1, C2, C3, C4), Ck = the least sum of the surface areas of
 // the 4-wide nodes that can represent the subtree of binary node i when it may occupy up to k child slots of its 4-wide parent
 // (k = 1: it is a child itself, a node of its own; k >= 2: it may be opened and its two children share the slots).  A triangle costs
@@ -386,85 +396,8 @@ __global__ __launch_bounds__(256) void k_refit_round(const KNode *__restrict__ n
         u.hi[c] = fmax_(a.hi[c], b.hi[c]);
     }
     nodeBox[i] = u;
-    if (cost) cost[i] = collapseCost(k.left, k.right, boxArea(u), cost);
+    cost[i] = collapseCost(k.left, k.right, boxArea(u), cost);
     stamp[i] = round;
-}
-
-// Tree rotations (Kensler 2008) on the binary tree before it is collapsed: node N with children L, R may exchange R with one of
-// L's children (or L with one of R's) when that shrinks the surface area of the rebuilt child — the LBVH splits by Morton prefix,
-// blind to the boxes, and a rotation repairs the worst of it.  One launch handles the nodes of ONE stamp value (the round of the
-// bottom-up refit that finished them: a parent's stamp is larger than its children's), bottom-up, so that no two nodes of a launch
-// are parent and child and the subtrees below are final: no locks.  Hits do not depend on the tree.
-__global__ __launch_bounds__(256) void k_rotate(KNode *__restrict__ nodes, int nInternal, const Box6 *__restrict__ leafBox, Box6 *__restrict__ nodeBox,
-                                                const uint32_t *__restrict__ stamp, uint32_t which, uint32_t *__restrict__ applied)
-{
-    const int i = blockIdx.x * 256 + threadIdx.x;
-    if (i >= nInternal || stamp[i] != which) return;
-    const KNode N = nodes[i];
-    auto boxOf = [&](int ref) { return ref < 0 ? leafBox[~ref] : nodeBox[ref]; };
-    auto unite = [](const Box6 &a, const Box6 &b) {
-        Box6 u;
-#pragma unroll
-        for (int c = 0; c < 3; ++c) u.lo[c] = fmin_(a.lo[c], b.lo[c]), u.hi[c] = fmax_(a.hi[c], b.hi[c]);
-        return u;
-    };
-    // option k: 0/1 = R <-> L.left / L.right, 2/3 = L <-> R.left / R.right; gain = area of the child before - after
-    float bestGain = 0.0f;
-    int best = -1;
-    Box6 bestBox;
-    for (int side = 0; side < 2; ++side) {
-        const int inner = side == 0 ? N.left : N.right, other = side == 0 ? N.right : N.left;
-        if (inner < 0) continue;
-        const KNode A = nodes[inner];
-        const float before = boxArea(nodeBox[inner]);
-        const Box6 bo = boxOf(other), b1 = boxOf(A.left), b2 = boxOf(A.right);
-        const Box6 u0 = unite(bo, b2), u1 = unite(b1, bo); // `other` takes the place of A.left / of A.right
-        const float g0 = before - boxArea(u0), g1 = before - boxArea(u1);
-        if (g0 > bestGain) bestGain = g0, best = 2 * side, bestBox = u0;
-        if (g1 > bestGain) bestGain = g1, best = 2 * side + 1, bestBox = u1;
-    }
-    if (best < 0) return;
-    const int side = best >> 1;
-    const int inner = side == 0 ? N.left : N.right, other = side == 0 ? N.right : N.left;
-    KNode A = nodes[inner];
-    int moved; // the grandchild that becomes N's direct child
-    if (best & 1)
-        moved = A.right, A.right = other;
-    else
-        moved = A.left, A.left = other;
-    KNode M = N;
-    if (side == 0)
-        M.right = moved;
-    else
-        M.left = moved;
-    nodes[inner] = A;
-    nodes[i] = M;
-    nodeBox[inner] = bestBox;
-    atomicAdd(applied, 1u);
-}
-
-// Collapse the binary tree into 4-wide nodes, one tree level per launch.  binOf[i] is the binary (Karras)
-// node that 4-wide node i stands for.  Starting from its two children, the inner child with the largest
-// surface area is replaced by its own two children until four children exist (or none can be opened).
-// Leaves hold ONE triangle.  The inner children of a node are appended together through one atomic reservation
-// (siblings become neighbours in memory), and so are its triangles, which are copied to their final place.
-HRD float boxArea(const Box6 &b)
-{
-    const float dx = b.hi[0] - b.lo[0], dy = b.hi[1] - b.lo[1], dz = b.hi[2] - b.lo[2];
-    return dx * dy + dy * dz + dz * dx;
-}
-
-// (C1, C2, C3, C4) of a binary node from its children's (see k_refit_round); a triangle child (ref < 0) costs nothing
-HRD float4 collapseCost(int left, int right, float area, const float4 *__restrict__ cost)
-{
-    const float4 z = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
-    const float4 cl = left < 0 ? z : cost[left], cr = right < 0 ? z : cost[right];
-    const float h2 = cl.x + cr.x;
-    const float h3 = fmin_(cl.x + cr.y, cl.y + cr.x);
-    const float h4 = fmin_(cl.x + cr.z, fmin_(cl.y + cr.y, cl.z + cr.x));
-    const float c1 = area + h4;
-    const float c2 = fmin_(c1, h2), c3 = fmin_(c2, h3), c4 = fmin_(c3, h4);
-    return make_float4(c1, c2, c3, c4);
 }
 
 // biased exponent e (1..254) of the smallest power of two s = 2^(e-127) with ext / s <= 255
@@ -511,6 +444,11 @@ HRD Node4 encodeNode4(const Box6 *cb, const Box6 &nb, int nValid, int nInner, ui
     return nd;
 }
 
+// Collapse the binary tree into 4-wide nodes, one tree level per launch.  binOf[i] is the binary (Karras)
+// node that 4-wide node i stands for.  Its (up to four) children are the descendants of that node which make the summed surface
+// area of the 4-wide nodes below the least (the costs of k_refit_round).
+// Leaves hold ONE triangle.  The inner children of a node are appended together through one atomic reservation
+// (siblings become neighbours in memory), and so are its triangles, which are copied to their final place.
 __global__ __launch_bounds__(256) void k_collapse4(const KNode *__restrict__ knodes, const Box6 *__restrict__ leafBox,
                                                    const Box6 *__restrict__ nodeBox, int *__restrict__ binOf, uint32_t levelStart,
                                                    uint32_t levelEnd, uint32_t *__restrict__ counter, uint32_t *__restrict__ leafCounter,
@@ -521,56 +459,34 @@ __global__ __launch_bounds__(256) void k_collapse4(const KNode *__restrict__ kno
     if (i >= levelEnd) return;
     const int b = binOf[i];
     int cand[4];
-    int n = 2;
-    if (cost) {
-        // The children that minimise the summed area of the nodes below (k_refit_round's costs): binary node b is opened over four slots;
-        // a child with a budget of k slots stays one child (a node of its own, or a triangle) unless opening it over those slots is cheaper.
-        auto costOf = [&](int ref, int k) -> float {
-            if (ref < 0) return 0.0f;
-            const float4 c = cost[ref];
-            return k == 1 ? c.x : (k == 2 ? c.y : (k == 3 ? c.z : c.w));
-        };
-        int stackRef[4], stackK[4], sp = 0;
-        n = 0;
-        stackRef[sp] = b, stackK[sp] = 4, ++sp;
-        bool first = true;
-        while (sp > 0) {
-            --sp;
-            const int ref = stackRef[sp], k = stackK[sp];
-            const bool open = first || (ref >= 0 && k >= 2 && costOf(ref, k) < costOf(ref, 1));
-            first = false;
-            if (!open) {
-                cand[n++] = ref;
-                continue;
-            }
-            const int L = knodes[ref].left, R = knodes[ref].right;
-            int bestL = 1;
-            float best = costOf(L, 1) + costOf(R, k - 1);
-            for (int jl = 2; jl < k; ++jl) {
-                const float c = costOf(L, jl) + costOf(R, k - jl);
-                if (c < best) best = c, bestL = jl;
-            }
-            stackRef[sp] = R, stackK[sp] = k - bestL, ++sp;
-            stackRef[sp] = L, stackK[sp] = bestL, ++sp;
+    // The children that minimise the summed area of the nodes below (k_refit_round's costs): binary node b is opened over four slots;
+    // a child with a budget of k slots stays one child (a node of its own, or a triangle) unless opening it over those slots is cheaper.
+    auto costOf = [&](int ref, int k) -> float {
+        if (ref < 0) return 0.0f;
+        const float4 c = cost[ref];
+        return k == 1 ? c.x : (k == 2 ? c.y : (k == 3 ? c.z : c.w));
+    };
+    int stackRef[4], stackK[4], sp = 0, n = 0;
+    stackRef[sp] = b, stackK[sp] = 4, ++sp;
+    bool first = true;
+    while (sp > 0) {
+        --sp;
+        const int ref = stackRef[sp], k = stackK[sp];
+        const bool open = first || (ref >= 0 && k >= 2 && costOf(ref, k) < costOf(ref, 1));
+        first = false;
+        if (!open) {
+            cand[n++] = ref;
+            continue;
         }
-    } else
-    {
-    cand[0] = knodes[b].left, cand[1] = knodes[b].right;
-    cand[2] = cand[3] = 0;
-    for (int round = 0; round < 2; ++round) {
-        int pick = -1;
-        float bestArea = -1.0f;
-        for (int c = 0; c < n; ++c) {
-            const int ref = cand[c];
-            if (ref < 0) continue; // a single triangle
-            const float a = boxArea(nodeBox[ref]);
-            if (a > bestArea) bestArea = a, pick = c;
+        const int L = knodes[ref].left, R = knodes[ref].right;
+        int bestL = 1;
+        float best = costOf(L, 1) + costOf(R, k - 1);
+        for (int jl = 2; jl < k; ++jl) {
+            const float c = costOf(L, jl) + costOf(R, k - jl);
+            if (c < best) best = c, bestL = jl;
         }
-        if (pick < 0) break;
-        const int ref = cand[pick];
-        cand[pick] = knodes[ref].left;
-        cand[n++] = knodes[ref].right;
-    }
+        stackRef[sp] = R, stackK[sp] = k - bestL, ++sp;
+        stackRef[sp] = L, stackK[sp] = bestL, ++sp;
     }
     // inner children first, triangles after them (the order of the children inside a node is free)
     int ord[4];
@@ -1124,289 +1040,294 @@ __global__ __launch_bounds__(kPlocTail) void k_ploc_tail(uint32_t *__restrict__ 
     if (t == 0) state[0] = (uint32_t)m, state[1] = base;
 }
 
+// ------------------------------------------------------------------------------ the build on the host
+namespace {
+// Device scratch of a build: every array it hands out is freed when the holder goes out of scope, on whichever path its function is left.
+struct Scratch {
+    std::vector<void *> held;
+    Scratch() = default;
+    Scratch(const Scratch &) = delete;
+    ~Scratch() { for (void *p : held) hipFree(p); }
+    template <class T> bool alloc(T *&p, size_t count)
+    {
+        if (hipMalloc(&p, sizeof(T) * count) != hipSuccess) return false;
+        held.push_back(p);
+        return true;
+    }
+    // the array stops being scratch: it is the caller's from here on
+    template <class T> T *release(T *p)
+    {
+        held.erase(std::remove(held.begin(), held.end(), (void *)p), held.end());
+        return p;
+    }
+};
+
+// What the stages of buildLBVH hand to one another.  A stage returns 0 or the build's return code; `mem` frees everything on every path.
+struct Build {
+    hipStream_t st;
+    uint32_t n; // triangles
+    const BuildOptions &opt;
+    BuildResult *out;
+    Scratch mem;
+    uint32_t *keys = nullptr;                     // sortByMorton: the sorted keys,
+    Tri *sorted = nullptr, *finalTris = nullptr;  // the triangles in their order (collapse: in leaf order)
+    Box6 *leafBox = nullptr;                      // and their padded boxes
+    int nInternal = 0;                            // radixTree: n - 1 binary nodes, the root is node 0
+    uint32_t gi = 0;                              // workgroups of a launch over them
+    KNode *knodes = nullptr, *pKnodes = nullptr;  // the radix tree (sahSubtrees rewrites parts of it) and plocCandidate's tree: nodes,
+    Box6 *nodeBox = nullptr, *pBox = nullptr;     // boxes
+    float4 *cost = nullptr, *pCost = nullptr;     // and costs of the collapse (k_refit_round, k_collapse4)
+    uint32_t *stamp = nullptr, rootStamp = 0;     // the round that finished each radix node; the root's = the tree's height
+    int pRoot = 0;                                // the PLOC tree's root
+    bool usePloc = false;                         // ... and whether it is the tree to collapse
+};
+} // namespace
+
+// Refit rounds (k_refit_round) numbered from `first` until the root is stamped, `limit` rounds at the most; the host looks at the root's
+// stamp after every 16th round counted from the first.  b.rootStamp = what it saw last (0: the root was not finished at that look).
+static int refitToRoot(Build &b, uint32_t first, uint32_t limit)
+{
+    b.rootStamp = 0;
+    for (uint32_t k = 1; k <= limit && b.rootStamp == 0; ++k) {
+        hipLaunchKernelGGL(k_refit_round, dim3(b.gi), dim3(256), 0, b.st, b.knodes, b.nInternal, b.leafBox, b.nodeBox, b.stamp, first + k - 1u, b.cost);
+        if ((k & 15u) == 0u) {
+            HR_CHECK(hipMemcpyAsync(&b.rootStamp, b.stamp, 4, hipMemcpyDeviceToHost, b.st));
+            HR_CHECK(hipStreamSynchronize(b.st));
+        }
+    }
+    return 0;
+}
+
+// a tree's collapse cost C1 over the surface area of the root's box (0 for a flat root): what BuildResult reports
+static float costOverRootArea(const float4 &c, const Box6 &root)
+{
+    const float dx = root.hi[0] - root.lo[0], dy = root.hi[1] - root.lo[1], dz = root.hi[2] - root.lo[2];
+    const float ra = dx * dy + dy * dz + dz * dx;
+    return ra > 0.0f ? c.x / ra : 0.0f;
+}
+
+static int sortByMorton(Build &b, const Tri *trisPrim, const float lo[3], const float hi[3], float pad)
+{
+    const uint32_t n = b.n, nBlocks = (n + kSortTile - 1) / kSortTile, g256 = (n + 255) / 256;
+    uint32_t *keysA, *keysB, *valsA, *valsB, *blockHist;
+    if (!(b.mem.alloc(keysA, n) && b.mem.alloc(keysB, n) && b.mem.alloc(valsA, n) && b.mem.alloc(valsB, n) && b.mem.alloc(blockHist, 256ull * nBlocks) &&
+          b.mem.alloc(b.sorted, n) && b.mem.alloc(b.leafBox, n)))
+        return 1;
+    const v3 vlo(lo[0], lo[1], lo[2]);
+    const v3 ext(hi[0] - lo[0], hi[1] - lo[1], hi[2] - lo[2]);
+    hipLaunchKernelGGL(k_morton, dim3(g256), dim3(256), 0, b.st, trisPrim, n, vlo, ext, keysA, valsA);
+    for (int pass = 0; pass < 4; ++pass) {
+        const int shift = pass * 8;
+        hipLaunchKernelGGL(k_sort_hist, dim3(nBlocks), dim3(64), 0, b.st, keysA, n, shift, blockHist, nBlocks);
+        hipLaunchKernelGGL(k_scan_single, dim3(1), dim3(1024), 0, b.st, blockHist, 256u * nBlocks, (uint32_t *)nullptr);
+        hipLaunchKernelGGL(k_sort_scatter, dim3(nBlocks), dim3(64), 0, b.st, keysA, valsA, n, shift, blockHist, nBlocks, keysB, valsB);
+        std::swap(keysA, keysB);
+        std::swap(valsA, valsB);
+    }
+    hipLaunchKernelGGL(k_gather_tris, dim3(g256), dim3(256), 0, b.st, trisPrim, valsA, n, b.sorted, pad, b.leafBox);
+    b.keys = keysA;
+    return 0;
+}
+
+// the radix tree over the sorted keys, with its boxes and collapse costs
+static int radixTree(Build &b)
+{
+    b.nInternal = (int)b.n - 1;
+    b.gi = (uint32_t)(b.nInternal + 255) / 256;
+    if (!(b.mem.alloc(b.knodes, b.nInternal) && b.mem.alloc(b.nodeBox, b.nInternal) && b.mem.alloc(b.stamp, b.nInternal) && b.mem.alloc(b.cost, b.nInternal)))
+        return 1;
+    HR_CHECK(hipMemsetAsync(b.stamp, 0, 4ull * b.nInternal, b.st));
+    hipLaunchKernelGGL(k_karras, dim3(b.gi), dim3(256), 0, b.st, b.keys, (int)b.n, b.knodes);
+    // tree height <= 30 key bits + 28 index bits
+    if (int rc = refitToRoot(b, 1u, 64u)) return rc;
+    return b.rootStamp == 0 ? 3 : 0; // (the last of the 64 rounds is one the host looks after)
+}
+
+// the radix tree's bottom subtrees rebuilt by full-sweep SAH (k_sah_subtrees), then the nodes above them refitted again
+static int sahSubtrees(Build &b)
+{
+    const int sahT = b.opt.sahSub > kSahMax ? kSahMax : b.opt.sahSub;
+    if (sahT < 3 || b.n <= (uint32_t)sahT) return 0;
+    const uint32_t maxWork = b.n / 3u + 1u;
+    Scratch mem;
+    SahWork *work;
+    uint32_t *counters; // [0] subtrees found, [1] replaced
+    float4 c0{}, c1{};
+    Box6 rootBox{};
+    uint32_t found[2] = {0u, 0u};
+    if (!(mem.alloc(work, maxWork) && mem.alloc(counters, 2))) return 1;
+    HR_CHECK(hipMemsetAsync(counters, 0, 8, b.st));
+    hipLaunchKernelGGL(k_sah_find, dim3(b.gi), dim3(256), 0, b.st, b.knodes, b.nInternal, sahT, b.stamp, work, maxWork, counters);
+    HR_CHECK(hipMemcpyAsync(found, counters, 4, hipMemcpyDeviceToHost, b.st));
+    HR_CHECK(hipMemcpyAsync(&c0, b.cost, sizeof(float4), hipMemcpyDeviceToHost, b.st));
+    HR_CHECK(hipMemcpyAsync(&rootBox, b.nodeBox, sizeof(Box6), hipMemcpyDeviceToHost, b.st));
+    HR_CHECK(hipStreamSynchronize(b.st));
+    if (found[0] > maxWork) return 8; // (cannot happen: see k_sah_find)
+    if (found[0] > 0u) hipLaunchKernelGGL(k_sah_subtrees, dim3(found[0]), dim3(64), 0, b.st, b.knodes, b.leafBox, b.nodeBox, b.cost, b.stamp, work, counters);
+    // (k_sah_find has cleared the stamps of the nodes above: the old stamps below them are <= rootStamp, the new ones 1)
+    if (int rc = refitToRoot(b, b.rootStamp + 1u, 64u)) return rc;
+    HR_CHECK(hipMemcpyAsync(&b.rootStamp, b.stamp, 4, hipMemcpyDeviceToHost, b.st));
+    HR_CHECK(hipMemcpyAsync(found + 1, counters + 1, 4, hipMemcpyDeviceToHost, b.st));
+    HR_CHECK(hipMemcpyAsync(&c1, b.cost, sizeof(float4), hipMemcpyDeviceToHost, b.st));
+    HR_CHECK(hipStreamSynchronize(b.st));
+    if (b.rootStamp == 0) return 3;
+    b.out->sahCostBefore = costOverRootArea(c0, rootBox), b.out->sahCostAfter = costOverRootArea(c1, rootBox);
+    b.out->sahFound = found[0], b.out->sahReplaced = found[1];
+    return 0;
+}
+
 // Binary tree over the sorted triangles by PLOC: knodes / nodeBox / cost have n - 1 entries; *rootOut is the root's index (n - 2).
 // Returns 0, or non-zero when it did not finish (the caller then keeps the radix tree).
 static int buildPLOC(hipStream_t st, const Box6 *leafBox, uint32_t n, int radius, KNode *knodes, Box6 *nodeBox, float4 *cost, int *rootOut)
 {
-    int *ref[2] = {nullptr, nullptr};
-    Box6 *box[2] = {nullptr, nullptr};
-    uint32_t *nn = nullptr, *state = nullptr;
-    unsigned long long *sums = nullptr;
+    Scratch mem;
+    int *ref[2];
+    Box6 *box[2];
+    uint32_t *nn, *state;
+    unsigned long long *sums;
     const uint32_t nb0 = (n + 255) / 256;
-    bool ok = hipMalloc(&ref[0], 4ull * n) == hipSuccess && hipMalloc(&ref[1], 4ull * n) == hipSuccess && hipMalloc(&box[0], sizeof(Box6) * (size_t)n) == hipSuccess &&
-              hipMalloc(&box[1], sizeof(Box6) * (size_t)n) == hipSuccess && hipMalloc(&nn, 4ull * n) == hipSuccess && hipMalloc(&state, 16) == hipSuccess &&
-              hipMalloc(&sums, 8ull * nb0) == hipSuccess;
+    if (!(mem.alloc(ref[0], n) && mem.alloc(ref[1], n) && mem.alloc(box[0], n) && mem.alloc(box[1], n) && mem.alloc(nn, n) && mem.alloc(state, 4) &&
+          mem.alloc(sums, nb0)))
+        return 1;
     const uint32_t init[4] = {n, 0u, 0u, 0u};
-    ok = ok && hipMemcpyAsync(state, init, 16, hipMemcpyHostToDevice, st) == hipSuccess;
-    int rc = ok ? 0 : 1;
-    if (ok) {
-        hipLaunchKernelGGL(k_ploc_init, dim3(nb0), dim3(256), 0, st, leafBox, n, ref[0], box[0]);
-        const int r = radius < 1 ? 1 : (radius > HR_PLOC_RADIUS_MAX ? HR_PLOC_RADIUS_MAX : radius);
-        uint32_t m = n;
-        int cur = 0;
-        // every iteration merges at least one pair (k_ploc_nn), typically a third of the clusters: ~45 iterations for a million
-        // triangles.  The host reads the cluster count back after each (a 4-byte copy: the launches are sized by it).
-        for (uint32_t it = 0; m > (uint32_t)kPlocTail; ++it) {
-            if (it >= 4096u) { // (a pathological input that merges a pair at a time: not worth it, the radix tree is kept)
-                rc = 7;
-                break;
-            }
-            const uint32_t nb = (m + 255) / 256;
-            hipLaunchKernelGGL(k_ploc_nn, dim3(nb), dim3(256), 0, st, box[cur], state, r, nn);
-            hipLaunchKernelGGL((k_ploc_merge<0>), dim3(nb), dim3(256), 0, st, state, nn, ref[cur], box[cur], sums, ref[cur ^ 1], box[cur ^ 1], knodes, nodeBox, cost);
-            hipLaunchKernelGGL(k_ploc_scan, dim3(1), dim3(1024), 0, st, sums, state);
-            hipLaunchKernelGGL((k_ploc_merge<1>), dim3(nb), dim3(256), 0, st, state, nn, ref[cur], box[cur], sums, ref[cur ^ 1], box[cur ^ 1], knodes, nodeBox, cost);
-            hipLaunchKernelGGL(k_ploc_advance, dim3(1), dim3(1), 0, st, state);
-            uint32_t mNew = 0;
-            if (hipMemcpyAsync(&mNew, state, 4, hipMemcpyDeviceToHost, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess) {
-                rc = 1;
-                break;
-            }
-            if (mNew >= m || mNew == 0) { // (cannot happen: see k_ploc_nn)
-                rc = 7;
-                break;
-            }
-            m = mNew;
-            cur ^= 1;
-        }
-        if (rc == 0 && m > 1) hipLaunchKernelGGL(k_ploc_tail, dim3(1), dim3(kPlocTail), 0, st, state, ref[cur], box[cur], r, knodes, nodeBox, cost);
-        uint32_t made = 0;
-        if (rc == 0 && (hipMemcpyAsync(&made, state + 1, 4, hipMemcpyDeviceToHost, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess)) rc = 1;
-        if (rc == 0 && made != n - 1) rc = 7;
-        *rootOut = (int)n - 2;
+    HR_CHECK(hipMemcpyAsync(state, init, 16, hipMemcpyHostToDevice, st));
+    hipLaunchKernelGGL(k_ploc_init, dim3(nb0), dim3(256), 0, st, leafBox, n, ref[0], box[0]);
+    const int r = radius < 1 ? 1 : (radius > HR_PLOC_RADIUS_MAX ? HR_PLOC_RADIUS_MAX : radius);
+    uint32_t m = n;
+    int cur = 0;
+    // every iteration merges at least one pair (k_ploc_nn), typically a third of the clusters: ~45 iterations for a million
+    // triangles.  The host reads the cluster count back after each (a 4-byte copy: the launches are sized by it).
+    for (uint32_t it = 0; m > (uint32_t)kPlocTail; ++it) {
+        if (it >= 4096u) return 7; // (a pathological input that merges a pair at a time: not worth it, the radix tree is kept)
+        const uint32_t nb = (m + 255) / 256;
+        hipLaunchKernelGGL(k_ploc_nn, dim3(nb), dim3(256), 0, st, box[cur], state, r, nn);
+        hipLaunchKernelGGL((k_ploc_merge<0>), dim3(nb), dim3(256), 0, st, state, nn, ref[cur], box[cur], sums, ref[cur ^ 1], box[cur ^ 1], knodes, nodeBox, cost);
+        hipLaunchKernelGGL(k_ploc_scan, dim3(1), dim3(1024), 0, st, sums, state);
+        hipLaunchKernelGGL((k_ploc_merge<1>), dim3(nb), dim3(256), 0, st, state, nn, ref[cur], box[cur], sums, ref[cur ^ 1], box[cur ^ 1], knodes, nodeBox, cost);
+        hipLaunchKernelGGL(k_ploc_advance, dim3(1), dim3(1), 0, st, state);
+        uint32_t mNew = 0;
+        HR_CHECK(hipMemcpyAsync(&mNew, state, 4, hipMemcpyDeviceToHost, st));
+        HR_CHECK(hipStreamSynchronize(st));
+        if (mNew >= m || mNew == 0) return 7; // (cannot happen: see k_ploc_nn)
+        m = mNew;
+        cur ^= 1;
     }
-    hipFree(ref[0]), hipFree(ref[1]), hipFree(box[0]), hipFree(box[1]), hipFree(nn), hipFree(state), hipFree(sums);
-    return rc;
+    if (m > 1) hipLaunchKernelGGL(k_ploc_tail, dim3(1), dim3(kPlocTail), 0, st, state, ref[cur], box[cur], r, knodes, nodeBox, cost);
+    uint32_t made = 0;
+    HR_CHECK(hipMemcpyAsync(&made, state + 1, 4, hipMemcpyDeviceToHost, st));
+    HR_CHECK(hipStreamSynchronize(st));
+    *rootOut = (int)n - 2;
+    return made == n - 1 ? 0 : 7;
 }
 
+// The second candidate: the PLOC tree over the same sorted triangles; the one whose collapse costs less (summed surface area of the
+// 4-wide nodes = expected node visits of a random ray) is kept.  A PLOC tree that could not be built is no error: the radix tree stays.
+static int plocCandidate(Build &b)
+{
+    if (b.opt.ploc == 0 || b.n < 4u) return 0;
+    bool ok = b.mem.alloc(b.pKnodes, b.nInternal) && b.mem.alloc(b.pBox, b.nInternal) && b.mem.alloc(b.pCost, b.nInternal) &&
+              buildPLOC(b.st, b.leafBox, b.n, b.opt.plocRadius, b.pKnodes, b.pBox, b.pCost, &b.pRoot) == 0;
+    float4 cR{}, cP{};
+    Box6 rootBox{};
+    ok = ok && hipMemcpyAsync(&cR, b.cost, sizeof(float4), hipMemcpyDeviceToHost, b.st) == hipSuccess &&
+         hipMemcpyAsync(&cP, b.pCost + b.pRoot, sizeof(float4), hipMemcpyDeviceToHost, b.st) == hipSuccess &&
+         hipMemcpyAsync(&rootBox, b.nodeBox, sizeof(Box6), hipMemcpyDeviceToHost, b.st) == hipSuccess && hipStreamSynchronize(b.st) == hipSuccess;
+    if (ok) {
+        b.out->costRadix = costOverRootArea(cR, rootBox), b.out->costPloc = costOverRootArea(cP, rootBox);
+        // PLOC has to win clearly (5 %): the surface-area measure assumes rays distributed like random lines through the root box,
+        // while real rays concentrate where the geometry is — the benchmark soup inside a room (c3d) rates PLOC 2.3 % cheaper
+        // because of the room's 18 large triangles and traces 4.3 % SLOWER with it (the soup itself suits the radix tree's regular
+        // cells: PLOC 4.9 % dearer, 3 % slower); a mesh gains far more than the margin (terrain: 26.5 % cheaper, 18 % fewer node
+        // visits per ray, +5.5 % Mrays/s) — profiles/r4j_ploc_ab.txt, r4k_tree_costs.txt
+        b.usePloc = b.opt.ploc >= 2 || cP.x < 0.95f * cR.x;
+    }
+    (void)hipGetLastError();
+    return 0;
+}
+
+// The chosen binary tree collapsed to 4-wide nodes, one level per launch, into the BuildResult's arrays (the caller's to free).
+static int collapse(Build &b, const SceneConsts *dConsts)
+{
+    BuildResult *out = b.out;
+    const uint32_t n = b.n, nMax = (uint32_t)b.nInternal; // every 4-wide node stands for one binary inner node
+    uint32_t *total; // [0] nodes appended, [1] triangles placed
+    int *binOf;
+    if (!(b.mem.alloc(b.finalTris, n) && b.mem.alloc(total, 2) && b.mem.alloc(binOf, nMax))) return 1;
+    HR_CHECK(hipMalloc(&out->nodes, sizeof(Node4) * (size_t)nMax));
+    HR_CHECK(hipMalloc(&out->nodes32, sizeof(Node32) * (size_t)nMax));
+    HR_CHECK(hipMalloc(&out->leafKeys, sizeof(int) * (size_t)nMax));
+    HR_CHECK(hipMalloc(&out->nodeBox, sizeof(Box6) * (size_t)nMax));
+    uint32_t levelStart = 0, levelEnd = 1;
+    for (int attempt = 0; attempt < 2; ++attempt) {
+        const KNode *bk = b.usePloc ? b.pKnodes : b.knodes;
+        const Box6 *bb = b.usePloc ? b.pBox : b.nodeBox;
+        const float4 *bc = b.usePloc ? b.pCost : b.cost;
+        const int rootBin = b.usePloc ? b.pRoot : 0;
+        const uint32_t init[2] = {1u, 0u};
+        HR_CHECK(hipMemcpyAsync(binOf, &rootBin, 4, hipMemcpyHostToDevice, b.st));
+        HR_CHECK(hipMemcpyAsync(total, init, 8, hipMemcpyHostToDevice, b.st));
+        levelStart = 0, levelEnd = 1;
+        out->levels = 0;
+        // (the radix tree is at most 58 levels deep — its key length; a PLOC tree has no such bound, so it is only kept when its collapse
+        // fits the traversal stack; otherwise the second attempt collapses the radix tree)
+        const int levelCap = b.usePloc ? (b.opt.maxLevels < 64 ? b.opt.maxLevels : 64) : 64;
+        for (int level = 0; level < levelCap && levelEnd > levelStart; ++level) {
+            const uint32_t cnt = levelEnd - levelStart;
+            hipLaunchKernelGGL(k_collapse4, dim3((cnt + 255) / 256), dim3(256), 0, b.st, bk, b.leafBox, bb, binOf, levelStart, levelEnd, total, total + 1,
+                               b.sorted, b.finalTris, out->nodes, out->nodeBox, dConsts, bc);
+            uint32_t newEnd = 0;
+            HR_CHECK(hipMemcpyAsync(&newEnd, total, 4, hipMemcpyDeviceToHost, b.st));
+            HR_CHECK(hipStreamSynchronize(b.st));
+            if (newEnd > nMax) return 4;
+            out->levelStart[level] = levelStart, out->levelStart[level + 1] = levelEnd;
+            levelStart = levelEnd;
+            levelEnd = newEnd;
+            out->levels = level + 1;
+        }
+        if (!(levelEnd > levelStart && b.usePloc)) break;
+        b.usePloc = false; // too deep for the stack: fall back to the radix tree
+    }
+    out->builder = b.usePloc ? 1 : 0;
+    if (levelEnd > levelStart) return 6; // deeper than the key length allows: cannot happen with n < 2^28
+    out->nNodes = (int)levelEnd;
+    uint32_t placed = 0;
+    HR_CHECK(hipMemcpyAsync(&placed, total + 1, 4, hipMemcpyDeviceToHost, b.st));
+    HR_CHECK(hipStreamSynchronize(b.st));
+    return placed == n ? 0 : 5; // every triangle is the leaf of exactly one node
+}
+
+// the triangles in leaf order become the result's, with the way back from a prim id to its slot
+static int leafOrder(Build &b)
+{
+    BuildResult *out = b.out;
+    out->tris = b.mem.release(b.finalTris ? b.finalTris : b.sorted);
+    out->triSlots = b.n;
+    HR_CHECK(hipMalloc(&out->slotOfPrim, 4ull * b.n));
+    hipLaunchKernelGGL(k_slot_of_prim, dim3((out->triSlots + 255) / 256), dim3(256), 0, b.st, out->tris, out->triSlots, out->slotOfPrim);
+    HR_CHECK(hipStreamSynchronize(b.st));
+    return hipGetLastError() != hipSuccess ? 1 : 0;
+}
+
+// Returns 0 or: 1 a HIP call failed, 2 too many triangles, 3 a refit did not reach the root, 4 / 5 / 6 the collapse made too many nodes /
+// lost a triangle / is too deep, 8 more SAH work items than triangles allow (7, PLOC did not finish, never leaves: the radix tree is kept).
+// The first stage that fails ends the build; the arrays of *out allocated by then are the caller's to free, like those of a finished build.
 int buildLBVH(hipStream_t st, const Tri *trisPrim, uint32_t n, const float lo[3], const float hi[3], float pad, const SceneConsts *dConsts,
               BuildResult *out, const BuildOptions &opt)
 {
-    out->nodes = nullptr, out->nodes32 = nullptr, out->leafKeys = nullptr, out->tris = nullptr, out->nodeBox = nullptr, out->slotOfPrim = nullptr;
-    out->nNodes = 0, out->rootLeafCount = 0, out->levels = 0, out->triSlots = 0;
-    out->builder = 0, out->costRadix = out->costPloc = 0.0f;
-    out->sahCostBefore = out->sahCostAfter = 0.0f, out->sahFound = out->sahReplaced = 0u;
-    for (uint32_t &v : out->levelStart) v = 0;
+    *out = BuildResult{};
     if (n == 0) return 0;
     if (n >= (1u << 28)) return 2;
-    const uint32_t nBlocks = (n + kSortTile - 1) / kSortTile;
-    uint32_t *keysA = nullptr, *keysB = nullptr, *valsA = nullptr, *valsB = nullptr, *blockHist = nullptr, *stamp = nullptr, *total = nullptr;
-    Tri *finalTris = nullptr;
-    KNode *knodes = nullptr;
-    Box6 *leafBox = nullptr, *nodeBox = nullptr;
-    Tri *sorted = nullptr;
-    float4 *dpCost = nullptr; // costs of the collapse (k_refit_round, k_collapse4)
-    HR_CHECK(hipMalloc(&keysA, 4ull * n));
-    HR_CHECK(hipMalloc(&keysB, 4ull * n));
-    HR_CHECK(hipMalloc(&valsA, 4ull * n));
-    HR_CHECK(hipMalloc(&valsB, 4ull * n));
-    HR_CHECK(hipMalloc(&blockHist, 4ull * 256 * nBlocks));
-    HR_CHECK(hipMalloc(&sorted, sizeof(Tri) * (size_t)n));
-    HR_CHECK(hipMalloc(&leafBox, sizeof(Box6) * (size_t)n));
-    HR_CHECK(hipMalloc(&total, 8)); // [0] nodes appended, [1] triangles placed
-    const v3 vlo(lo[0], lo[1], lo[2]);
-    const v3 ext(hi[0] - lo[0], hi[1] - lo[1], hi[2] - lo[2]);
-    const uint32_t g256 = (n + 255) / 256;
-    hipLaunchKernelGGL(k_morton, dim3(g256), dim3(256), 0, st, trisPrim, n, vlo, ext, keysA, valsA);
-    for (int pass = 0; pass < 4; ++pass) {
-        const int shift = pass * 8;
-        hipLaunchKernelGGL(k_sort_hist, dim3(nBlocks), dim3(64), 0, st, keysA, n, shift, blockHist, nBlocks);
-        hipLaunchKernelGGL(k_scan_single, dim3(1), dim3(1024), 0, st, blockHist, 256u * nBlocks, (uint32_t *)nullptr);
-        hipLaunchKernelGGL(k_sort_scatter, dim3(nBlocks), dim3(64), 0, st, keysA, valsA, n, shift, blockHist, nBlocks, keysB, valsB);
-        std::swap(keysA, keysB);
-        std::swap(valsA, valsB);
-    }
-    hipLaunchKernelGGL(k_gather_tris, dim3(g256), dim3(256), 0, st, trisPrim, valsA, n, sorted, pad, leafBox);
-    int rc = 0;
+    Build b{st, n, opt, out};
+    if (int rc = sortByMorton(b, trisPrim, lo, hi, pad)) return rc;
     if (n <= 1u) { // a single triangle: the root is a leaf
         out->rootLeafCount = (int)n;
     } else {
-        const int nInternal = (int)n - 1;
-        const uint32_t gi = (nInternal + 255) / 256;
-        HR_CHECK(hipMalloc(&knodes, sizeof(KNode) * (size_t)nInternal));
-        HR_CHECK(hipMalloc(&nodeBox, sizeof(Box6) * (size_t)nInternal));
-        HR_CHECK(hipMalloc(&stamp, 4ull * nInternal));
-        HR_CHECK(hipMemsetAsync(stamp, 0, 4ull * nInternal, st));
-#if HR_COLLAPSE_DP
-        HR_CHECK(hipMalloc(&dpCost, sizeof(float4) * (size_t)nInternal));
-#endif
-        hipLaunchKernelGGL(k_karras, dim3(gi), dim3(256), 0, st, keysA, (int)n, knodes);
-        // tree height <= 30 key bits + 28 index bits; check the root every 16 rounds
-        uint32_t rootStamp = 0;
-        for (uint32_t round = 1; round <= 64 && rootStamp == 0; ++round) {
-            hipLaunchKernelGGL(k_refit_round, dim3(gi), dim3(256), 0, st, knodes, nInternal, leafBox, nodeBox, stamp, round, dpCost);
-            if ((round & 15u) == 0u) {
-                HR_CHECK(hipMemcpyAsync(&rootStamp, stamp, 4, hipMemcpyDeviceToHost, st));
-                HR_CHECK(hipStreamSynchronize(st));
-            }
-        }
-        if (rootStamp == 0) {
-            HR_CHECK(hipMemcpyAsync(&rootStamp, stamp, 4, hipMemcpyDeviceToHost, st));
-            HR_CHECK(hipStreamSynchronize(st));
-        }
-        if (rootStamp == 0) rc = 3;
-#if HR_ROTATE_SWEEPS
-        // tree rotations, bottom-up by stamp; between sweeps the refit rounds renew boxes and stamps (the heights have changed)
-        for (int sweep = 0; sweep < HR_ROTATE_SWEEPS && rc == 0; ++sweep) {
-            HR_CHECK(hipMemsetAsync(total, 0, 4, st));
-            for (uint32_t sv = 2; sv <= rootStamp; ++sv)
-                hipLaunchKernelGGL(k_rotate, dim3(gi), dim3(256), 0, st, knodes, nInternal, leafBox, nodeBox, stamp, sv, total);
-            HR_CHECK(hipMemsetAsync(stamp, 0, 4ull * nInternal, st));
-            rootStamp = 0;
-            for (uint32_t round = 1; round <= 96 && rootStamp == 0; ++round) {
-                hipLaunchKernelGGL(k_refit_round, dim3(gi), dim3(256), 0, st, knodes, nInternal, leafBox, nodeBox, stamp, round, dpCost);
-                if ((round & 15u) == 0u) {
-                    HR_CHECK(hipMemcpyAsync(&rootStamp, stamp, 4, hipMemcpyDeviceToHost, st));
-                    HR_CHECK(hipStreamSynchronize(st));
-                }
-            }
-            if (rootStamp == 0) {
-                HR_CHECK(hipMemcpyAsync(&rootStamp, stamp, 4, hipMemcpyDeviceToHost, st));
-                HR_CHECK(hipStreamSynchronize(st));
-            }
-            if (rootStamp == 0) rc = 3;
-        }
-#endif
-        // ---- the radix tree's bottom subtrees rebuilt by full-sweep SAH (k_sah_subtrees), then the nodes above them refitted again
-        const int sahT = opt.sahSub > kSahMax ? kSahMax : opt.sahSub;
-        if (rc == 0 && dpCost && sahT >= 3 && n > (uint32_t)sahT) {
-            const uint32_t maxWork = n / 3u + 1u;
-            SahWork *work = nullptr;
-            uint32_t *counters = nullptr; // [0] subtrees found, [1] replaced
-            float4 c0{};
-            Box6 rootBox{};
-            uint32_t found[2] = {0u, 0u};
-            bool ok = hipMalloc(&work, sizeof(SahWork) * (size_t)maxWork) == hipSuccess && hipMalloc(&counters, 8) == hipSuccess &&
-                      hipMemsetAsync(counters, 0, 8, st) == hipSuccess;
-            if (ok) {
-                hipLaunchKernelGGL(k_sah_find, dim3(gi), dim3(256), 0, st, knodes, nInternal, sahT, stamp, work, maxWork, counters);
-                ok = hipMemcpyAsync(found, counters, 4, hipMemcpyDeviceToHost, st) == hipSuccess &&
-                     hipMemcpyAsync(&c0, dpCost, sizeof(float4), hipMemcpyDeviceToHost, st) == hipSuccess &&
-                     hipMemcpyAsync(&rootBox, nodeBox, sizeof(Box6), hipMemcpyDeviceToHost, st) == hipSuccess && hipStreamSynchronize(st) == hipSuccess;
-            }
-            if (ok && found[0] > maxWork) ok = false, rc = 8; // (cannot happen: see k_sah_find)
-            if (ok && found[0] > 0u) hipLaunchKernelGGL(k_sah_subtrees, dim3(found[0]), dim3(64), 0, st, knodes, leafBox, nodeBox, dpCost, stamp, work, counters);
-            if (ok) { // (k_sah_find has cleared the stamps of the nodes above: the old stamps below them are <= rootStamp, the new ones 1)
-                const uint32_t r0 = rootStamp + 1u;
-                rootStamp = 0;
-                for (uint32_t round = r0; round < r0 + 64u && rootStamp == 0; ++round) {
-                    hipLaunchKernelGGL(k_refit_round, dim3(gi), dim3(256), 0, st, knodes, nInternal, leafBox, nodeBox, stamp, round, dpCost);
-                    if (((round - r0 + 1u) & 15u) == 0u) {
-                        HR_CHECK(hipMemcpyAsync(&rootStamp, stamp, 4, hipMemcpyDeviceToHost, st));
-                        HR_CHECK(hipStreamSynchronize(st));
-                    }
-                }
-                float4 c1{};
-                HR_CHECK(hipMemcpyAsync(&rootStamp, stamp, 4, hipMemcpyDeviceToHost, st));
-                HR_CHECK(hipMemcpyAsync(found + 1, counters + 1, 4, hipMemcpyDeviceToHost, st));
-                HR_CHECK(hipMemcpyAsync(&c1, dpCost, sizeof(float4), hipMemcpyDeviceToHost, st));
-                HR_CHECK(hipStreamSynchronize(st));
-                if (rootStamp == 0) rc = 3;
-                const float dx = rootBox.hi[0] - rootBox.lo[0], dy = rootBox.hi[1] - rootBox.lo[1], dz = rootBox.hi[2] - rootBox.lo[2];
-                const float ra = dx * dy + dy * dz + dz * dx;
-                out->sahCostBefore = ra > 0.0f ? c0.x / ra : 0.0f, out->sahCostAfter = ra > 0.0f ? c1.x / ra : 0.0f;
-                out->sahFound = found[0], out->sahReplaced = found[1];
-            }
-            hipFree(work), hipFree(counters);
-            if (!ok && rc == 0) rc = 1; // (the stamps may be cleared: no tree to go on with)
-        }
-        // ---- the second candidate: the PLOC tree over the same sorted triangles; the one whose collapse costs less (summed surface area
-        // of the 4-wide nodes = expected node visits of a random ray) is kept
-        KNode *pKnodes = nullptr;
-        Box6 *pBox = nullptr;
-        float4 *pCost = nullptr;
-        int pRoot = 0;
-        bool usePloc = false;
-        out->costRadix = out->costPloc = 0.0f;
-        if (rc == 0 && dpCost && opt.ploc != 0 && n >= 4u) {
-            bool ok = hipMalloc(&pKnodes, sizeof(KNode) * (size_t)nInternal) == hipSuccess && hipMalloc(&pBox, sizeof(Box6) * (size_t)nInternal) == hipSuccess &&
-                      hipMalloc(&pCost, sizeof(float4) * (size_t)nInternal) == hipSuccess;
-            ok = ok && buildPLOC(st, leafBox, n, opt.plocRadius, pKnodes, pBox, pCost, &pRoot) == 0;
-            float4 cR{}, cP{};
-            Box6 rootBox{};
-            ok = ok && hipMemcpyAsync(&cR, dpCost, sizeof(float4), hipMemcpyDeviceToHost, st) == hipSuccess &&
-                 hipMemcpyAsync(&cP, pCost + pRoot, sizeof(float4), hipMemcpyDeviceToHost, st) == hipSuccess &&
-                 hipMemcpyAsync(&rootBox, nodeBox, sizeof(Box6), hipMemcpyDeviceToHost, st) == hipSuccess && hipStreamSynchronize(st) == hipSuccess;
-            if (ok) {
-                const float dx = rootBox.hi[0] - rootBox.lo[0], dy = rootBox.hi[1] - rootBox.lo[1], dz = rootBox.hi[2] - rootBox.lo[2];
-                const float ra = dx * dy + dy * dz + dz * dx;
-                out->costRadix = ra > 0.0f ? cR.x / ra : 0.0f, out->costPloc = ra > 0.0f ? cP.x / ra : 0.0f;
-                // PLOC has to win clearly (5 %): the surface-area measure assumes rays distributed like random lines through the root box,
-                // while real rays concentrate where the geometry is — the benchmark soup inside a room (c3d) rates PLOC 2.3 % cheaper
-                // because of the room's 18 large triangles and traces 4.3 % SLOWER with it (the soup itself suits the radix tree's regular
-                // cells: PLOC 4.9 % dearer, 3 % slower); a mesh gains far more than the margin (terrain: 26.5 % cheaper, 18 % fewer node
-                // visits per ray, +5.5 % Mrays/s) — profiles/r4j_ploc_ab.txt, r4k_tree_costs.txt
-                usePloc = opt.ploc >= 2 || cP.x < 0.95f * cR.x;
-            }
-            (void)hipGetLastError();
-        }
-        const uint32_t nMax = (uint32_t)nInternal; // every 4-wide node stands for one binary inner node
-        HR_CHECK(hipMalloc(&finalTris, sizeof(Tri) * (size_t)n));
-        int *binOf = nullptr;
-        HR_CHECK(hipMalloc(&out->nodes, sizeof(Node4) * (size_t)nMax));
-        HR_CHECK(hipMalloc(&out->nodes32, sizeof(Node32) * (size_t)nMax));
-        HR_CHECK(hipMalloc(&out->leafKeys, sizeof(int) * (size_t)nMax));
-        HR_CHECK(hipMalloc(&out->nodeBox, sizeof(Box6) * (size_t)nMax));
-        HR_CHECK(hipMalloc(&binOf, 4ull * nMax));
-        uint32_t levelStart = 0, levelEnd = 1;
-        for (int attempt = 0; attempt < 2 && rc == 0; ++attempt) {
-            const KNode *bk = usePloc ? pKnodes : knodes;
-            const Box6 *bb = usePloc ? pBox : nodeBox;
-            const float4 *bc = usePloc ? pCost : dpCost;
-            const int rootBin = usePloc ? pRoot : 0;
-            const uint32_t init[2] = {1u, 0u};
-            HR_CHECK(hipMemcpyAsync(binOf, &rootBin, 4, hipMemcpyHostToDevice, st));
-            HR_CHECK(hipMemcpyAsync(total, init, 8, hipMemcpyHostToDevice, st));
-            levelStart = 0, levelEnd = 1;
-            out->levels = 0;
-            // (the radix tree is at most 58 levels deep — its key length; a PLOC tree has no such bound, so it is only kept when its collapse
-            // fits the traversal stack; otherwise the second attempt collapses the radix tree)
-            const int levelCap = usePloc ? (opt.maxLevels < 64 ? opt.maxLevels : 64) : 64;
-            for (int level = 0; level < levelCap && levelEnd > levelStart; ++level) {
-                const uint32_t cnt = levelEnd - levelStart;
-                hipLaunchKernelGGL(k_collapse4, dim3((cnt + 255) / 256), dim3(256), 0, st, bk, leafBox, bb, binOf, levelStart, levelEnd, total,
-                                   total + 1, sorted, finalTris, out->nodes, out->nodeBox, dConsts, bc);
-                uint32_t newEnd = 0;
-                HR_CHECK(hipMemcpyAsync(&newEnd, total, 4, hipMemcpyDeviceToHost, st));
-                HR_CHECK(hipStreamSynchronize(st));
-                if (newEnd > nMax) {
-                    rc = 4;
-                    break;
-                }
-                out->levelStart[level] = levelStart, out->levelStart[level + 1] = levelEnd;
-                levelStart = levelEnd;
-                levelEnd = newEnd;
-                out->levels = level + 1;
-            }
-            if (rc == 0 && levelEnd > levelStart && usePloc) { // too deep for the stack: fall back to the radix tree
-                usePloc = false;
-                continue;
-            }
-            break;
-        }
-        out->builder = usePloc ? 1 : 0;
-        hipFree(binOf);
-        hipFree(pKnodes), hipFree(pBox), hipFree(pCost);
-        if (levelEnd > levelStart && rc == 0) rc = 6; // deeper than the key length allows: cannot happen with n < 2^28
-        out->nNodes = (int)levelEnd;
-        uint32_t placed = 0;
-        HR_CHECK(hipMemcpyAsync(&placed, total + 1, 4, hipMemcpyDeviceToHost, st));
-        HR_CHECK(hipStreamSynchronize(st));
-        if (placed != n && rc == 0) rc = 5; // every triangle is the leaf of exactly one node
+        if (int rc = radixTree(b)) return rc;
+        if (int rc = sahSubtrees(b)) return rc;
+        if (int rc = plocCandidate(b)) return rc;
+        if (int rc = collapse(b, dConsts)) return rc;
     }
-    out->tris = finalTris ? finalTris : sorted;
-    out->triSlots = n;
-    HR_CHECK(hipMalloc(&out->slotOfPrim, 4ull * n));
-    hipLaunchKernelGGL(k_slot_of_prim, dim3((out->triSlots + 255) / 256), dim3(256), 0, st, out->tris, out->triSlots, out->slotOfPrim);
-    HR_CHECK(hipStreamSynchronize(st));
-    hipFree(keysA), hipFree(keysB), hipFree(valsA), hipFree(valsB), hipFree(blockHist), hipFree(leafBox), hipFree(total);
-    if (knodes) hipFree(knodes);
-    if (nodeBox) hipFree(nodeBox);
-    if (stamp) hipFree(stamp);
-    if (dpCost) hipFree(dpCost);
-    if (finalTris) hipFree(sorted);
-    if (hipGetLastError() != hipSuccess) return 1;
-    return rc;
+    return leafOrder(b);
 }
 
 // ------------------------------------------------------------------------------------ content hash
@@ -1431,521 +1352,6 @@ void launchHashWords(hipStream_t st, const void *words, size_t nWords, unsigned 
     size_t blocks = (nWords + 255) / 256;
     if (blocks > 4096) blocks = 4096;
     hipLaunchKernelGGL(k_hash_words, dim3((unsigned)blocks), dim3(256), 0, st, reinterpret_cast<const uint32_t *>(words), nWords, seed, out);
-}
-
-// ------------------------------------------------------------------ environment importance table (HR_ESTIMATOR_ENV_MIS)
-// The distribution the one-sample MIS estimator draws environment directions from (include/hrcore.h): texel weight =
-// (luminosity of the brightest texel of its 3 x 3 neighbourhood + maxLuminosity / 65536) x cos(elevation of the row), quantised to
-// integers so that the sums do not depend on their order — the tables are bit-identical to oracle/oracle_scene.cpp::buildEnvTable.
-__global__ __launch_bounds__(256) void k_env_lum(TexDesc t, float *__restrict__ lum, uint32_t *__restrict__ maxBits)
-{
-    const uint32_t i = blockIdx.x * 256 + threadIdx.x;
-    float l = 0.0f;
-    if (i < (uint32_t)(t.w * t.h)) {
-        const v4 c = texel(t, (int)(i % (uint32_t)t.w), (int)(i / (uint32_t)t.w));
-        l = (c.x * 0.33f + c.y * 0.59f) + c.z * 0.11f; // utility.rlsl:163-166 luminosity
-        l = l > 0.0f ? l : 0.0f;
-        l = l < 1e30f ? l : 1e30f; // (an infinite texel must not turn the normalisation into Inf / Inf)
-        lum[i] = l;
-    }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) l = fmax_(l, __shfl_xor(l, o));
-    if ((threadIdx.x & 63) == 0 && l > 0.0f) atomicMax(maxBits, __float_as_uint(l)); // non-negative floats order like their bits
-}
-__global__ __launch_bounds__(256) void k_env_dilate(const float *__restrict__ lum, float *__restrict__ dil, int w, int h)
-{
-    const uint32_t idx = blockIdx.x * 256 + threadIdx.x;
-    if (idx >= (uint32_t)(w * h)) return;
-    const int i = (int)(idx % (uint32_t)w), j = (int)(idx / (uint32_t)w);
-    float m = 0.0f;
-    for (int dj = -1; dj <= 1; ++dj) {
-        const int jj = j + dj < 0 ? 0 : (j + dj >= h ? h - 1 : j + dj);
-        for (int di = -1; di <= 1; ++di) {
-            const int ii = (i + di + w) % w;
-            const float l = lum[(size_t)jj * w + ii];
-            m = l > m ? l : m;
-        }
-    }
-    dil[idx] = m;
-}
-HRD uint32_t envWeight(float lum, float floorLum, float norm, float c)
-{
-    const float wt = (lum + floorLum) * c;
-    const float q = norm > 0.0f ? (wt / norm) * 1048576.0f : 0.0f;
-    return (uint32_t)q + 1u;
-}
-// one workgroup per row: quantised weights and their sum
-__global__ __launch_bounds__(256) void k_env_rows(const float *__restrict__ dil, int w, int h, const uint32_t *__restrict__ maxBits,
-                                                  uint32_t *__restrict__ wq, unsigned long long *__restrict__ rowSum)
-{
-    __shared__ unsigned long long part[4];
-    const int j = blockIdx.x;
-    const float maxLum = __uint_as_float(*maxBits);
-    const float floorLum = maxLum * (1.0f / 65536.0f), norm = maxLum + floorLum;
-    const float elevation = (((float)j + 0.5f) / (float)h - 0.5f) * HR_KPI;
-    const float c = cos_(elevation);
-    unsigned long long s = 0;
-    for (int i = threadIdx.x; i < w; i += 256) {
-        const uint32_t v = envWeight(dil[(size_t)j * w + i], floorLum, norm, c);
-        wq[(size_t)j * w + i] = v;
-        s += v;
-    }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o);
-    if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6] = s;
-    __syncthreads();
-    if (threadIdx.x == 0) rowSum[j] = part[0] + part[1] + part[2] + part[3];
-}
-// marginal over the rows (h is at most a few thousand: one thread)
-__global__ void k_env_marginal(const unsigned long long *__restrict__ rowSum, int w, int h, const uint32_t *__restrict__ maxBits,
-                               float *__restrict__ rowCdf, unsigned long long *__restrict__ total, float *__restrict__ meanLum)
-{
-    unsigned long long t = 0;
-    for (int j = 0; j < h; ++j) t += rowSum[j];
-    unsigned long long acc = 0;
-    for (int j = 0; j < h; ++j) {
-        rowCdf[j] = (float)acc / (float)t;
-        acc += rowSum[j];
-    }
-    rowCdf[h] = 1.0f;
-    *total = t;
-    // mean luminosity over the sphere from the same integers: sum(weight) / sum(cos), rows in order
-    const float maxLum = __uint_as_float(*maxBits);
-    const float norm = maxLum + maxLum * (1.0f / 65536.0f);
-    float sumC = 0.0f;
-    for (int j = 0; j < h; ++j) sumC = sumC + cos_((((float)j + 0.5f) / (float)h - 0.5f) * HR_KPI);
-    *meanLum = (((float)t / 1048576.0f) * norm) / ((float)w * sumC);
-}
-// one workgroup per row: conditional CDF over the columns (chunked scan with a carry) and the texel probabilities
-// The probability of a texel is what sampleEnv() really draws it with: the float CDF steps the two searches invert,
-// (rowCdf[j + 1] - rowCdf[j]) x (colCdf[i + 1] - colCdf[i]) — not the exact ratio of the integer weights, which a float CDF of a map
-// with a 2^20 : 1 weight range cannot resolve for dim texels (the balance heuristic needs the density samples are drawn with).
-__global__ __launch_bounds__(256) void k_env_cols(const uint32_t *__restrict__ wq, const unsigned long long *__restrict__ rowSum,
-                                                  const float *__restrict__ rowCdf, int w, float *__restrict__ colCdf,
-                                                  float *__restrict__ prob)
-{
-    __shared__ unsigned long long waveSum[4];
-    __shared__ unsigned long long carry;
-    const int j = blockIdx.x;
-    const float fr = (float)rowSum[j], pRow = rowCdf[j + 1] - rowCdf[j];
-    if (threadIdx.x == 0) carry = 0;
-    __syncthreads();
-    const uint32_t lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    for (int base = 0; base < w; base += 256) {
-        const int i = base + (int)threadIdx.x;
-        const unsigned long long v = i < w ? (unsigned long long)wq[(size_t)j * w + i] : 0ull;
-        unsigned long long inc = v;
-#pragma unroll
-        for (int o = 1; o < 64; o <<= 1) {
-            const unsigned long long up = __shfl_up(inc, o);
-            if ((int)lane >= o) inc += up;
-        }
-        if (lane == 63) waveSum[wave] = inc;
-        __syncthreads();
-        unsigned long long before = carry;
-        for (uint32_t k = 0; k < wave; ++k) before += waveSum[k];
-        if (i < w) {
-            const float cThis = (float)(before + inc - v) / fr, cNext = (i == w - 1) ? 1.0f : (float)(before + inc) / fr;
-            colCdf[(size_t)j * (w + 1) + i] = cThis;
-            prob[(size_t)j * w + i] = pRow * (cNext - cThis);
-        }
-        __syncthreads();
-        if (threadIdx.x == 255) carry = before + inc;
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) colCdf[(size_t)j * (w + 1) + w] = 1.0f;
-}
-
-// scratch: lum, dil (w*h floats each), wq (w*h uint32), rowSum (h uint64), total (uint64), maxBits (uint32) — caller-owned
-void launchEnvTable(hipStream_t st, const TexDesc &tex, float *lum, float *dil, uint32_t *wq, unsigned long long *rowSum, unsigned long long *total,
-                    uint32_t *maxBits, float *rowCdf, float *colCdf, float *prob, float *meanLum)
-{
-    const int w = tex.w, h = tex.h;
-    const uint32_t n = (uint32_t)((size_t)w * (size_t)h), g = (n + 255) / 256;
-    hipMemsetAsync(maxBits, 0, 4, st);
-    hipLaunchKernelGGL(k_env_lum, dim3(g), dim3(256), 0, st, tex, lum, maxBits);
-    hipLaunchKernelGGL(k_env_dilate, dim3(g), dim3(256), 0, st, lum, dil, w, h);
-    hipLaunchKernelGGL(k_env_rows, dim3(h), dim3(256), 0, st, dil, w, h, maxBits, wq, rowSum);
-    hipLaunchKernelGGL(k_env_marginal, dim3(1), dim3(1), 0, st, rowSum, w, h, maxBits, rowCdf, total, meanLum);
-    hipLaunchKernelGGL(k_env_cols, dim3(h), dim3(256), 0, st, wq, rowSum, rowCdf, w, colCdf, prob);
-}
-
-// Guide tables of the two inverse-CDF searches (hr_shade.h::sampleEnv): guide[k] = the largest index whose CDF value is <= k / K.
-// A search for x starts in [guide[floor(x K)], guide[floor(x K) + 1]] and returns what the search over the whole table returns
-// (the oracle's plain binary search), after ~2 probes instead of 10 + 11 dependent loads.
-HRD int cdfSearch(const float *cdf, int lo, int hi, float x)
-{
-    while (lo < hi) {
-        const int mid = (lo + hi + 1) >> 1;
-        if (cdf[mid] <= x)
-            lo = mid;
-        else
-            hi = mid - 1;
-    }
-    return lo;
-}
-__global__ __launch_bounds__(64) void k_env_guides(const float *__restrict__ rowCdf, const float *__restrict__ colCdf, int w, int h,
-                                                   uint16_t *__restrict__ rowGuide, uint16_t *__restrict__ colGuide)
-{
-    // block 0: the row guide (kEnvRowGuide + 1 entries); block j + 1: the column guide of row j (kEnvColGuide + 1 entries)
-    if (blockIdx.x == 0) {
-        for (int k = threadIdx.x; k <= kEnvRowGuide; k += 64)
-            rowGuide[k] = (uint16_t)cdfSearch(rowCdf, 0, h - 1, (float)k * (1.0f / (float)kEnvRowGuide));
-    } else {
-        const int j = (int)blockIdx.x - 1;
-        const float *cc = colCdf + (size_t)j * (w + 1);
-        for (int k = threadIdx.x; k <= kEnvColGuide; k += 64)
-            colGuide[(size_t)j * (kEnvColGuide + 1) + k] = (uint16_t)cdfSearch(cc, 0, w - 1, (float)k * (1.0f / (float)kEnvColGuide));
-    }
-}
-void launchEnvGuides(hipStream_t st, const float *rowCdf, const float *colCdf, int w, int h, uint16_t *rowGuide, uint16_t *colGuide)
-{
-    hipLaunchKernelGGL(k_env_guides, dim3(h + 1), dim3(64), 0, st, rowCdf, colCdf, w, h, rowGuide, colGuide);
-}
-
-// ---------------------------------------------------------------------------- mip chain, texel density (HR_TEXTURE_LOD_CONE)
-// One level of the chain: dst(x, y) = ((s(2x, 2y) + s(2x+1, 2y)) + (s(2x, 2y+1) + s(2x+1, 2y+1))) * 0.25 per channel, source
-// coordinates clamped to the source level (odd sizes); u8 data enters as float(byte) / 255.0f, levels >= 1 are f32.
-__global__ __launch_bounds__(256) void k_mip_down(const void *__restrict__ src, int srcIsU8, int sw, int sh, int c, float *__restrict__ dst, int dw, int dh)
-{
-    const uint32_t i = blockIdx.x * 256 + threadIdx.x;
-    if (i >= (uint32_t)(dw * dh)) return;
-    const int x = (int)(i % (uint32_t)dw), y = (int)(i / (uint32_t)dw);
-    const int x0 = 2 * x < sw ? 2 * x : sw - 1, x1 = 2 * x + 1 < sw ? 2 * x + 1 : sw - 1;
-    const int y0 = 2 * y < sh ? 2 * y : sh - 1, y1 = 2 * y + 1 < sh ? 2 * y + 1 : sh - 1;
-    for (int k = 0; k < c; ++k) {
-        float a, b, cc, d;
-        if (srcIsU8) {
-            const uint8_t *p = reinterpret_cast<const uint8_t *>(src);
-            a = (float)p[((size_t)y0 * sw + x0) * c + k] / 255.0f, b = (float)p[((size_t)y0 * sw + x1) * c + k] / 255.0f;
-            cc = (float)p[((size_t)y1 * sw + x0) * c + k] / 255.0f, d = (float)p[((size_t)y1 * sw + x1) * c + k] / 255.0f;
-        } else {
-            const float *p = reinterpret_cast<const float *>(src);
-            a = p[((size_t)y0 * sw + x0) * c + k], b = p[((size_t)y0 * sw + x1) * c + k];
-            cc = p[((size_t)y1 * sw + x0) * c + k], d = p[((size_t)y1 * sw + x1) * c + k];
-        }
-        dst[((size_t)y * dw + x) * c + k] = ((a + b) + (cc + d)) * 0.25f;
-    }
-}
-
-// levels 1 .. nLevels-1 of `t` into `mips` (laid out as hr_texture.h's mipOffset expects)
-void launchMipChain(hipStream_t st, const TexDesc &t, int nLevels, float *mips)
-{
-    const void *src = t.px;
-    int srcU8 = t.dtype == HR_TEX_U8 ? 1 : 0, sw = t.w, sh = t.h;
-    size_t off = 0;
-    for (int l = 1; l < nLevels; ++l) {
-        const int dw = sw / 2 < 1 ? 1 : sw / 2, dh = sh / 2 < 1 ? 1 : sh / 2;
-        float *dst = mips + off;
-        hipLaunchKernelGGL(k_mip_down, dim3(((uint32_t)(dw * dh) + 255) / 256), dim3(256), 0, st, src, srcU8, sw, sh, t.c, dst, dw, dh);
-        off += (size_t)dw * dh * t.c;
-        src = dst, srcU8 = 0, sw = dw, sh = dh;
-    }
-}
-
-__global__ void k_tex_lod_scale(TexDesc *table, int n)
-{
-    const int i = blockIdx.x * 64 + threadIdx.x;
-    if (i < n) table[i].lodScale = 0.5f * (log_((float)table[i].w * (float)table[i].h) * 1.4426950408889634f);
-}
-void launchTexLodScale(hipStream_t st, TexDesc *table, int n)
-{
-    if (n > 0) hipLaunchKernelGGL(k_tex_lod_scale, dim3((n + 63) / 64), dim3(64), 0, st, table, n);
-}
-
-// texDensity[prim] = 0.5 * log2(uv area / world area) of every triangle (twice-areas cancel); -1e30 where either area is zero
-// (no uvs, degenerate triangle): such a triangle is textured at level 0
-__global__ __launch_bounds__(256) void k_tex_density(const Tri *__restrict__ leafTris, uint32_t nSlots, const TriAttr *__restrict__ attrs,
-                                                     float *__restrict__ out)
-{
-    const uint32_t i = blockIdx.x * 256 + threadIdx.x;
-    if (i >= nSlots) return;
-    const Tri tr = leafTris[i];
-    const uint32_t prim = __float_as_uint(tr.r.y);
-    if (prim == 0xFFFFFFFFu) return;
-    const v3 e1(tr.p.w, tr.q.x, tr.q.y), e2(tr.q.z, tr.q.w, tr.r.x);
-    const float world2 = length(cross(e1, e2));
-    const TriAttr &a = attrs[prim];
-    const float du1 = a.uv[2] - a.uv[0], dv1 = a.uv[3] - a.uv[1], du2 = a.uv[4] - a.uv[0], dv2 = a.uv[5] - a.uv[1];
-    const float uv2 = abs_(du1 * dv2 - dv1 * du2);
-    out[prim] = (world2 > 0.0f && uv2 > 0.0f) ? 0.5f * (log_(uv2 / world2) * 1.4426950408889634f) : -1e30f;
-}
-void launchTexDensity(hipStream_t st, const Tri *leafTris, uint32_t nSlots, const TriAttr *attrs, float *out)
-{
-    if (nSlots) hipLaunchKernelGGL(k_tex_density, dim3((nSlots + 255) / 256), dim3(256), 0, st, leafTris, nSlots, attrs, out);
-}
-
-// ---------------------------------------------------------------------------------------- QMC
-// Random.h:26-34 (see oracle/oracle_qmc.cpp for the x86 conversion note)
-HRD uint32_t toUint32(float f) { return (uint32_t)(unsigned long long)(long long)(f * 4294967296.0f); }
-HRD float toNormalizedFloat(uint32_t u) { return (float)u * (1.0f / 4294967296.0f); }
-HRD uint32_t burleyHash(uint32_t x) // Random.h:36-45
-{
-    x ^= x >> 16;
-    x *= 0x85ebca6bu;
-    x ^= x >> 13;
-    x *= 0xc2b2ae35u;
-    x ^= x >> 16;
-    return x;
-}
-HRD uint32_t burleyHashCombine(uint32_t seed, uint32_t v) { return seed ^ (v + (seed << 6) + (seed >> 2)); } // :47-50
-HRD uint32_t nestedUniformScramble(uint32_t x, uint32_t seed) // Random.h:52-78 (bit reversal = v_bfrev_b32)
-{
-    x = __brev(x);
-    x += seed;
-    x ^= x * 0x6c50b47cu;
-    x ^= x * 0xb82f1e52u;
-    x ^= x * 0xc7afe638u;
-    x ^= x * 0x8d22f6e6u;
-    return __brev(x);
-}
-HRD uint32_t sobolDim1(uint32_t index) // Random.h:236-244: v[b] = v[b-1] ^ (v[b-1] >> 1)
-{
-    uint32_t result = 0, v = 0x80000000u;
-    for (uint32_t bit = 0; bit < 32; ++bit) {
-        if ((index >> bit) & 1u) result ^= v;
-        v ^= v >> 1;
-    }
-    return result;
-}
-HRD float haltonValue(uint32_t index, int base) // Random.h:192-204
-{
-    float result = 0.0f, f = 1.0f;
-    const float denom = (float)base;
-    uint32_t n = index;
-    while (n > 0) {
-        f = f / denom;
-        result += f * (float)(n % (uint32_t)base);
-        n = n / (uint32_t)base;
-    }
-    return result;
-}
-__constant__ int kHaltonBases[16][2] = {{2, 3},  {2, 5},  {2, 7},  {3, 7}, {4, 5},   {5, 7},  {5, 9},  {5, 11},
-                                        {6, 11}, {5, 11}, {8, 11}, {3, 5}, {11, 15}, {2, 15}, {3, 19}, {7, 10}}; // Random.h:172-189
-
-// owenScrambleSequence (Random.h:85-108) with sobol / halton / hammersley generators (radialSobol's disk mapping,
-// Random.h:268-289, is applied on the host: hr_core.hip::radialOnHost)
-__global__ __launch_bounds__(256) void k_qmc(int mode, uint32_t sequenceIndex, uint32_t count, float2 *__restrict__ out)
-{
-    const uint32_t i = blockIdx.x * 256 + threadIdx.x;
-    if (i >= count) return;
-    const uint32_t seed = burleyHash(sequenceIndex + 1);
-    const uint32_t index = nestedUniformScramble(i, seed);
-    float sx, sy;
-    if (mode == HR_SAMPLE_SOBOL) {
-        sx = toNormalizedFloat(__brev(index)); // dimension 0: direction numbers 2^(31-bit)
-        sy = toNormalizedFloat(sobolDim1(index));
-    } else if (mode == HR_SAMPLE_HALTON) {
-        sx = haltonValue(index, kHaltonBases[sequenceIndex & 15][0]);
-        sy = haltonValue(index, kHaltonBases[sequenceIndex & 15][1]);
-    } else {
-        sx = (float)i * (1.0f / (float)count);
-        sy = (float)__brev(index) * 2.3283064365386963e-10f;
-    }
-    float x = toNormalizedFloat(nestedUniformScramble(toUint32(sx), burleyHashCombine(seed, 0)));
-    float y = toNormalizedFloat(nestedUniformScramble(toUint32(sy), burleyHashCombine(seed, 1)));
-    out[i] = make_float2(x, y);
-}
-
-void launchQmc(hipStream_t st, int mode, uint32_t sequenceIndex, uint32_t count, float2 *out)
-{
-    if (count == 0) return;
-    hipLaunchKernelGGL(k_qmc, dim3((count + 255) / 256), dim3(256), 0, st, mode, sequenceIndex, count, out);
-}
-
-// ---------------------------------------------------------------- tables of the sequential generators
-// util::uniformRandomFloats (edges == 0) and util::randomPolygonal (edges = 5 / 6 / 8) — Random.h:113-130, 293-355; arithmetic in hr_tables.h.
-// One workgroup per sequence: MT19937's state lives in LDS, seeded by one lane (a 623-step chain), twisted by 208 lanes in three rounds
-// (word i needs words i+1 and i+397 from before the twist for i < 227 and word i-227 from after it: a round of 208 < 227 words never reads a
-// word of its own round after it was written) and tempered 624 draws at a time.  uniformRandomFloats maps draw 2s / 2s+1 to sample s, in parallel;
-// randomPolygonal consumes a data-dependent number of draws per sample (Lemire's rejection for the fan triangle, a rejection loop for the
-// barycentrics), so one lane walks the block of draws with the four-state machine of the serial loop.  The polygon's vertices come from the
-// host (cosf / sinf of the platform's libm, the same calls the reference makes: like radialSobol's disk mapping in hr_scene.inl).
-struct PolyVerts { float x[8], y[8]; };
-static constexpr int kMtRound = 208; // 3 x 208 = 624
-__global__ __launch_bounds__(256) void k_mt_tables(uint32_t seed0, uint32_t count, uint32_t edges, PolyVerts verts, float2 *__restrict__ outBase,
-                                                   size_t stride)
-{
-    __shared__ uint32_t st[kMtN], draws[kMtN];
-    __shared__ uint32_t sDone;
-    const uint32_t tid = threadIdx.x;
-    float2 *out = outBase + (size_t)blockIdx.x * stride;
-    if (tid == 0) {
-        uint32_t v = seed0 + blockIdx.x;
-        st[0] = v;
-        for (uint32_t i = 1; i < (uint32_t)kMtN; ++i) st[i] = v = mtSeedNext(v, i);
-        sDone = 0;
-    }
-    __syncthreads();
-    uint32_t done = 0, phase = 0; // (lane 0's: samples finished; 0 = fan triangle, first draw, 1 = its retries, 2 = alpha, 3 = beta)
-    MtIntDraw pick{edges, 0u, 0ull};
-    float alpha = 0.0f;
-    for (uint32_t drawBase = 0;; drawBase += (uint32_t)kMtN) {
-        for (int r = 0; r < 3; ++r) {
-            const uint32_t i = (uint32_t)(r * kMtRound) + tid;
-            uint32_t w = 0;
-            if (tid < (uint32_t)kMtRound) w = mtTwist(st[i], st[(i + 1) % kMtN], st[(i + kMtM) % kMtN]);
-            __syncthreads();
-            if (tid < (uint32_t)kMtRound) st[i] = w;
-            __syncthreads();
-        }
-        for (uint32_t k = tid; k < (uint32_t)kMtN; k += 256) draws[k] = mtTemper(st[k]);
-        __syncthreads();
-        if (edges == 0) {
-            float *o = reinterpret_cast<float *>(out);
-            for (uint32_t k = tid; k < (uint32_t)kMtN; k += 256) {
-                const uint64_t g = (uint64_t)drawBase + k;
-                if (g < 2ull * count) o[g] = mtCanonical(draws[k]);
-            }
-            if ((uint64_t)drawBase + kMtN >= 2ull * count) break;
-        } else {
-            if (tid == 0) {
-                for (int k = 0; k < kMtN && done < count; ++k) {
-                    const uint32_t u = draws[k];
-                    if (phase < 2) {
-                        phase = pick.accept(u, phase == 0) ? 2u : 1u;
-                    } else if (phase == 2) {
-                        alpha = mtCanonical(u), phase = 3;
-                    } else {
-                        const float beta = mtCanonical(u);
-                        if (alpha + beta > 1.0f) {
-                            phase = 2;
-                            continue;
-                        }
-                        const float gamma = 1.0f - (alpha + beta);
-                        const int t0 = pick.value(), t1 = (t0 + 1) % (int)edges;
-                        const float vx = 0.0f * alpha + verts.x[t0] * beta + verts.x[t1] * gamma; // (the fan's centre is vertex 0 of every triangle)
-                        const float vy = 0.0f * alpha + verts.y[t0] * beta + verts.y[t1] * gamma;
-                        out[done++] = make_float2((vx + 1.0f) * 0.5f, (vy + 1.0f) * 0.5f);
-                        phase = 0;
-                    }
-                }
-                sDone = done;
-            }
-            __syncthreads();
-            if (sDone >= count) break;
-        }
-    }
-}
-void launchMtTables(hipStream_t st, uint32_t seed0, int nSeq, uint32_t count, uint32_t edges, const float *vx, const float *vy, float2 *out, size_t stride)
-{
-    if (count == 0 || nSeq <= 0) return;
-    PolyVerts v{};
-    for (uint32_t i = 0; i < edges && i < 8u; ++i) v.x[i] = vx[i], v.y[i] = vy[i];
-    hipLaunchKernelGGL(k_mt_tables, dim3((uint32_t)nSeq), dim3(256), 0, st, seed0, count, edges, v, out, stride);
-}
-
-// util::blueNoise (BlueNoise.h:52-88): point i is the best of 30 hashed candidates, "best" = furthest from its nearest earlier point.  The
-// candidates do not depend on the points (a hash of a running seed), so one launch makes them all; the choice is sequential over the points
-// and parallel inside a point: a workgroup per sequence, 30 groups of 32 lanes — a group per candidate, a lane per 32nd earlier point —
-// min over squared distances (the square root is monotone, it is taken once per candidate), then one lane picks the first candidate whose
-// nearest distance exceeds the running maximum, as the serial loop does.  15 n^2 distance tests per sequence of n points.
-static constexpr int kBlueCandidates = 30, kBlueLds = 8192;
-__global__ __launch_bounds__(256) void k_blue_candidates(int32_t seq0, uint32_t nSeq, uint32_t count, float2 *__restrict__ cand, float2 *__restrict__ outBase, size_t stride)
-{
-    const uint32_t perSeq = (count - 1u) * (uint32_t)kBlueCandidates + 1u; // (entry 0: the first point itself)
-    const uint64_t gid = (uint64_t)blockIdx.x * 256 + threadIdx.x;
-    const uint32_t s = (uint32_t)(gid / perSeq), k = (uint32_t)(gid % perSeq);
-    if (s >= nSeq) return;
-    const uint32_t seed = blueSeed(seq0 + (int32_t)s) + 2u * k;
-    const float2 p = make_float2(blueRandom(seed), blueRandom(seed + 1u));
-    if (k == 0)
-        outBase[(size_t)s * stride] = p;
-    else
-        cand[(size_t)s * (perSeq - 1u) + (k - 1u)] = p;
-}
-template <bool LDS>
-__global__ __launch_bounds__(1024) void k_blue_noise(uint32_t count, const float2 *__restrict__ candBase, float2 *__restrict__ outBase, size_t stride)
-{
-    __shared__ float2 ptsLds[LDS ? kBlueLds : 1];
-    __shared__ float nearest[32];
-    float2 *out = outBase + (size_t)blockIdx.x * stride;
-    const float2 *cand = candBase + (size_t)blockIdx.x * (count - 1u) * kBlueCandidates;
-    float2 *pts = LDS ? ptsLds : out;
-    const uint32_t tid = threadIdx.x, g = tid >> 5, l = tid & 31u;
-    if (LDS && tid == 0) ptsLds[0] = out[0];
-    __syncthreads();
-    const float diag = sqrt_(1.0f * 1.0f + 1.0f * 1.0f);
-    for (uint32_t i = 1; i < count; ++i) {
-        if (g < (uint32_t)kBlueCandidates) {
-            const float2 c = cand[(size_t)(i - 1u) * kBlueCandidates + g];
-            float m = 3.0e38f;
-            for (uint32_t j = l; j < i; j += 32u) {
-                const float2 p = pts[j];
-                const float dx = p.x - c.x, dy = p.y - c.y;
-                m = fmin_(m, dx * dx + dy * dy);
-            }
-#pragma unroll
-            for (int sh = 16; sh > 0; sh >>= 1) m = fmin_(m, __shfl_xor(m, sh));
-            if (l == 0) nearest[g] = fmin_(diag, sqrt_(m));
-        }
-        __syncthreads();
-        if (tid == 0) {
-            float furthest = 0.0f;
-            int best = -1;
-            for (int c = 0; c < kBlueCandidates; ++c)
-                if (nearest[c] > furthest) furthest = nearest[c], best = c;
-            const float2 p = best < 0 ? make_float2(0.0f, 0.0f) : cand[(size_t)(i - 1u) * kBlueCandidates + best];
-            pts[i] = p;
-            if (LDS) out[i] = p;
-        }
-        __syncthreads();
-    }
-}
-// cand: scratch of nSeq * (count - 1) * 30 points
-void launchBlueNoise(hipStream_t st, int32_t seq0, int nSeq, uint32_t count, float2 *out, size_t stride, float2 *cand)
-{
-    if (count == 0 || nSeq <= 0) return;
-    const uint64_t total = (uint64_t)nSeq * ((uint64_t)(count - 1u) * kBlueCandidates + 1u);
-    hipLaunchKernelGGL(k_blue_candidates, dim3((uint32_t)((total + 255) / 256)), dim3(256), 0, st, seq0, (uint32_t)nSeq, count, cand, out, stride);
-    int dev = 0, ldsMax = 0; // (the LDS copy of the points is 64 KB + the candidates' row: more than a gfx9 before gfx950 gives one workgroup)
-    if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&ldsMax, hipDeviceAttributeMaxSharedMemoryPerBlock, dev) != hipSuccess) ldsMax = 0;
-    if (count <= (uint32_t)kBlueLds && (size_t)ldsMax >= sizeof(float2) * kBlueLds + 256)
-        hipLaunchKernelGGL(k_blue_noise<true>, dim3((uint32_t)nSeq), dim3(1024), 0, st, count, cand, out, stride);
-    else
-        hipLaunchKernelGGL(k_blue_noise<false>, dim3((uint32_t)nSeq), dim3(1024), 0, st, count, cand, out, stride);
-}
-
-// ------------------------------------------------------------------------------ multiscatter LUT
-// MultiScatterUtil.cpp:20-139: one thread per texel integrates 4096 Sobol samples of the GGX lobe.
-HRD float lutG1(float NdotI, float alpha)
-{
-    const float alpha2 = alpha * alpha;
-    const float denom = sqrt_(alpha2 + (1.0f - alpha2) * (NdotI * NdotI)) + NdotI;
-    return (2.0f * NdotI) / fmax_(denom, 1e-5f);
-}
-__global__ __launch_bounds__(128) void k_multiscatter_lut(const float2 *__restrict__ seq, int samples, float *__restrict__ out, int dim)
-{
-    const int col = threadIdx.x, row = blockIdx.x;
-    const float roughness = clamp_(((float)row + 0.5f) / (float)dim, 0.0f, 1.0f);
-    const float alpha = roughness * roughness;
-    const float NdotV = clamp_(((float)col + 0.5f) / (float)dim, 0.0f, 1.0f);
-    const v3 V(sqrt_(1.0f - (NdotV * NdotV)), 0.0f, NdotV);
-    float result = 0.0f;
-    for (int i = 0; i < samples; ++i) {
-        const float2 r = seq[i];
-        const float a2 = alpha * alpha;
-        const float cosTheta = sqrt_(fmax_(0.0f, (1.0f - r.x) / ((a2 - 1.0f) * r.x + 1.0f)));
-        const float sinTheta = sqrt_(fmax_(0.0f, 1.0f - cosTheta * cosTheta));
-        float sn, cs;
-        sincos_(6.28318530717958647692f * r.y, &sn, &cs);
-        v3 H(sinTheta * cs, sinTheta * sn, cosTheta);
-        H = normalize(H);
-        const v3 L = 2.0f * dot(V, H) * H - V;
-        const float NdotL = clamp_(L.z, 0.0f, 1.0f);
-        if (NdotL > 0.0f) {
-            const float VdotH = clamp_(dot(V, H), 0.0f, 1.0f);
-            const float NdotH = clamp_(H.z, 0.0f, 1.0f);
-            result += (lutG1(NdotL, alpha) * lutG1(NdotV, alpha) * VdotH) / (NdotV * NdotH);
-        }
-    }
-    const float value = result / (float)samples;
-    out[row * dim + col] = (1.0f - value) / value;
-}
-
-void launchMultiscatterLUT(hipStream_t st, const float2 *sobol4096, float *out128x128)
-{
-    hipLaunchKernelGGL(k_multiscatter_lut, dim3(128), dim3(128), 0, st, sobol4096, 4096, out128x128, 128);
 }
 
 } // namespace hr

@@ -20,7 +20,7 @@
 //   hr_metric.inl     the convergence metric: exact relative L2 against a reference, or predicted from the moments (include/hrcore_metric.h)
 // (one translation unit: the .inl files are sections of this one, included below)
 // The kernels it launches are units of their own (declared in hr_kernels.h): the render stages hr_raygen.hip, hr_trace.hip, hr_shade.hip and
-// hr_frame.hip (resolve, shard exchange, display) over what they share in hr_wave.h; hr_build.hip; one unit per post-process feature.
+// hr_frame.hip (resolve, shard exchange, display) over what they share in hr_wave.h; hr_build.hip (scene assembly, the tree) and hr_tables.hip (the table generators); one unit per post-process feature.
 #include "hr_ctx.h"
 
 static const int kTableRing = 4;

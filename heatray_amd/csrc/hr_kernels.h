@@ -1,4 +1,4 @@
-// hr_kernels.h — host-visible declarations of the kernel launchers (the render stages hr_frame.hip, hr_raygen.hip, hr_trace.hip and hr_shade.hip; hr_build.hip; the post-process units).
+// hr_kernels.h — host-visible declarations of the kernel launchers (the render stages hr_frame.hip, hr_raygen.hip, hr_trace.hip and hr_shade.hip; hr_build.hip and hr_tables.hip; the post-process units).
 #pragma once
 
 #include "hr_types.h"
@@ -324,12 +324,14 @@ void refitLBVH(hipStream_t st, const BuildResult &tree, uint32_t nTris, SceneCon
 void encodeNodes32(hipStream_t st, const BuildResult &tree, const SceneConsts *consts, SceneDev *scene);
 void gridOf(const SceneConsts &k, float gridLo[3], float gridCell[3], uint32_t gridCellExp[3]);
 // order-independent 64-bit digest of a device buffer, added to *out (device)
-void launchMipChain(hipStream_t st, const TexDesc &t, int nLevels, float *mips);
-void launchTexLodScale(hipStream_t st, TexDesc *table, int n);
-void launchTexDensity(hipStream_t st, const Tri *leafTris, uint32_t nSlots, const TriAttr *attrs, float *out);
 void launchHashWords(hipStream_t st, const void *words, size_t nWords, unsigned long long seed, unsigned long long *out);
 void launchAreaSum(hipStream_t st, const Box6 *nodeBox, uint32_t n, SceneConsts *consts);
 void launchTriAreaSum(hipStream_t st, const Tri *leafTris, uint32_t nSlots, SceneConsts *consts);
+
+// ---- hr_tables.hip (the arithmetic of the sequential generators: hr_tables.h)
+void launchMipChain(hipStream_t st, const TexDesc &t, int nLevels, float *mips);
+void launchTexLodScale(hipStream_t st, TexDesc *table, int n);
+void launchTexDensity(hipStream_t st, const Tri *leafTris, uint32_t nSlots, const TriAttr *attrs, float *out);
 
 // environment importance table (HR_ESTIMATOR_ENV_MIS): scratch and outputs are caller-owned device arrays
 void launchEnvGuides(hipStream_t st, const float *rowCdf, const float *colCdf, int w, int h, uint16_t *rowGuide, uint16_t *colGuide);

@@ -1,7 +1,7 @@
 // hr_tables.h — the arithmetic of the sample tables that have no closed form per index: util::uniformRandomFloats and
 // util::randomPolygonal (std::mt19937 + the standard distributions, /root/reference/Source/Utility/Random.h:113-130, 293-355) and
 // util::blueNoise (best-candidate points over an FNV-1a hash, /root/reference/Source/Utility/BlueNoise.h:32-100, Random.h:158-165).
-// Pure integer / float32 functions, no memory, so that the kernels in hr_build.hip and the CPU unit test
+// Pure integer / float32 functions, no memory, so that the kernels in hr_tables.hip and the CPU unit test
 // (tests/host/tables_arith_test.cpp, against the host's own <random>) compile the same lines.
 //
 // The reference leaves the distributions to the C++ library it is built with.  The contract here is libstdc++'s (GCC 11+), the library

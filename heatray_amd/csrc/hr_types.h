@@ -114,7 +114,7 @@ struct SceneDev {
     int32_t nSeq, seqLen, nSeqOffsets;
     // importance table of the environment map (HR_ESTIMATOR_ENV_MIS): P(row < j), P(col < i | row j), P(texel); envW == 0: none
     const float *envRowCdf, *envColCdf, *envProb;
-    const uint16_t *envRowGuide, *envColGuide; // guide tables of the two inverse-CDF searches (hr_build.hip::k_env_guides)
+    const uint16_t *envRowGuide, *envColGuide; // guide tables of the two inverse-CDF searches (hr_tables.hip::k_env_guides)
     int32_t envW, envH;
     float envMeanLum; // solid-angle-weighted mean luminosity of the map (light-pick weight of the MIS estimator)
     // interactive-mode block table (hr_interactive_blocks_set); blockNx == 0: the unshuffled list

@@ -147,7 +147,7 @@ vec4 sampleTexture(const Texture &t, float u, float v)
 }
 
 // ---- HR_TEXTURE_LOD_CONE (include/hrcore.h): mip chain + trilinear lookup; the product's heatray_amd/csrc/hr_texture.h and the
-// mip / density kernels of hr_build.hip follow THIS arithmetic, operation for operation.
+// mip / density kernels of hr_tables.hip follow THIS arithmetic, operation for operation.
 static inline int mipDim(int n, int level)
 {
     const int d = n >> level;
