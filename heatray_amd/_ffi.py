@@ -335,6 +335,27 @@ class MetricResult(C.Structure):
         return {k: getattr(self, k) for k, _ in self._fields_ if k != "reserved"}
 
 
+# every symbol include/hrcore_despeckle.h declares (firefly suppression: the outlier clamp ahead of the denoiser).  Resolved lazily like
+# the AOV symbols
+HR_DESPECKLE_API_VERSION = 1
+HR_DESPECKLE_RANK_HIGHEST, HR_DESPECKLE_TAPS = 4, 24
+DESPECKLE_SYMBOLS = ["despeckle_api_version", "despeckle_default_params", "despeckle", "despeckle_readback", "despeckle_denoise", "despeckle_denoise_readback"]
+
+
+class DespeckleParams(C.Structure):
+    """hr_despeckle_params"""
+    _fields_ = [("rank", C.c_int32), ("min_taps", C.c_int32), ("ratio", C.c_float), ("sigmas", C.c_float), ("floor", C.c_float), ("reserved", C.c_uint32 * 3)]
+
+
+class DespeckleResult(C.Structure):
+    """hr_despeckle_result"""
+    _fields_ = [("valid_pixels", C.c_uint64), ("clamped_pixels", C.c_uint64), ("kept_pixels", C.c_uint64), ("starved_pixels", C.c_uint64),
+                ("nonfinite_pixels", C.c_uint64), ("reserved", C.c_uint64 * 3)]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_ if k != "reserved"}
+
+
 # The optional headers: feature -> (its symbols, the version the binding was written against, what "this library has no ..." calls it);
 # the version function is <feature>_api_version.  Engine._feature_call checks a feature on its first call
 FEATURES = {
@@ -347,6 +368,7 @@ FEATURES = {
     "tree": (TREE_SYMBOLS, HR_TREE_API_VERSION, "tree build report"),
     "exposure": (EXPOSURE_SYMBOLS, HR_EXPOSURE_API_VERSION, "auto-exposure"),
     "metric": (METRIC_SYMBOLS, HR_METRIC_API_VERSION, "convergence metric"),
+    "despeckle": (DESPECKLE_SYMBOLS, HR_DESPECKLE_API_VERSION, "firefly suppression"),
 }
 
 
@@ -905,6 +927,52 @@ class Engine:
         u64p = C.POINTER(C.c_uint64)
         self._feature_call("metric", "metric_last", C.byref(r), num.ctypes.data_as(u64p) if with_bins else None, den.ctypes.data_as(u64p) if with_bins else None)
         return (r.as_dict(), num, den) if with_bins else r.as_dict()
+
+    # -- firefly suppression (include/hrcore_despeckle.h)
+    def despeckle(self, params=None, with_moments=False, with_result=False):
+        """The despeckled frame (H x W x 4 float32, accumulation format like readback()) of the passes rendered so far; needs
+        HR_AOV_MOMENTS enabled before the frame's first pass.  params: a DespeckleParams (heatray_amd.despeckle.default_params()),
+        None = the defaults.  with_moments: and the despeckled MOMENTS plane; with_result: and the DespeckleResult as a dict; the image
+        alone, or a tuple in that order."""
+        p, m = f32p(), f32p()
+        w, h, n = C.c_int32(), C.c_int32(), C.c_uint32()
+        r = DespeckleResult()
+        self._feature_call("despeckle", "despeckle_readback", C.byref(params) if params is not None else None, C.byref(p), C.byref(m) if with_moments else None,
+                           C.byref(w), C.byref(h), C.byref(n), C.byref(r))
+        out = [np.ctypeslib.as_array(p, shape=(h.value, w.value, 4)).copy()]
+        if with_moments:
+            out.append(np.ctypeslib.as_array(m, shape=(h.value, w.value, 4)).copy())
+        if with_result:
+            out.append(r.as_dict())
+        return out[0] if len(out) == 1 else tuple(out)
+
+    def despeckle_to_device(self, out_ptr, moments_out_ptr=None, params=None, frame=None, moments=None, stream=None, with_result=False):
+        """Asynchronous: the despeckled frame, and with moments_out_ptr the despeckled moments, (W x H float4 each) into device memory,
+        e.g. torch tensors; ordered like denoise_to_device.  frame / moments: device pointers of a caller's pair instead of the
+        context's own (both or neither).  with_result: waits and returns the DespeckleResult as a dict."""
+        r = DespeckleResult()
+        self._feature_call("despeckle", "despeckle", C.byref(params) if params is not None else None, C.c_void_p(int(frame) if frame else 0),
+                           C.c_void_p(int(moments) if moments else 0), C.c_void_p(int(out_ptr) if out_ptr else 0),
+                           C.c_void_p(int(moments_out_ptr) if moments_out_ptr else 0), C.c_void_p(stream or 0), None, C.byref(r) if with_result else None)
+        return r.as_dict() if with_result else None
+
+    def despeckle_denoise(self, params=None, dparams=None, spatial=False, sparams=None, with_result=False):
+        """denoise() (spatial: denoise_spatial()) run from the despeckled frame and moments instead of the raw ones.  params: a
+        DespeckleParams, dparams: a DenoiseParams, sparams: a DenoiseSpatialParams; None = the defaults.  with_result: (image, the
+        DespeckleResult as a dict)."""
+        p = f32p()
+        w, h, n = C.c_int32(), C.c_int32(), C.c_uint32()
+        r = DespeckleResult()
+        self._feature_call("despeckle", "despeckle_denoise_readback", C.byref(params) if params is not None else None, C.byref(dparams) if dparams is not None else None,
+                           C.c_int32(int(bool(spatial))), C.byref(sparams) if sparams is not None else None, C.byref(p), C.byref(w), C.byref(h), C.byref(n), C.byref(r))
+        img = np.ctypeslib.as_array(p, shape=(h.value, w.value, 4)).copy()
+        return (img, r.as_dict()) if with_result else img
+
+    def despeckle_denoise_to_device(self, device_ptr, params=None, dparams=None, spatial=False, sparams=None, stream=None):
+        """Asynchronous: despeckle_denoise's image (W x H float4) into device memory; ordered like denoise_to_device."""
+        self._feature_call("despeckle", "despeckle_denoise", C.byref(params) if params is not None else None, C.byref(dparams) if dparams is not None else None,
+                           C.c_int32(int(bool(spatial))), C.byref(sparams) if sparams is not None else None, C.c_void_p(int(device_ptr) if device_ptr else 0),
+                           C.c_void_p(stream or 0), None, None)
 
     def debug_trace(self, origins, dirs, tmax=None, skip_prim=None, any_hit=False):
         o, d = _f32(origins).reshape(-1, 3), _f32(dirs).reshape(-1, 3)

@@ -13,6 +13,7 @@
 //                     ready for a full-frame post-process?" (their result counters: ResultCounters in hr_ctx.h)
 //   hr_aov.inl        the AOV planes (include/hrcore_aov.h);  hr_denoise.inl  the denoiser over them (include/hrcore_denoise.h)
 //   hr_denoise_spatial.inl  the denoiser with a spatial variance estimate for pixels with few samples (include/hrcore_denoise_spatial.h)
+//   hr_despeckle.inl  firefly suppression: the outlier clamp the denoiser can be run behind (include/hrcore_despeckle.h)
 //   hr_adaptive.inl   the sample mask and the error estimate that builds it (include/hrcore_adaptive.h)
 //   hr_history.inl    history reprojection across a camera change (include/hrcore_history.h)
 //   hr_reproject.inl  its progressive form and the preview of unsampled pixels (include/hrcore_reproject.h)
@@ -155,6 +156,10 @@ static void aovFreePlanes(hr_ctx *c)
     if (c->dnPinned) hipHostFree(c->dnPinned);
     c->dnWork = c->dnOut = c->dnPinned = nullptr, c->dnPinnedBytes = 0;
     c->dnSpatial.free();
+    hipFree(c->dkPlanes); // (... and so do the despeckled frame and moments the denoiser can be run from)
+    if (c->dkPinned) hipHostFree(c->dkPinned);
+    c->dkPlanes = c->dkPinned = nullptr, c->dkPinnedBytes = 0;
+    c->dk.free();
     if (c->aovPinned) hipHostFree(c->aovPinned);
     c->aovPinned = nullptr, c->aovPinnedBytes = 0;
 }
@@ -771,6 +776,9 @@ int hr_debug_trace(hr_ctx *c, int32_t n, const float *o, const float *d, const f
 
 // ------------------------------------------------------------------------------------------ denoiser with the spatial variance estimate
 #include "hr_denoise_spatial.inl"
+
+// ------------------------------------------------------------------------------------------ firefly suppression ahead of the denoiser
+#include "hr_despeckle.inl"
 
 // ------------------------------------------------------------------------------------------ auto-exposure
 #include "hr_exposure.inl"

@@ -490,6 +490,12 @@ struct hr_ctx {
     ResultCounters<unsigned long long> mt; // kMtWords of hr_metric.h: the last measurement's bins, counters and max_abs bits
     uint32_t mtKind = 0, mtPasses = 0;     // ... its kind (HR_METRIC_*) and the frame's passes in it
     bool mtMeasured = false;               // `mt` holds a measurement (hr_metric_last)
+    // Firefly suppression (include/hrcore_despeckle.h).  The planes are made by the first call whose output does not go straight to the
+    // caller's memory and are freed with the denoiser's buffers (aovFreePlanes: hr_frame_resize, hr_aov_enable, hr_ctx_destroy).
+    float *dkPlanes = nullptr;             // 2 x W x H float4: the despeckled frame, then the despeckled moments
+    float *dkPinned = nullptr;             // the read-backs' host buffer: the same two images
+    size_t dkPinnedBytes = 0;
+    ResultCounters<unsigned long long> dk; // kDespeckleResultWords
     size_t aovFramesPerSlot() const { return (aovMask & HR_AOV_SURFACE) ? 2 : 0; }
     // Context group (include/hrcore_group.h): non-null when this handle is a group.  Its own fields then describe the ASSEMBLED frame on the
     // group's first device (W, H, frame, fbInternal, the read-back buffers) and `stream` is the assembly stream; no pass pipeline runs on it.

@@ -40,19 +40,33 @@ struct DenoiseSpatialRun {
     bool varianceOnly;           // stop after the estimate: cv[1] holds its variance, no image is written
 };
 
+// hr_despeckle.inl's calls: a pair that stands in for the frame and its MOMENTS plane, made on the ctx stream from the frame that the
+// caller's own frameReady (with the denoiser's need) has completed; ALBEDO and NORMAL_DEPTH stay the ctx's planes
+struct DenoiseSource {
+    const float *frame, *moments; // W x H float4 each, accumulation format, the frame's sample counts
+    uint32_t passes;              // what that frameReady gave
+};
+
 // Completes the passes, checks, and enqueues the filter on the ctx stream; the image goes to `out`, or to c->dnOut when out is null.
-// Without `spatial` every launch is hr_denoise's.
-static int denoiseRun(hr_ctx *c, const hr_denoise_params *params, float *out, uint32_t *passes, const DenoiseSpatialRun *spatial = nullptr)
+// Without `spatial` every launch is hr_denoise's.  With `source` the two launches that read the frame and the MOMENTS plane (Prepare
+// and the spatial estimate) read the pair instead; without it every launch and their order are as they were.
+static int denoiseRun(hr_ctx *c, const hr_denoise_params *params, float *out, uint32_t *passes, const DenoiseSpatialRun *spatial = nullptr,
+                      const DenoiseSource *source = nullptr)
 {
     hr_denoise_params p;
     int rc = denoiseCheckParams(c, params, &p);
     if (rc) return rc;
     if (c->W <= 0) FAIL(c, HR_ERR_INVALID, "no frame"); // (asked first: a sharded context without a frame hears this, not frameReady's refusal)
     uint32_t n = 0;
-    const float *frame = nullptr;
-    const FrameNeed need{HR_AOV_SURFACE | HR_AOV_MOMENTS, "denoise", "the filter", true, false, std::string("denoise") + kNeedsAovPlanes, std::string("denoise") + kAovPlanesLate};
-    rc = frameReady(c, need, &frame, &n);
-    if (rc) return rc;
+    const float *frame = nullptr, *moments = nullptr;
+    if (source) {
+        frame = source->frame, moments = source->moments, n = source->passes;
+    } else {
+        const FrameNeed need{HR_AOV_SURFACE | HR_AOV_MOMENTS, "denoise", "the filter", true, false, std::string("denoise") + kNeedsAovPlanes, std::string("denoise") + kAovPlanesLate};
+        rc = frameReady(c, need, &frame, &n);
+        if (rc) return rc;
+        moments = c->aovPlane[HR_AOV_PLANE_MOMENTS];
+    }
     rc = denoiseEnsureBuffers(c, out == nullptr && !(spatial && spatial->varianceOnly));
     if (rc) return rc;
     if (spatial) HIP_TRY(c, c->dnSpatial.ensure(kDenoiseSpatialResultWords));
@@ -60,7 +74,7 @@ static int denoiseRun(hr_ctx *c, const hr_denoise_params *params, float *out, ui
     const size_t px = (size_t)c->W * c->H;
     DenoiseBufs b;
     b.cv[0] = c->dnWork, b.cv[1] = b.cv[0] + 4 * px, b.nd = b.cv[1] + 4 * px, b.ac = b.nd + 4 * px, b.grad = b.ac + 4 * px;
-    launchDenoisePrepare(c->stream, c->W, c->H, frame, c->aovPlane[HR_AOV_PLANE_ALBEDO], c->aovPlane[HR_AOV_PLANE_NORMAL_DEPTH], c->aovPlane[HR_AOV_PLANE_MOMENTS], b);
+    launchDenoisePrepare(c->stream, c->W, c->H, frame, c->aovPlane[HR_AOV_PLANE_ALBEDO], c->aovPlane[HR_AOV_PLANE_NORMAL_DEPTH], moments, b);
     int first = 0; // the half of the ping-pong the iterations start from
     if (spatial) {
         HIP_TRY(c, c->dnSpatial.zero(c->stream));
@@ -85,13 +99,13 @@ static void denoiseSpatialFill(const hr_ctx *c, hr_denoise_spatial_result *out)
 }
 
 // The three calls of include/hrcore_denoise.h behind their argument checks.  hr_denoise_spatial.inl's calls are the same with `spatial`
-// (and a `result` to fetch); without it every launch, and their order, is the plain call's.
+// (and a `result` to fetch); without it every launch, and their order, is the plain call's.  hr_despeckle.inl's calls bring a `source`.
 static int denoiseToDevice(hr_ctx *c, const hr_denoise_params *params, const DenoiseSpatialRun *spatial, void *device_out, void *stream, uint32_t *passes,
-                           hr_denoise_spatial_result *result)
+                           hr_denoise_spatial_result *result, const DenoiseSource *source = nullptr)
 {
     // a foreign stream: filter on the ctx stream into the ctx's image, and copy out over there
     const bool foreign = stream && (hipStream_t)stream != c->stream;
-    int rc = denoiseRun(c, params, foreign ? nullptr : (float *)device_out, passes, spatial);
+    int rc = denoiseRun(c, params, foreign ? nullptr : (float *)device_out, passes, spatial, source);
     if (rc == HR_OK && result) { // (a result asked for: the call waits for the kernels)
         HIP_TRY(c, c->dnSpatial.fetch(c->stream));
         HIP_TRY(c, hipStreamSynchronize(c->stream));
@@ -102,9 +116,9 @@ static int denoiseToDevice(hr_ctx *c, const hr_denoise_params *params, const Den
 }
 
 static int denoiseReadback(hr_ctx *c, const hr_denoise_params *params, const DenoiseSpatialRun *spatial, const float **rgba, int32_t *w, int32_t *h, uint32_t *passes,
-                           hr_denoise_spatial_result *result)
+                           hr_denoise_spatial_result *result, const DenoiseSource *source = nullptr)
 {
-    int rc = denoiseRun(c, params, nullptr, passes, spatial);
+    int rc = denoiseRun(c, params, nullptr, passes, spatial, source);
     const size_t bytes = (size_t)c->W * c->H * 16;
     if (rc == HR_OK) rc = growPinned(c, c->dnPinned, c->dnPinnedBytes, bytes);
     if (rc) return rc;

@@ -12,6 +12,7 @@
 #include "../../include/hrcore_tree.h"
 #include "../../include/hrcore_exposure.h"
 #include "../../include/hrcore_metric.h"
+#include "../../include/hrcore_despeckle.h"
 
 #include <cstddef>
 
@@ -252,6 +253,17 @@ struct MtWindow; // hr_metric.h: the measured rectangle
 // kind 0 (compare): image against other = the reference; kind 1 (estimate): image = the frame, other = its MOMENTS plane; all W x H float4
 // -> words: kMtWords of hr_metric.h (the 256 bins of NUM, those of DEN, the four counters, the bits of max_abs), zeroed by the caller
 void launchMetricAccumulate(hipStream_t st, int numCUs, int W, int H, int kind, const float *image, const float *other, const MtWindow &win, unsigned long long *words);
+
+// ---- hr_despeckle.hip (include/hrcore_despeckle.h)
+// frame and moments (W x H float4 each) -> out and, where not null, momentsOut: the despeckled pair; no output is an input;
+// result: kDespeckleSlots copies of {valid, clamped, kept, starved, nonfinite pixels}, each copy on a 128-byte line of its own, zeroed by
+// the caller: a workgroup adds to copy blockIdx.x % kDespeckleSlots and the host sums the copies.  (Every workgroup of a frame adds to
+// `valid`, and atomics on ONE word serialise at about 12 ns each: with one copy the 8100 workgroups of a 1080p frame took 104 us whatever
+// else the kernel did or left out, profiles/despeckle_time.txt.)
+static const int kDespeckleCounters = 5, kDespeckleSlots = 64, kDespeckleSlotStride = 16;
+static const size_t kDespeckleResultWords = (size_t)kDespeckleSlots * kDespeckleSlotStride;
+void launchDespeckle(hipStream_t st, int W, int H, const float *frame, const float *moments, const hr_despeckle_params &p, float *out, float *momentsOut,
+                     unsigned long long *result);
 
 // ---- hr_build.hip
 // Per-geometry descriptor for the assemble kernel; all pointers are device pointers.  Attributes are addressed with a stride

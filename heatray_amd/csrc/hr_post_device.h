@@ -1,5 +1,5 @@
 // hr_post_device.h — what the kernels of the post-process features (hr_history.hip, hr_reproject.hip, hr_denoise_spatial.hip,
-// hr_adaptive.hip) share.  Device code only.  The workgroup counters: a kernel counts per wave (waveCount, waveSum), lane 0 of each wave
+// hr_adaptive.hip, hr_despeckle.hip) share.  Device code only.  The workgroup counters: a kernel counts per wave (waveCount, waveSum), lane 0 of each wave
 // adds into `sRed` in LDS under the kernel's own rule for what it adds, and wgCountersFlush sends the workgroup's totals on: integer
 // atomics, a result does not depend on their order.
 #pragma once

@@ -1,5 +1,5 @@
 // hr_postprocess.inl — a section of hr_core.hip (included before the feature sections): the host plumbing that the AOV planes, the
-// denoiser, adaptive sampling, history reprojection, the progressive merge, auto-exposure and the convergence metric share ("Adding a post-process feature"); the
+// denoiser, adaptive sampling, history reprojection, the progressive merge, auto-exposure, the convergence metric and firefly suppression share ("Adding a post-process feature"); the
 // result counters' type, ResultCounters, is in hr_ctx.h beside the context's fields of it.
 
 // `bytes` of device memory that is complete on the ctx stream -> dst, on `stream` (null: the ctx stream).  On a foreign stream the copy
