@@ -47,6 +47,7 @@ struct LaunchCfg {
     int packetSwizzle = 0; // k_raygen_packets deals whole 32x32 tiles to the XCDs instead of consecutive 16-pixel patches (HR_TUNE pswz)
     int packetStep = 1;    // k_raygen_packets tests a node's children once per packet against the packet's bounds (hr_ctx::useIntervalStep; hr_packet_interval.h)
     bool aovSurface = false; // HR_AOV_SURFACE is enabled: launch the shading kernel that records the first visible surface (include/hrcore_aov.h)
+    bool packetLens = false; // (LAST: hr_ctx::cfg fills the fields above by position)  a pass injected this step has a lens: k_raygen_packets_rays<.., false>, and SegDev::listed stays 0 (hr_pipeline.inl)
 };
 
 // One in-flight pass as seen by the kernels of one macro step.
@@ -76,6 +77,7 @@ struct SegDev {
     uint32_t sInCap;  // occlusion rays sqIn can hold
     uint32_t sOutCap; // occlusion rays sqOut can hold
     float *aov;       // HR_AOV_SURFACE: the pass's AOV record, two float4 per pixel (albedo + hit, normal + depth; full-frame indexing), or null
+    uint32_t listed;  // the packet kernel lists this entry's hits itself: k_shade_sort leaves the entry out
 };
 
 #ifndef HR_MAX_SEGS

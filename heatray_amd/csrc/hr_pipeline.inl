@@ -458,6 +458,7 @@ static int macroStep(hr_ctx *c, int g, int nInject)
         sg.qCountOut = &ps.ctr->qCount[(st + 1) % R];
         sg.sCountOut = &ps.ctr->sCount[st % R];
         sg.pCount = &ps.ctr->pCount[st % R], sg.gCount = &ps.ctr->gCount[st % R];
+        sg.listed = 0;
         sg.hitCap = closest ? boundIn[k] : 0u, sg.packets = 0; // (capacity of hits, the hit list and qout: what was carved above)
         sg.pp = ps.pp;
         sg.closestEnabled = closest ? 1 : 0;
@@ -486,6 +487,10 @@ static int macroStep(hr_ctx *c, int g, int nInject)
     const bool corunNow = packetsNow && (c->tune.corun == 2 || (c->tune.corun == 1 && c->lastOwnPerRay >= (double)c->tune.cmin));
     for (int j = 0; j < nInjectedSegs; ++j)
         if (packetsNow) tbl.seg[injectedSegs[j]].packets = corunNow ? 2 : 1;
+    bool anyLens = false; // (one decision per step: the table is copied before the launches are put together)
+    for (int j = 0; j < nInjectedSegs; ++j) anyLens = anyLens || tbl.seg[injectedSegs[j]].pp.aperture_radius > 1e-30f;
+    for (int j = 0; j < nInjectedSegs; ++j)
+        if (packetsNow && (!anyLens || cfg.collectStats)) tbl.seg[injectedSegs[j]].listed = 1; // (the kernels with the endings: hr_raygen.hip, launchRaygenPackets)
     tbl.hostCameraCount = corunNow ? G.dCounts + (size_t)kTableRing * kMaxSegs : nullptr;
     tbl.probe = c->dProbe, tbl.hostProbe = (g == 0 && (c->probePending || probeSeg >= 0)) ? G.dProbeHost + 8 * ring : nullptr; // (reported only while a probe is awaited)
     G.countN[ring] = n;
@@ -519,9 +524,8 @@ static int macroStep(hr_ctx *c, int g, int nInject)
             a.sample_index = b.sample_index = 0;
             uniformParams = std::memcmp(&a, &b, sizeof(a)) == 0;
         }
-        LaunchCfg cfgP = cfg; // (a pass with a lens: none of its packets has one origin, none can take the interval step)
-        for (int j = 0; j < segs.n; ++j)
-            if (tbl.seg[segs.seg[j]].pp.aperture_radius > 1e-30f) cfgP.packetStep = 0;
+        LaunchCfg cfgP = cfg; // (a step with a lens: none of its packets has one origin, none can take the interval step)
+        if (anyLens) cfgP.packetStep = 0, cfgP.packetLens = true; // (k_raygen_packets_rays<.., false>, whose hits k_shade_sort lists: `listed` above)
         if (corunNow) { // beside k_trace: fork after the table copy, join before the shading kernels
             LaunchCfg cb = cfgP;
             cb.stream = G.streamB;

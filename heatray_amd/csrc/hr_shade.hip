@@ -1,4 +1,5 @@
-// hr_shade.hip — the shading stage: k_shade_sort (misses shaded in place, hits appended to their pass's hit lists) and the sixteen
+// hr_shade.hip — the shading stage: k_shade_sort (misses shaded in place, hits appended to their pass's hit lists; the camera rays the packet
+// kernel traced are not its business: that kernel shades their misses and lists their hits itself, hr_raygen.hip, SegDev::listed) and the sixteen
 // k_shade_hit<MODE, CLS> (physicallyBased.rlsl / glass.rlsl on the hit lists).  The shaders themselves are hr_shade.h.
 #include "hr_kernels.h"
 #include "hr_display.h"
@@ -96,7 +97,8 @@ __global__ __launch_bounds__(kSortBlock) void k_shade_sort(const SceneDev *__res
             if (cnt) __hip_atomic_store(tbl->hostCameraCount, (uint32_t)(sum / cnt), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
         }
     }
-    buildStarts(start, nSeg, [&](int k) { return tbl->seg[k].closestEnabled ? closestCount(tbl->seg[k]) : 0u; });
+    // (an entry whose rays the packet kernel traced, shaded or listed itself is left out, as k_trace leaves it out with skipPackets)
+    buildStarts(start, nSeg, [&](int k) { return (tbl->seg[k].closestEnabled && !tbl->seg[k].listed) ? closestCount(tbl->seg[k]) : 0u; });
     const uint32_t total = start[nSeg];
     const bool glassToo = tbl->hasGlass != 0;
     uint32_t nAccum = 0;
