@@ -356,7 +356,29 @@ class DespeckleResult(C.Structure):
         return {k: getattr(self, k) for k, _ in self._fields_ if k != "reserved"}
 
 
-# The optional headers: feature -> (its symbols, the version the binding was written against, what "this library has no ..." calls it);
+# every symbol include/hrcore_mesh.h declares (mesh preparation: smooth normals and tangent frames for a mesh without them).  Resolved
+# lazily like the AOV symbols
+HR_MESH_API_VERSION = 1
+HR_MESH_WEIGHT_ANGLE, HR_MESH_WEIGHT_AREA, HR_MESH_WEIGHT_UNIFORM = 0, 1, 2
+HR_MESH_WANT_NORMALS, HR_MESH_WANT_TANGENTS = 1, 2
+MESH_SYMBOLS = ["mesh_api_version", "mesh_default_params", "mesh_prepare", "mesh_last"]
+
+
+class MeshParams(C.Structure):
+    """hr_mesh_params"""
+    _fields_ = [("weight", C.c_int32), ("weld", C.c_int32), ("want", C.c_int32), ("reserved", C.c_int32 * 5)]
+
+
+class MeshResult(C.Structure):
+    """hr_mesh_result"""
+    _fields_ = [("triangles", C.c_uint64), ("degenerate_triangles", C.c_uint64), ("degenerate_uv_triangles", C.c_uint64), ("weld_groups", C.c_uint64),
+                ("unreferenced_vertices", C.c_uint64), ("cancelled_vertices", C.c_uint64), ("fallback_tangents", C.c_uint64), ("max_valence", C.c_uint64)]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
+# The optional headers: feature ->(its symbols, the version the binding was written against, what "this library has no ..." calls it);
 # the version function is <feature>_api_version.  Engine._feature_call checks a feature on its first call
 FEATURES = {
     "aov": (AOV_SYMBOLS, HR_AOV_API_VERSION, "AOVs"),
@@ -369,6 +391,7 @@ FEATURES = {
     "exposure": (EXPOSURE_SYMBOLS, HR_EXPOSURE_API_VERSION, "auto-exposure"),
     "metric": (METRIC_SYMBOLS, HR_METRIC_API_VERSION, "convergence metric"),
     "despeckle": (DESPECKLE_SYMBOLS, HR_DESPECKLE_API_VERSION, "firefly suppression"),
+    "mesh": (MESH_SYMBOLS, HR_MESH_API_VERSION, "mesh preparation"),
 }
 
 
@@ -973,6 +996,49 @@ class Engine:
         self._feature_call("despeckle", "despeckle_denoise", C.byref(params) if params is not None else None, C.byref(dparams) if dparams is not None else None,
                            C.c_int32(int(bool(spatial))), C.byref(sparams) if sparams is not None else None, C.c_void_p(int(device_ptr) if device_ptr else 0),
                            C.c_void_p(stream or 0), None, None)
+
+    # -- mesh preparation (include/hrcore_mesh.h)
+    def prepare_mesh(self, positions, indices, uvs=None, normals=None, mode=HR_TRIANGLES, params=None, with_result=False):
+        """(normals, tangents, bitangents) of a mesh that comes without them, V x 3 float32 each, None for what params.want does not ask
+        for.  positions: V x 3, indices: the index list of `mode`; uvs (V x 2) are needed for tangents, normals (V x 3) for tangents
+        without normals.  Strided arrays go as they are (the last axis contiguous).  params: a MeshParams
+        (heatray_amd.meshprep.default_params()), None = the defaults.  with_result: and the MeshResult as a dict.  A side call: the scene
+        and the frame are left alone."""
+        def strided(a, comps):
+            if a is None:
+                return None, 0
+            a = np.asarray(a)
+            if a.dtype != np.float32 or a.ndim != 2 or a.shape[1] != comps or a.strides[1] != 4 or a.strides[0] < 4 * comps:
+                a = _f32(a).reshape(-1, comps)
+            return a, a.strides[0]
+        pos, ps = strided(positions, 3)
+        uv, us = strided(uvs, 2)
+        nrm, ns = strided(normals, 3)
+        idx = np.ascontiguousarray(indices, dtype=np.uint32).reshape(-1)
+        want = params.want if params is not None else HR_MESH_WANT_NORMALS
+        d = MeshDesc()
+        d.positions, d.uvs, d.normals = _ptr(pos), _ptr(uv), _ptr(nrm)
+        d.position_stride, d.uv_stride, d.normal_stride = ps, us, ns
+        d.n_vertices = pos.shape[0]
+        d.indices, d.n_indices, d.mode = _ptr(idx, u32p), idx.size, mode
+        out = [np.empty((pos.shape[0], 3), dtype=np.float32) if want & bit else None
+               for bit in (HR_MESH_WANT_NORMALS, HR_MESH_WANT_TANGENTS, HR_MESH_WANT_TANGENTS)]
+        r = MeshResult()
+        self._feature_call("mesh", "mesh_prepare", C.byref(d), C.byref(params) if params is not None else None, *(_ptr(a) for a in out), C.byref(r))
+        return (*out, r.as_dict()) if with_result else tuple(out)
+
+    def add_mesh_prepared(self, positions, indices, uvs=None, **add_mesh_kwargs):
+        """add_mesh for a mesh without normals: prepare_mesh makes them, and with uvs the tangents and bitangents too (weight ANGLE,
+        weld on); the remaining keywords are add_mesh's (mode included).  Returns the geometry id."""
+        p = MeshParams(HR_MESH_WEIGHT_ANGLE, 1, HR_MESH_WANT_NORMALS | (HR_MESH_WANT_TANGENTS if uvs is not None else 0))
+        n, t, b = self.prepare_mesh(positions, indices, uvs=uvs, mode=add_mesh_kwargs.get("mode", HR_TRIANGLES), params=p)
+        return self.add_mesh(positions, n, indices, uvs=uvs, tangents=t, bitangents=b, **add_mesh_kwargs)
+
+    def mesh_last(self):
+        """The last successful prepare_mesh's MeshResult as a dict."""
+        r = MeshResult()
+        self._feature_call("mesh", "mesh_last", C.byref(r))
+        return r.as_dict()
 
     def debug_trace(self, origins, dirs, tmax=None, skip_prim=None, any_hit=False):
         o, d = _f32(origins).reshape(-1, 3), _f32(dirs).reshape(-1, 3)

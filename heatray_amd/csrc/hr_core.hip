@@ -14,6 +14,7 @@
 //   hr_aov.inl        the AOV planes (include/hrcore_aov.h);  hr_denoise.inl  the denoiser over them (include/hrcore_denoise.h)
 //   hr_denoise_spatial.inl  the denoiser with a spatial variance estimate for pixels with few samples (include/hrcore_denoise_spatial.h)
 //   hr_despeckle.inl  firefly suppression: the outlier clamp the denoiser can be run behind (include/hrcore_despeckle.h)
+//   hr_mesh.inl       mesh preparation: smooth normals and tangent frames for a mesh without them (include/hrcore_mesh.h)
 //   hr_adaptive.inl   the sample mask and the error estimate that builds it (include/hrcore_adaptive.h)
 //   hr_history.inl    history reprojection across a camera change (include/hrcore_history.h)
 //   hr_reproject.inl  its progressive form and the preview of unsampled pixels (include/hrcore_reproject.h)
@@ -228,6 +229,15 @@ static void metricFree(hr_ctx *c)
     c->mtMeasured = false;
 }
 
+// Mesh preparation (include/hrcore_mesh.h): the scratch goes with the context
+static void meshPrepFree(hr_ctx *c)
+{
+    hipFree(c->msScratch);
+    c->msScratch = nullptr, c->msScratchBytes = 0;
+    c->ms.free();
+    c->msPrepared = false;
+}
+
 static void freeTree(hr_ctx *c)
 {
     hipFree(c->tree.nodes), hipFree(c->tree.nodes32), hipFree(c->tree.leafKeys), hipFree(c->tree.tris), hipFree(c->tree.nodeBox), hipFree(c->tree.slotOfPrim);
@@ -393,6 +403,7 @@ int hr_ctx_destroy(hr_ctx *c)
     reprojectFree(c);
     exposureFree(c);
     metricFree(c);
+    meshPrepFree(c);
     c->meshReleaseAll();
     for (int k = 0; k < 2; ++k) {
         if (c->stage[k]) hipHostFree(c->stage[k]);
@@ -785,3 +796,6 @@ int hr_debug_trace(hr_ctx *c, int32_t n, const float *o, const float *d, const f
 
 // ------------------------------------------------------------------------------------------ convergence metric
 #include "hr_metric.inl"
+
+// ------------------------------------------------------------------------------------------ mesh preparation
+#include "hr_mesh.inl"

@@ -496,6 +496,14 @@ struct hr_ctx {
     float *dkPinned = nullptr;             // the read-backs' host buffer: the same two images
     size_t dkPinnedBytes = 0;
     ResultCounters<unsigned long long> dk; // kDespeckleResultWords
+    // Mesh preparation (include/hrcore_mesh.h).  Nothing here depends on the frame or the scene: one block of scratch sized by the largest
+    // mesh prepared so far, grown only (meshPrepFree: hr_ctx_destroy), not counted against memBudget.  On a group's handle only msLast
+    // and msPrepared are used: the call itself runs on the first member.
+    char *msScratch = nullptr;
+    size_t msScratchBytes = 0;
+    ResultCounters<unsigned long long> ms; // kMsCounterWords
+    hr_mesh_result msLast{};               // the last successful hr_mesh_prepare's result
+    bool msPrepared = false;               // ... there has been one (hr_mesh_last)
     size_t aovFramesPerSlot() const { return (aovMask & HR_AOV_SURFACE) ? 2 : 0; }
     // Context group (include/hrcore_group.h): non-null when this handle is a group.  Its own fields then describe the ASSEMBLED frame on the
     // group's first device (W, H, frame, fbInternal, the read-back buffers) and `stream` is the assembly stream; no pass pipeline runs on it.

@@ -13,6 +13,7 @@
 #include "../../include/hrcore_exposure.h"
 #include "../../include/hrcore_metric.h"
 #include "../../include/hrcore_despeckle.h"
+#include "../../include/hrcore_mesh.h"
 
 #include <cstddef>
 
@@ -266,6 +267,30 @@ static const int kDespeckleCounters = 5, kDespeckleSlots = 64, kDespeckleSlotStr
 static const size_t kDespeckleResultWords = (size_t)kDespeckleSlots * kDespeckleSlotStride;
 void launchDespeckle(hipStream_t st, int W, int H, const float *frame, const float *moments, const hr_despeckle_params &p, float *out, float *momentsOut,
                      unsigned long long *result);
+
+// ---- hr_mesh.hip (include/hrcore_mesh.h)
+// What one hr_mesh_prepare holds on the device, cut out of the context's scratch by hr_mesh.inl.  V vertices, T triangles, C = 3 T
+// corners.  The four sort arrays hold max(C, V) words each (the corner sort, then the weld's sorts), blockHist 256 words per sort tile.
+struct MsBufs {
+    const float *pos, *uv, *nrmIn; // tightly packed: 3, 2, 3 floats per vertex (uv / nrmIn null unless read)
+    const uint32_t *idx;
+    uint32_t V, T, C;
+    int32_t strip, weight, weld, want;
+    uint8_t *tflag;                // per triangle: MS_FACE | MS_UV
+    float *cN, *cT, *cB;           // per corner: the contributions (cT, cB with tangents only)
+    uint32_t *keysA, *keysB, *valsA, *valsB, *blockHist;
+    uint32_t *vBegin, *vEnd, *vFirst; // per vertex: its range in the sorted corners, its lowest non-degenerate corner
+    float *vS, *vTa, *vBa;            // per vertex: the sums
+    uint32_t *perm, *groupOf, *groupStart, *scan, *nGroups; // the weld: sorted vertex ids, vertex -> group, group -> first place in perm (V + 1), the heads' scan, one word
+    float *gN;                     // per group: the normal
+    uint8_t *gClass;               // ... and MS_NORMAL / MS_CANCELLED / MS_UNREFERENCED
+    float *outN, *outT, *outB;     // per vertex: the outputs, 3 floats each
+    unsigned long long *counters;  // kMsCounterWords, zeroed by the caller
+};
+enum { kMsDegenerate = 0, kMsDegenerateUv = 1, kMsUnreferenced = 2, kMsCancelled = 3, kMsFallback = 4, kMsMaxValence = 5, kMsGroups = 6 };
+static const size_t kMsCounterWords = 8;
+size_t meshSortBlocks(size_t n); // sort tiles of n keys
+void launchMeshPrepare(hipStream_t st, const MsBufs &b);
 
 // ---- hr_build.hip
 // Per-geometry descriptor for the assemble kernel; all pointers are device pointers.  Attributes are addressed with a stride
