@@ -25,8 +25,8 @@ static int adaptiveCheckParams(hr_ctx *c, const hr_adaptive_params *in, hr_adapt
 
 static int sampleMaskEnsure(hr_ctx *c, bool bytesToo)
 {
-    if (!c->smWords) HIP_TRY(c, hipMalloc((void **)&c->smWords, sampleMaskWords(c->W, c->H) * 4));
-    if (bytesToo && !c->smBytes) HIP_TRY(c, hipMalloc((void **)&c->smBytes, (size_t)c->W * c->H));
+    if (!c->adaptive.maskWords) HIP_TRY(c, hipMalloc((void **)&c->adaptive.maskWords, sampleMaskWords(c->W, c->H) * 4));
+    if (bytesToo && !c->adaptive.maskBytes) HIP_TRY(c, hipMalloc((void **)&c->adaptive.maskBytes, (size_t)c->W * c->H));
     return HR_OK;
 }
 
@@ -42,27 +42,27 @@ static int sampleMaskSetPlain(hr_ctx *c, const uint8_t *mask)
     }
     rc = sampleMaskEnsure(c, true);
     if (rc) return rc;
-    HIP_TRY(c, hipMemcpyAsync(c->smBytes, mask, (size_t)c->W * c->H, hipMemcpyHostToDevice, c->stream));
-    launchMaskPack(c->stream, c->W, c->H, c->smBytes, c->smWords);
+    HIP_TRY(c, hipMemcpyAsync(c->adaptive.maskBytes, mask, (size_t)c->W * c->H, hipMemcpyHostToDevice, c->stream));
+    launchMaskPack(c->stream, c->W, c->H, c->adaptive.maskBytes, c->adaptive.maskWords);
     HIP_TRY(c, hipGetLastError());
     HIP_TRY(c, hipStreamSynchronize(c->stream)); // (the caller's bytes are pageable host memory: read before the call returns)
-    c->frame.mask = c->smWords;
+    c->frame.mask = c->adaptive.maskWords;
     return HR_OK;
 }
 
 // a context group: the words on the group's first device (complete: its stream was synchronised) -> every member, installed there
 static int groupSampleMaskDistribute(hr_ctx *c)
 {
-    const uint32_t *src = c->smWords;
+    const uint32_t *src = c->adaptive.maskWords;
     const int dev0 = c->device;
     const size_t bytes = sampleMaskWords(c->W, c->H) * 4;
     return groupAll(c, [=](hr_ctx *m, int) {
         int rc = drainPipeline(m);
         if (rc == HR_OK) rc = sampleMaskEnsure(m, false);
         if (rc) return rc;
-        HIP_TRY(m, hipMemcpyPeerAsync(m->smWords, m->device, src, dev0, bytes, m->stream));
+        HIP_TRY(m, hipMemcpyPeerAsync(m->adaptive.maskWords, m->device, src, dev0, bytes, m->stream));
         HIP_TRY(m, hipStreamSynchronize(m->stream)); // (the source is the group's buffer, which its next call may rewrite)
-        m->frame.mask = m->smWords;
+        m->frame.mask = m->adaptive.maskWords;
         return HR_OK;
     });
 }
@@ -78,13 +78,13 @@ static int groupSampleMaskSet(hr_ctx *c, const uint8_t *mask)
     }
     int rc = sampleMaskEnsure(c, true);
     if (rc) return rc;
-    HIP_TRY(c, hipMemcpyAsync(c->smBytes, mask, (size_t)c->W * c->H, hipMemcpyHostToDevice, c->stream));
-    launchMaskPack(c->stream, c->W, c->H, c->smBytes, c->smWords);
+    HIP_TRY(c, hipMemcpyAsync(c->adaptive.maskBytes, mask, (size_t)c->W * c->H, hipMemcpyHostToDevice, c->stream));
+    launchMaskPack(c->stream, c->W, c->H, c->adaptive.maskBytes, c->adaptive.maskWords);
     HIP_TRY(c, hipGetLastError());
     HIP_TRY(c, hipStreamSynchronize(c->stream));
     rc = groupSampleMaskDistribute(c);
     if (rc) return rc;
-    c->frame.mask = c->smWords;
+    c->frame.mask = c->adaptive.maskWords;
     return HR_OK;
 }
 
@@ -118,9 +118,9 @@ int hr_sample_mask_get(hr_ctx *c, uint8_t *out, int32_t *installed)
     }
     const int rc = sampleMaskEnsure(c, true);
     if (rc) return rc;
-    launchMaskUnpack(c->stream, c->W, c->H, c->frame.mask, c->smBytes); // (a group's handle holds the copy its members were sent)
+    launchMaskUnpack(c->stream, c->W, c->H, c->frame.mask, c->adaptive.maskBytes); // (a group's handle holds the copy its members were sent)
     HIP_TRY(c, hipGetLastError());
-    HIP_TRY(c, hipMemcpyAsync(out, c->smBytes, px, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipMemcpyAsync(out, c->adaptive.maskBytes, px, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(c, hipStreamSynchronize(c->stream));
     return HR_OK;
 }
@@ -139,32 +139,32 @@ int hr_adaptive_update(hr_ctx *c, const hr_adaptive_params *params, int32_t inst
     rc = frameReady(c, need, &frame, &n);
     if (rc) return rc;
     const size_t px = (size_t)c->W * c->H, maskBytes = sampleMaskWords(c->W, c->H) * 4;
-    if (!c->adError) HIP_TRY(c, hipMalloc((void **)&c->adError, px * 4));
-    if (!c->adWords) HIP_TRY(c, hipMalloc((void **)&c->adWords, maskBytes));
-    HIP_TRY(c, c->ad.ensure(kAdaptiveResultWords));
+    if (!c->adaptive.error) HIP_TRY(c, hipMalloc((void **)&c->adaptive.error, px * 4));
+    if (!c->adaptive.builtWords) HIP_TRY(c, hipMalloc((void **)&c->adaptive.builtWords, maskBytes));
+    HIP_TRY(c, c->adaptive.result.ensure(kAdaptiveResultWords));
     if (install) {
         rc = sampleMaskEnsure(c, false);
         if (rc) return rc;
     }
-    HIP_TRY(c, c->ad.zero(c->stream));
-    launchAdaptiveError(c->stream, c->W, c->H, frame, c->aovPlane[HR_AOV_PLANE_MOMENTS], p, c->adError);
-    launchAdaptiveMask(c->stream, c->W, c->H, c->adError, p, c->adWords, c->ad.dev);
+    HIP_TRY(c, c->adaptive.result.zero(c->stream));
+    launchAdaptiveError(c->stream, c->W, c->H, frame, c->aov.plane[HR_AOV_PLANE_MOMENTS], p, c->adaptive.error);
+    launchAdaptiveMask(c->stream, c->W, c->H, c->adaptive.error, p, c->adaptive.builtWords, c->adaptive.result.dev);
     HIP_TRY(c, hipGetLastError());
-    c->adErrorValid = true;
-    if (install) HIP_TRY(c, hipMemcpyAsync(c->smWords, c->adWords, maskBytes, hipMemcpyDeviceToDevice, c->stream));
-    HIP_TRY(c, c->ad.fetch(c->stream));
+    c->adaptive.errorValid = true;
+    if (install) HIP_TRY(c, hipMemcpyAsync(c->adaptive.maskWords, c->adaptive.builtWords, maskBytes, hipMemcpyDeviceToDevice, c->stream));
+    HIP_TRY(c, c->adaptive.result.fetch(c->stream));
     HIP_TRY(c, hipStreamSynchronize(c->stream));
     if (install) {
         if (c->grp) {
             rc = groupSampleMaskDistribute(c);
             if (rc) return rc;
         }
-        c->frame.mask = c->smWords;
+        c->frame.mask = c->adaptive.maskWords;
     }
     if (out) {
         *out = hr_adaptive_result{};
-        out->unconverged_pixels = c->ad.host[0], out->active_pixels = c->ad.host[1];
-        std::memcpy(&out->max_error, &c->ad.host[2], 4);
+        out->unconverged_pixels = c->adaptive.result.host[0], out->active_pixels = c->adaptive.result.host[1];
+        std::memcpy(&out->max_error, &c->adaptive.result.host[2], 4);
         out->passes = n;
     }
     return HR_OK;
@@ -175,8 +175,8 @@ int hr_adaptive_error_copy(hr_ctx *c, void *device_out, void *stream)
     ENTER(c);
     if (!device_out) FAIL(c, HR_ERR_INVALID, "null output");
     if (c->W <= 0) FAIL(c, HR_ERR_INVALID, "no frame");
-    if (!c->adErrorValid) FAIL(c, HR_ERR_INVALID, "adaptive: no error map: hr_adaptive_update has not run since the frame was last resized");
-    return copyOutOnStream(c, device_out, c->adError, (size_t)c->W * c->H * sizeof(float), stream); // (the next update rewrites the map: behind the copy)
+    if (!c->adaptive.errorValid) FAIL(c, HR_ERR_INVALID, "adaptive: no error map: hr_adaptive_update has not run since the frame was last resized");
+    return copyOutOnStream(c, device_out, c->adaptive.error, (size_t)c->W * c->H * sizeof(float), stream); // (the next update rewrites the map: behind the copy)
 }
 
 int hr_adaptive_error_readback(hr_ctx *c, float *host_out)
@@ -184,8 +184,8 @@ int hr_adaptive_error_readback(hr_ctx *c, float *host_out)
     ENTER(c);
     if (!host_out) FAIL(c, HR_ERR_INVALID, "null output");
     if (c->W <= 0) FAIL(c, HR_ERR_INVALID, "no frame");
-    if (!c->adErrorValid) FAIL(c, HR_ERR_INVALID, "adaptive: no error map: hr_adaptive_update has not run since the frame was last resized");
-    HIP_TRY(c, hipMemcpyAsync(host_out, c->adError, (size_t)c->W * c->H * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+    if (!c->adaptive.errorValid) FAIL(c, HR_ERR_INVALID, "adaptive: no error map: hr_adaptive_update has not run since the frame was last resized");
+    HIP_TRY(c, hipMemcpyAsync(host_out, c->adaptive.error, (size_t)c->W * c->H * sizeof(float), hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(c, hipStreamSynchronize(c->stream));
     return HR_OK;
 }

@@ -8,7 +8,7 @@ static int aovCheckPlane(hr_ctx *c, int32_t plane)
 {
     if (plane < 0 || plane > HR_AOV_PLANE_MOMENTS) FAIL(c, HR_ERR_INVALID, "bad AOV plane id " + std::to_string(plane));
     if (c->W <= 0) FAIL(c, HR_ERR_INVALID, "no frame");
-    if (!c->aovPlane[plane])
+    if (!c->aov.plane[plane])
         FAIL(c, HR_ERR_INVALID, std::string("AOV plane ") + kAovPlaneNames[plane] + " is not enabled (hr_aov_enable with " +
                                     (plane == HR_AOV_PLANE_MOMENTS ? "HR_AOV_MOMENTS" : "HR_AOV_SURFACE") + ")");
     return HR_OK;
@@ -19,9 +19,9 @@ static int groupAovEnable(hr_ctx *c, uint32_t mask)
 {
     int rc = groupAll(c, [mask](hr_ctx *m, int) { return hr_aov_enable(m, mask); });
     if (rc) return rc;
-    if (mask == c->aovMask) return HR_OK;
+    if (mask == c->aov.mask) return HR_OK;
     HIP_TRY(c, hipStreamSynchronize(c->stream)); // (a gather in flight writes the planes about to go)
-    c->aovMask = mask;
+    c->aov.mask = mask;
     return aovAllocPlanes(c);
 }
 
@@ -42,13 +42,13 @@ static int groupAovAssemble(hr_ctx *c, int32_t plane, uint64_t *passes)
         if (M.slots) {
             if (afterGather) HIP_TRY(m, hipStreamWaitEvent(m->stream, evGathered, 0)); // the last gather has read the buffer
             FrameDev fr = m->frame;
-            fr.fb = m->aovPlane[plane];
-            launchPackOwned(m->cfg(m->stream), fr, m->aovPlane[plane], M.packed, 0, nullptr);
+            fr.fb = m->aov.plane[plane];
+            launchPackOwned(m->cfg(m->stream), fr, m->aov.plane[plane], M.packed, 0, nullptr);
             HIP_TRY(m, hipGetLastError());
             if (M.staging) HIP_TRY(m, hipMemcpyPeerAsync(M.staging, dev0, M.packed, M.device, M.slots * 16, m->stream));
         }
         HIP_TRY(m, hipEventRecord(M.evPacked, m->stream));
-        M.passes = (uint32_t)(m->nextResolveOrder - m->aovZeroedAt);
+        M.passes = (uint32_t)(m->nextResolveOrder - m->aov.zeroedAt);
         return HR_OK;
     });
     if (rc) return rc;
@@ -66,7 +66,7 @@ static int groupAovAssemble(hr_ctx *c, int32_t plane, uint64_t *passes)
         if (M.slots) fewest = any ? std::min<uint64_t>(fewest, M.passes) : M.passes, any = true;
     }
     list.blockStart[g->n] = blocks;
-    launchGatherMembers(c->cfg(c->stream), c->frame, list, c->aovPlane[plane]);
+    launchGatherMembers(c->cfg(c->stream), c->frame, list, c->aov.plane[plane]);
     HIP_TRY(c, hipGetLastError());
     HIP_TRY(c, hipEventRecord(g->evGathered, c->stream));
     g->gathered = true;
@@ -83,17 +83,17 @@ int hr_aov_enable(hr_ctx *c, uint32_t mask)
     ENTER(c);
     if (mask & ~(HR_AOV_SURFACE | HR_AOV_MOMENTS)) FAIL(c, HR_ERR_INVALID, "unknown AOV mask bits " + std::to_string(mask & ~(HR_AOV_SURFACE | HR_AOV_MOMENTS)));
     if (c->grp) return groupAovEnable(c, mask);
-    if (mask == c->aovMask) return HR_OK;
+    if (mask == c->aov.mask) return HR_OK;
     QUIESCE(c);
     // HR_AOV_SURFACE changes what a pass slot holds: the slots are released and re-allocated with the new size (as when
     // HR_ESTIMATOR_ALL_LIGHTS is first used)
-    const bool slotsChange = ((mask ^ c->aovMask) & HR_AOV_SURFACE) != 0;
+    const bool slotsChange = ((mask ^ c->aov.mask) & HR_AOV_SURFACE) != 0;
     if (slotsChange) {
         const uint32_t keepCap = c->queueCapacity;
         freeQueues(c);
         c->queueCapacity = keepCap;
     }
-    c->aovMask = mask;
+    c->aov.mask = mask;
     const int rc = aovAllocPlanes(c);
     if (rc) return rc;
     if (slotsChange) slotBudget(c);
@@ -104,7 +104,7 @@ int hr_aov_mask(hr_ctx *c, uint32_t *mask)
 {
     ENTER(c);
     if (!mask) FAIL(c, HR_ERR_INVALID, "null output");
-    *mask = c->aovMask;
+    *mask = c->aov.mask;
     return HR_OK;
 }
 
@@ -120,17 +120,17 @@ int hr_aov_readback(hr_ctx *c, int32_t plane, const float **rgba, int32_t *w, in
         rc = groupAovAssemble(c, plane, &n);
     } else {
         rc = drainPipeline(c);
-        n = c->nextResolveOrder - c->aovZeroedAt;
+        n = c->nextResolveOrder - c->aov.zeroedAt;
     }
-    if (rc == HR_OK) rc = growPinned(c, c->aovPinned, c->aovPinnedBytes, bytes);
+    if (rc == HR_OK) rc = c->aov.pinned.grow(c, bytes);
     if (rc) return rc;
-    HIP_TRY(c, hipMemcpyAsync(c->aovPinned, c->aovPlane[plane], bytes, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipMemcpyAsync(c->aov.pinned.ptr, c->aov.plane[plane], bytes, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(c, hipStreamSynchronize(c->stream));
     if (!c->grp) {
         rc = overflowCheck(c);
         if (rc) return rc;
     }
-    *rgba = c->aovPinned;
+    *rgba = c->aov.pinned.ptr;
     if (w) *w = c->W;
     if (h) *h = c->H;
     if (passes) *passes = n;
@@ -145,7 +145,7 @@ int hr_aov_copy(hr_ctx *c, int32_t plane, void *device_out, void *stream)
     if (rc) return rc;
     rc = c->grp ? groupAovAssemble(c, plane, nullptr) : drainPipeline(c);
     if (rc) return rc;
-    return copyOutOnStream(c, device_out, c->aovPlane[plane], (size_t)c->W * c->H * 4 * sizeof(float), stream); // (the next resolve or gather rewrites the plane: behind the copy)
+    return copyOutOnStream(c, device_out, c->aov.plane[plane], (size_t)c->W * c->H * 4 * sizeof(float), stream); // (the next resolve or gather rewrites the plane: behind the copy)
 }
 
 } // extern "C"

@@ -5,12 +5,14 @@
 // that needs one fails with HR_ERR_DEVICE.
 //
 //   hr_ctx.h          the context (what the opaque handle points to), the error macros
+//   hr_features.h     the state of the post-process features, one struct per feature with a release(); PinnedBuf, ResultCounters
 //   hr_core.hip       this file: context life cycle, frame, display, read-backs, statistics
 //   hr_scene.inl      geometry ingest, commit (build / refit / tree cache), textures, materials, lights, sample tables
 //   hr_pipeline.inl   ray memory, the macro step, batching and the packet selector, hr_render_pass, the step log
 //   hr_group.inl      context groups (include/hrcore_group.h): member threads, the assembly of the members' tiles
-//   hr_postprocess.inl  what the sections below share: the copy out on a caller's stream, the pinned read-back buffers, "is the frame
-//                     ready for a full-frame post-process?" (their result counters: ResultCounters in hr_ctx.h)
+//   hr_postprocess.inl  what the sections below share: the copy out on a caller's stream, "is the frame ready for a full-frame
+//                     post-process?", and the four functions that say when each feature's state goes (planes gone, frame resized,
+//                     frame cleared, context destroyed)
 //   hr_aov.inl        the AOV planes (include/hrcore_aov.h);  hr_denoise.inl  the denoiser over them (include/hrcore_denoise.h)
 //   hr_denoise_spatial.inl  the denoiser with a spatial variance estimate for pixels with few samples (include/hrcore_denoise_spatial.h)
 //   hr_despeckle.inl  firefly suppression: the outlier clamp the denoiser can be run behind (include/hrcore_despeckle.h)
@@ -27,6 +29,7 @@
 
 static const int kTableRing = 4;
 static int drainPipeline(hr_ctx *c);
+static void featuresPlanesGone(hr_ctx *c), featuresFrameResized(hr_ctx *c), featuresFrameCleared(hr_ctx *c), featuresDestroyed(hr_ctx *c); // hr_postprocess.inl: when the features' state goes
 // A kernel found a ray queue longer than its capacity (hr_wave.h: queueOverflow): rays were dropped, the frame is not the render
 // that was asked for.  Sticky until hr_clear; every call that hands finished work to the caller reports it.
 static int overflowCheck(hr_ctx *c)
@@ -142,7 +145,7 @@ static void slotBudget(hr_ctx *c)
     c->maxSlots = kMaxSlots;
     if (hipMemGetInfo(&freeB, &totalB) == hipSuccess) {
         const size_t fbBytes = (size_t)c->W * c->H * 4 * sizeof(float);
-        const size_t k = (c->allLightsUsed ? 4 : 1) + c->aovFramesPerSlot();
+        const size_t k = (c->allLightsUsed ? 4 : 1) + c->aov.framesPerSlot();
         const size_t perSlot = fbBytes * k + sizeof(Counters);
         const size_t fit = (freeB / 2) / perSlot; // at most half of the free device memory for pass slots
         c->maxSlots = fit < 1 ? 1 : (fit > (size_t)kMaxSlots ? kMaxSlots : (int)fit);
@@ -150,92 +153,20 @@ static void slotBudget(hr_ctx *c)
 }
 
 // AOVs (include/hrcore_aov.h): the frame's planes of the enabled mask at the frame's size, zeroed on the ctx stream
-static void aovFreePlanes(hr_ctx *c)
-{
-    for (float *&p : c->aovPlane) hipFree(p), p = nullptr;
-    hipFree(c->dnWork), hipFree(c->dnOut); // (the denoiser's buffers live and die with the planes it reads)
-    if (c->dnPinned) hipHostFree(c->dnPinned);
-    c->dnWork = c->dnOut = c->dnPinned = nullptr, c->dnPinnedBytes = 0;
-    c->dnSpatial.free();
-    hipFree(c->dkPlanes); // (... and so do the despeckled frame and moments the denoiser can be run from)
-    if (c->dkPinned) hipHostFree(c->dkPinned);
-    c->dkPlanes = c->dkPinned = nullptr, c->dkPinnedBytes = 0;
-    c->dk.free();
-    if (c->aovPinned) hipHostFree(c->aovPinned);
-    c->aovPinned = nullptr, c->aovPinnedBytes = 0;
-}
-static void aovFree(hr_ctx *c)
-{
-    aovFreePlanes(c);
-    if (c->evAov) hipEventDestroy(c->evAov);
-    c->evAov = nullptr;
-}
 static int aovAllocPlanes(hr_ctx *c)
 {
-    aovFreePlanes(c);
-    c->aovZeroedAt = c->nextResolveOrder;
+    c->aov.freePlanes();
+    featuresPlanesGone(c);
+    c->aov.zeroedAt = c->nextResolveOrder;
     if (c->W <= 0) return HR_OK;
     const size_t bytes = (size_t)c->W * c->H * 4 * sizeof(float);
-    const bool want[3] = {(c->aovMask & HR_AOV_SURFACE) != 0, (c->aovMask & HR_AOV_SURFACE) != 0, (c->aovMask & HR_AOV_MOMENTS) != 0};
+    const bool want[3] = {(c->aov.mask & HR_AOV_SURFACE) != 0, (c->aov.mask & HR_AOV_SURFACE) != 0, (c->aov.mask & HR_AOV_MOMENTS) != 0};
     for (int p = 0; p < 3; ++p) {
         if (!want[p]) continue;
-        HIP_TRY(c, hipMalloc(&c->aovPlane[p], bytes));
-        HIP_TRY(c, hipMemsetAsync(c->aovPlane[p], 0, bytes, c->stream));
+        HIP_TRY(c, hipMalloc(&c->aov.plane[p], bytes));
+        HIP_TRY(c, hipMemsetAsync(c->aov.plane[p], 0, bytes, c->stream));
     }
     return HR_OK;
-}
-
-// Adaptive sampling (include/hrcore_adaptive.h): the mask and the update's buffers live and die with the frame's size
-static void adaptiveFree(hr_ctx *c)
-{
-    hipFree(c->smWords), hipFree(c->smBytes), hipFree(c->adError), hipFree(c->adWords);
-    c->ad.free();
-    c->smWords = c->adWords = nullptr, c->smBytes = nullptr, c->adError = nullptr;
-    c->adErrorValid = false;
-    c->frame.mask = nullptr;
-}
-
-// History reprojection (include/hrcore_history.h): the history goes with the frame's size, not with its contents
-static void historyFree(hr_ctx *c)
-{
-    hipFree(c->hsHist);
-    c->hs.free();
-    c->hsHist = nullptr;
-    c->hsCaptured = c->hsMerged = false, c->hsPasses = 0;
-}
-
-// Progressive merge and preview (include/hrcore_reproject.h): the examined bits and the preview's buffers go with the frame's size
-static void reprojectFree(hr_ctx *c)
-{
-    hipFree(c->rpExamined), hipFree(c->rpOut);
-    c->rp.free();
-    if (c->rpPinned) hipHostFree(c->rpPinned);
-    c->rpExamined = nullptr, c->rpOut = c->rpPinned = nullptr, c->rpPinnedBytes = 0;
-    c->rpStale = true, c->rpMerged = false;
-}
-
-// Auto-exposure (include/hrcore_exposure.h): the last metering and the adaptation state go with the context, not with the frame
-static void exposureFree(hr_ctx *c)
-{
-    hipFree(c->exState);
-    c->ex.free();
-    c->exState = nullptr, c->exMetered = false;
-}
-
-// The convergence metric (include/hrcore_metric.h): the last measurement goes with the context, not with the frame
-static void metricFree(hr_ctx *c)
-{
-    c->mt.free();
-    c->mtMeasured = false;
-}
-
-// Mesh preparation (include/hrcore_mesh.h): the scratch goes with the context
-static void meshPrepFree(hr_ctx *c)
-{
-    hipFree(c->msScratch);
-    c->msScratch = nullptr, c->msScratchBytes = 0;
-    c->ms.free();
-    c->msPrepared = false;
 }
 
 static void freeTree(hr_ctx *c)
@@ -391,19 +322,14 @@ int hr_ctx_destroy(hr_ctx *c)
     c->drainTimes();
     for (hipEvent_t e : c->eventPool) hipEventDestroy(e);
     if (c->evPack) hipEventDestroy(c->evPack);
+    if (c->evCopyOut) hipEventDestroy(c->evCopyOut);
     freeQueues(c);
     freeSceneDevice(c);
     for (Texture &t : c->textures) hipFree(t.dpx);
     hipFree(c->fbInternal);
-    if (c->pinned) hipHostFree(c->pinned);
+    c->pinned.release();
     hipFree(c->dDisplay);
-    aovFree(c);
-    adaptiveFree(c);
-    historyFree(c);
-    reprojectFree(c);
-    exposureFree(c);
-    metricFree(c);
-    meshPrepFree(c);
+    featuresDestroyed(c);
     c->meshReleaseAll();
     for (int k = 0; k < 2; ++k) {
         if (c->stage[k]) hipHostFree(c->stage[k]);
@@ -412,7 +338,7 @@ int hr_ctx_destroy(hr_ctx *c)
     hipFree(c->dConsts);
     hipFree(c->dEnvRowCdf), hipFree(c->dEnvColCdf), hipFree(c->dEnvProb), hipFree(c->dEnvRowGuide), hipFree(c->dEnvColGuide);
     if (c->hConsts) hipHostFree(c->hConsts);
-    if (c->pinnedDisplay) hipHostFree(c->pinnedDisplay);
+    c->pinnedDisplay.release();
     hipFree(c->dMaterials), hipFree(c->dTextures), hipFree(c->dSeq), hipFree(c->dAperture), hipFree(c->dSeqOffsets);
     hipFree(c->dTexDensity);
     for (Texture &t : c->textures) hipFree(t.dmips);
@@ -507,6 +433,16 @@ int hr_frame_unpack(hr_ctx *c, int32_t src_rank, int32_t world, const void *devi
 }
 
 static size_t displayPixelBytes(int32_t format) { return format == HR_DISPLAY_RGBA8 ? 4 : 16; }
+// the display read-backs' device staging and its pinned host copy, at least `need` bytes each; they only grow
+static int growDisplay(hr_ctx *c, size_t need)
+{
+    if (c->pinnedDisplay.bytes >= need) return HR_OK;
+    c->pinnedDisplay.release(); // (first: a failure below leaves no size behind, the next call starts over)
+    hipFree(c->dDisplay);
+    c->dDisplay = nullptr;
+    HIP_TRY(c, hipMalloc(&c->dDisplay, need));
+    return c->pinnedDisplay.grow(c, need);
+}
 
 int hr_display(hr_ctx *c, const hr_display_params *params, int32_t format, void *device_out, uint32_t *passes_shown)
 {
@@ -549,14 +485,7 @@ int hr_display_readback(hr_ctx *c, const hr_display_params *params, int32_t form
         if (rc) return rc;
     }
     const size_t need = (size_t)c->W * c->H * 16;
-    if (c->displayBytes < need) {
-        hipFree(c->dDisplay);
-        if (c->pinnedDisplay) hipHostFree(c->pinnedDisplay);
-        c->dDisplay = nullptr, c->pinnedDisplay = nullptr, c->displayBytes = 0;
-        HIP_TRY(c, hipMalloc(&c->dDisplay, need));
-        HIP_TRY(c, hipHostMalloc(&c->pinnedDisplay, need, hipHostMallocDefault));
-        c->displayBytes = need;
-    }
+    if (int rc = growDisplay(c, need)) return rc;
     if (format & HR_DISPLAY_PROGRESSIVE) { // lagged, like hr_readback_progressive
         int rc = completeForSlowCaller(c);
         if (rc) return rc;
@@ -579,9 +508,9 @@ int hr_display_readback(hr_ctx *c, const hr_display_params *params, int32_t form
     int rc = hr_display(c, params, format, c->dDisplay, passes_shown);
     if (rc) return rc;
     const size_t bytes = (size_t)c->W * c->H * displayPixelBytes(format & ~HR_DISPLAY_PROGRESSIVE);
-    HIP_TRY(c, hipMemcpyAsync(c->pinnedDisplay, c->dDisplay, bytes, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipMemcpyAsync(c->pinnedDisplay.ptr, c->dDisplay, bytes, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(c, hipStreamSynchronize(c->stream));
-    *pixels = c->pinnedDisplay;
+    *pixels = c->pinnedDisplay.ptr;
     if (width) *width = c->W;
     if (height) *height = c->H;
     return HR_OK;
@@ -609,19 +538,12 @@ int hr_frame_resize(hr_ctx *c, int32_t w, int32_t h)
     hipFree(c->fbInternal);
     c->fbInternal = nullptr;
     c->fbExternal = nullptr;
-    adaptiveFree(c); // (the sample mask goes with the frame it was made for)
-    historyFree(c);  // (... and so does a captured history)
-    reprojectFree(c); // (... and the examined bits of the progressive merge)
+    featuresFrameResized(c); // (the sample mask goes with the frame it was made for, and so do a captured history and the progressive merge's examined bits)
     const size_t fbBytes = (size_t)w * h * 4 * sizeof(float);
     HIP_TRY(c, hipMalloc(&c->fbInternal, fbBytes));
     HIP_TRY(c, hipMemsetAsync(c->fbInternal, 0, fbBytes, c->stream));
     c->frameZeroedAt = c->nextResolveOrder;
-    if (c->pinnedBytes < fbBytes) {
-        if (c->pinned) hipHostFree(c->pinned);
-        c->pinned = nullptr, c->pinnedBytes = 0;
-        HIP_TRY(c, hipHostMalloc((void **)&c->pinned, fbBytes, hipHostMallocDefault));
-        c->pinnedBytes = fbBytes;
-    }
+    if (int rc = c->pinned.grow(c, fbBytes)) return rc;
     FrameDev &f = c->frame;
     f.W = w, f.H = h, f.rank = c->rank, f.world = c->world, f.tile = c->tile;
     f.tilesX = (w + c->tile - 1) / c->tile, f.tilesY = (h + c->tile - 1) / c->tile;
@@ -695,13 +617,13 @@ int hr_readback(hr_ctx *c, const float **rgba, int32_t *w, int32_t *h)
         int rc = drainPipeline(c);
         if (rc) return rc;
     }
-    HIP_TRY(c, hipMemcpyAsync(c->pinned, c->fb(), bytes, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipMemcpyAsync(c->pinned.ptr, c->fb(), bytes, hipMemcpyDeviceToHost, c->stream));
     QUIESCE(c);
     {
         const int rc = overflowCheck(c);
         if (rc) return rc;
     }
-    *rgba = c->pinned;
+    *rgba = c->pinned.ptr;
     if (w) *w = c->W;
     if (h) *h = c->H;
     return HR_OK;

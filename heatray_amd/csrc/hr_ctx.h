@@ -1,10 +1,12 @@
 // hr_ctx.h — the context behind the opaque hr_ctx handle of include/hrcore.h: everything one context owns on the device and the
 // state of its pass pipeline, plus the error macros of the host side.  Included by hr_core.hip only (ONE translation unit: the
-// host side's helpers keep internal linkage); hr_scene.inl and hr_pipeline.inl are that file's two large sections.
+// host side's helpers keep internal linkage); hr_scene.inl and hr_pipeline.inl are that file's two large sections.  The state of the
+// optional post-process features is one member each, of the structs of hr_features.h (with PinnedBuf and ResultCounters).
 #pragma once
 #include "hr_kernels.h"
 #include "hr_trace.h"
 #include "hr_tune.h"
+#include "hr_features.h"
 
 #include <algorithm>
 #include <atomic>
@@ -59,28 +61,6 @@ static_assert(kMaxSlots == 2 * kMaxSegs, "hr_tune.h bounds depth= by the step ta
 #define HR_BATCH_CAP 32 // most passes injected per macro step (small frames / tile shards reach it: 1/8 of a 1080p frame runs 6.6 % faster with 32 than with 12, profiles/r2p_shard_batch.txt)
 #endif
 
-// The result counters of a post-process feature: a few device words its kernel adds into and their pinned host copy.  A call runs
-// ensure, zero, its launches and fetch (each under HIP_TRY), synchronises the stream and fills its result struct from `host`.
-template <class Word> struct ResultCounters {
-    Word *dev = nullptr, *host = nullptr;
-    size_t words = 0;
-    hipError_t ensure(size_t n) // both buffers of n words, made by the first call
-    {
-        words = n;
-        hipError_t e = dev ? hipSuccess : hipMalloc((void **)&dev, n * sizeof(Word));
-        return e == hipSuccess && !host ? hipHostMalloc((void **)&host, n * sizeof(Word), hipHostMallocDefault) : e;
-    }
-    hipError_t zero(hipStream_t st) { return hipMemsetAsync(dev, 0, words * sizeof(Word), st); }
-    // enqueues dev -> host and does not wait: the caller synchronises `st`, once, with whatever else it copies back
-    hipError_t fetch(hipStream_t st) { return hipMemcpyAsync(host, dev, words * sizeof(Word), hipMemcpyDeviceToHost, st); }
-    void free()
-    {
-        hipFree(dev);
-        if (host) hipHostFree(host);
-        dev = host = nullptr, words = 0;
-    }
-};
-
 struct hr_ctx {
     int device = 0;
     hipStream_t stream = nullptr;
@@ -94,10 +74,11 @@ struct hr_ctx {
     // frame
     int W = 0, H = 0;
     float *fbInternal = nullptr, *fbExternal = nullptr;
-    float *pinned = nullptr;
-    size_t pinnedBytes = 0;
+    PinnedBuf pinned; // hr_readback's host buffer
     hipEvent_t evPack = nullptr; // orders hr_frame_pack_owned on a foreign stream against the resolves on the ctx stream
-    void *dDisplay = nullptr, *pinnedDisplay = nullptr; // display resolve: device staging + pinned host copy
+    hipEvent_t evCopyOut = nullptr; // orders a post-process feature's copy out on a foreign stream against the ctx stream (copyOutOnStream)
+    void *dDisplay = nullptr; // display resolve: device staging + pinned host copy, grown together (growDisplay)
+    PinnedBuf pinnedDisplay;
     // Progressive snapshots are handed out one call late from rotating buffers: the host then waits for a copy enqueued a
     // whole call ago instead of for everything it has just enqueued, so the GPU always has the next step queued
     // (waiting for the latest copy cost 0.8 ms of idle GPU per pass).
@@ -114,8 +95,8 @@ struct hr_ctx {
     };
     Lagged progFrame, progDisplay;
     unsigned long long snapshotEpoch = 1; // bumped by clear / resize / bind: older snapshots are not handed out any more
-    size_t displayBytes = 0;
     FrameDev frame{};
+    unsigned long long frameZeroedAt = 0; // value of nextResolveOrder when the frame was last zeroed (hr_clear, hr_frame_resize): the AOV planes hold the frame's passes when aov.zeroedAt equals it
     uint32_t queueCapacity = 0;
     // Pipeline of in-flight passes (hr_trace.hip header): every slot owns the queues, hit records, counters and
     // the pass buffer of one pass.
@@ -440,77 +421,23 @@ struct hr_ctx {
 
     float *fb() const { return fbExternal ? fbExternal : fbInternal; }
     Tune tune; // the HR_TUNE knobs (hr_tune.h), parsed by hr_ctx_create and never written afterwards
-    // AOVs (include/hrcore_aov.h): the frame's planes, summed by k_resolve_aov in pass order beside the frame.  With HR_AOV_SURFACE every
-    // pass slot also holds the pass's AOV record (PassSlot::aov) and the shading kernel variant with MODE & 4 writes it.
-    uint32_t aovMask = 0;
-    float *aovPlane[3] = {nullptr, nullptr, nullptr}; // W x H float4 each (HR_AOV_PLANE_*), null when not enabled
-    float *aovPinned = nullptr;                       // hr_aov_readback's host buffer
-    size_t aovPinnedBytes = 0;
-    unsigned long long aovZeroedAt = 0;               // value of nextResolveOrder when the planes were last zeroed
-    hipEvent_t evAov = nullptr;                       // orders a copy out on a foreign stream against the ctx stream (copyOutOnStream)
-    // Denoiser (include/hrcore_denoise.h): working planes and result image, allocated by the first call, freed with the AOV planes
-    unsigned long long frameZeroedAt = 0; // value of nextResolveOrder when the frame was last zeroed (hr_clear, hr_frame_resize): the planes hold the frame's passes when aovZeroedAt equals it
-    float *dnWork = nullptr;    // kDenoiseBytesPerPixel x W x H, cut into DenoiseBufs
-    float *dnOut = nullptr;     // the result when it does not go straight to the caller's memory (W x H float4)
-    float *dnPinned = nullptr;  // hr_denoise_readback's host buffer
-    size_t dnPinnedBytes = 0;
-    ResultCounters<unsigned long long> dnSpatial; // kDenoiseSpatialResultWords (include/hrcore_denoise_spatial.h): made and freed with dnWork
-    // Adaptive sampling (include/hrcore_adaptive.h).  frame.mask is smWords while a mask is installed, null otherwise.  The buffers are made
-    // by the first call that needs them and go with the frame (adaptiveFree: hr_frame_resize, hr_ctx_destroy).
-    uint32_t *smWords = nullptr;  // the installed mask's words (sampleMaskWords)
-    uint8_t *smBytes = nullptr;   // W x H bytes: staging of the byte form (hr_sample_mask_set / _get)
-    float *adError = nullptr;     // W x H floats: the error map of the last hr_adaptive_update
-    uint32_t *adWords = nullptr;  // the mask that update built (copied to smWords when it is installed)
-    ResultCounters<uint32_t> ad;  // kAdaptiveResultWords
-    bool adErrorValid = false;    // adError holds an update's map at this frame size
-    // History reprojection (include/hrcore_history.h).  The history survives hr_clear; it goes with the frame's size (historyFree:
-    // hr_frame_resize, hr_history_drop, hr_ctx_destroy).
-    float *hsHist = nullptr;          // kHistoryBytesPerPixel x W x H: H0, H1, H2
-    bool hsCaptured = false;          // hsHist holds a capture
-    uint32_t hsPasses = 0;            // complete passes of the frame it was captured from
-    float hsView[16] = {0}, hsFovTan = 0.0f, hsAspect = 0.0f; // ... and its camera
-    bool hsMerged = false;            // the history has been merged into the frame since its last hr_clear
-    ResultCounters<unsigned long long> hs; // kHistoryResultWords
-    // Progressive merge and preview (include/hrcore_reproject.h).  Everything here goes with the frame's size (reprojectFree: hr_frame_resize,
-    // hr_ctx_destroy); hr_clear marks the examined bits stale and the next hr_reproject_merge zeroes them.
-    unsigned long long *rpExamined = nullptr; // rpExaminedWords(W, H) words: one per 8 x 8 block of pixels
-    bool rpStale = true;                      // the bits belong to an earlier frame (or were never zeroed): all pixels count as not examined
-    bool rpMerged = false;                    // hr_reproject_merge has merged into the frame since its last hr_clear (hsMerged is set with it)
-    ResultCounters<unsigned long long> rp;    // kReprojectResultWords (the preview uses the first three)
-    float *rpOut = nullptr;                   // the preview when it does not go straight to the caller's memory (W x H float4)
-    float *rpPinned = nullptr;                // hr_reproject_preview_readback's host buffer
-    size_t rpPinnedBytes = 0;
-    // Auto-exposure (include/hrcore_exposure.h).  Nothing here depends on the frame's size: hr_clear and hr_frame_resize leave it alone
-    // (exposureFree: hr_ctx_destroy).
-    ResultCounters<unsigned long long> ex; // kExWords of hr_exposure.h: the last metering's bins, class counters and reduced words
-    uint32_t *exState = nullptr;           // {there is an adaptation state, its scale's bits} on the device: hr_exposure_reset zeroes it
-    bool exMetered = false;                // `ex` holds a metering (hr_exposure_last)
-    // The convergence metric (include/hrcore_metric.h).  Nothing here depends on the frame's size: hr_clear and hr_frame_resize leave it
-    // alone (metricFree: hr_ctx_destroy).
-    ResultCounters<unsigned long long> mt; // kMtWords of hr_metric.h: the last measurement's bins, counters and max_abs bits
-    uint32_t mtKind = 0, mtPasses = 0;     // ... its kind (HR_METRIC_*) and the frame's passes in it
-    bool mtMeasured = false;               // `mt` holds a measurement (hr_metric_last)
-    // Firefly suppression (include/hrcore_despeckle.h).  The planes are made by the first call whose output does not go straight to the
-    // caller's memory and are freed with the denoiser's buffers (aovFreePlanes: hr_frame_resize, hr_aov_enable, hr_ctx_destroy).
-    float *dkPlanes = nullptr;             // 2 x W x H float4: the despeckled frame, then the despeckled moments
-    float *dkPinned = nullptr;             // the read-backs' host buffer: the same two images
-    size_t dkPinnedBytes = 0;
-    ResultCounters<unsigned long long> dk; // kDespeckleResultWords
-    // Mesh preparation (include/hrcore_mesh.h).  Nothing here depends on the frame or the scene: one block of scratch sized by the largest
-    // mesh prepared so far, grown only (meshPrepFree: hr_ctx_destroy), not counted against memBudget.  On a group's handle only msLast
-    // and msPrepared are used: the call itself runs on the first member.
-    char *msScratch = nullptr;
-    size_t msScratchBytes = 0;
-    ResultCounters<unsigned long long> ms; // kMsCounterWords
-    hr_mesh_result msLast{};               // the last successful hr_mesh_prepare's result
-    bool msPrepared = false;               // ... there has been one (hr_mesh_last)
-    size_t aovFramesPerSlot() const { return (aovMask & HR_AOV_SURFACE) ? 2 : 0; }
+    // The optional post-process features (hr_features.h).  When each one's state goes: featuresPlanesGone, featuresFrameResized,
+    // featuresFrameCleared and featuresDestroyed in hr_postprocess.inl.
+    AovState aov;
+    DenoiseState denoise;
+    AdaptiveState adaptive;
+    HistoryState history;
+    ReprojectState reproject;
+    ExposureState exposure;
+    MetricState metric;
+    DespeckleState despeckle;
+    MeshPrepState meshPrep;
     // Context group (include/hrcore_group.h): non-null when this handle is a group.  Its own fields then describe the ASSEMBLED frame on the
     // group's first device (W, H, frame, fbInternal, the read-back buffers) and `stream` is the assembly stream; no pass pipeline runs on it.
     GroupState *grp = nullptr;
     LaunchCfg cfg(hipStream_t st) const
     {
-        return LaunchCfg{st, numCUs, traceBlocks, tune.sblocks, collectStats, textureLodUsed, allLightsUsed, hasGlass, tune.pswz, useIntervalStep() ? 1 : 0, (aovMask & HR_AOV_SURFACE) != 0};
+        return LaunchCfg{st, numCUs, traceBlocks, tune.sblocks, collectStats, textureLodUsed, allLightsUsed, hasGlass, tune.pswz, useIntervalStep() ? 1 : 0, (aov.mask & HR_AOV_SURFACE) != 0};
     }
 };
 
@@ -533,3 +460,12 @@ struct hr_ctx {
     if (!(ctx)) return HR_ERR_INVALID;               \
     HIP_TRY(ctx, hipSetDevice((ctx)->device))
 
+
+inline int PinnedBuf::grow(hr_ctx *c, size_t need)
+{
+    if (bytes >= need) return HR_OK;
+    release();
+    HIP_TRY(c, hipHostMalloc((void **)&ptr, need, hipHostMallocDefault));
+    bytes = need;
+    return HR_OK;
+}

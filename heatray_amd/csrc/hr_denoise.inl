@@ -1,5 +1,5 @@
 // hr_denoise.inl — a section of hr_core.hip (included at its end): the entry points of include/hrcore_denoise.h.  The kernels are in
-// hr_denoise.hip; the buffers' life follows the AOV planes' (aovFreePlanes).  The calls of include/hrcore_denoise_spatial.h run through
+// hr_denoise.hip; the buffers' life follows the AOV planes' (featuresPlanesGone).  The calls of include/hrcore_denoise_spatial.h run through
 // the same three functions (denoiseToDevice, denoiseReadback, denoiseDisplay) with a DenoiseSpatialRun.
 
 // Which kernel runs an iteration when the caller leaves the choice to the library: the LDS-tiled kernel for the steps it exists for
@@ -29,8 +29,8 @@ static int denoiseCheckParams(hr_ctx *c, const hr_denoise_params *in, hr_denoise
 static int denoiseEnsureBuffers(hr_ctx *c, bool needOut)
 {
     const size_t px = (size_t)c->W * c->H;
-    if (!c->dnWork) HIP_TRY(c, hipMalloc((void **)&c->dnWork, px * kDenoiseBytesPerPixel));
-    if (needOut && !c->dnOut) HIP_TRY(c, hipMalloc((void **)&c->dnOut, px * 16));
+    if (!c->denoise.work) HIP_TRY(c, hipMalloc((void **)&c->denoise.work, px * kDenoiseBytesPerPixel));
+    if (needOut && !c->denoise.out) HIP_TRY(c, hipMalloc((void **)&c->denoise.out, px * 16));
     return HR_OK;
 }
 
@@ -47,7 +47,7 @@ struct DenoiseSource {
     uint32_t passes;              // what that frameReady gave
 };
 
-// Completes the passes, checks, and enqueues the filter on the ctx stream; the image goes to `out`, or to c->dnOut when out is null.
+// Completes the passes, checks, and enqueues the filter on the ctx stream; the image goes to `out`, or to c->denoise.out when out is null.
 // Without `spatial` every launch is hr_denoise's.  With `source` the two launches that read the frame and the MOMENTS plane (Prepare
 // and the spatial estimate) read the pair instead; without it every launch and their order are as they were.
 static int denoiseRun(hr_ctx *c, const hr_denoise_params *params, float *out, uint32_t *passes, const DenoiseSpatialRun *spatial = nullptr,
@@ -65,20 +65,20 @@ static int denoiseRun(hr_ctx *c, const hr_denoise_params *params, float *out, ui
         const FrameNeed need{HR_AOV_SURFACE | HR_AOV_MOMENTS, "denoise", "the filter", true, false, std::string("denoise") + kNeedsAovPlanes, std::string("denoise") + kAovPlanesLate};
         rc = frameReady(c, need, &frame, &n);
         if (rc) return rc;
-        moments = c->aovPlane[HR_AOV_PLANE_MOMENTS];
+        moments = c->aov.plane[HR_AOV_PLANE_MOMENTS];
     }
     rc = denoiseEnsureBuffers(c, out == nullptr && !(spatial && spatial->varianceOnly));
     if (rc) return rc;
-    if (spatial) HIP_TRY(c, c->dnSpatial.ensure(kDenoiseSpatialResultWords));
-    if (!out) out = c->dnOut;
+    if (spatial) HIP_TRY(c, c->denoise.spatial.ensure(kDenoiseSpatialResultWords));
+    if (!out) out = c->denoise.out;
     const size_t px = (size_t)c->W * c->H;
     DenoiseBufs b;
-    b.cv[0] = c->dnWork, b.cv[1] = b.cv[0] + 4 * px, b.nd = b.cv[1] + 4 * px, b.ac = b.nd + 4 * px, b.grad = b.ac + 4 * px;
-    launchDenoisePrepare(c->stream, c->W, c->H, frame, c->aovPlane[HR_AOV_PLANE_ALBEDO], c->aovPlane[HR_AOV_PLANE_NORMAL_DEPTH], moments, b);
+    b.cv[0] = c->denoise.work, b.cv[1] = b.cv[0] + 4 * px, b.nd = b.cv[1] + 4 * px, b.ac = b.nd + 4 * px, b.grad = b.ac + 4 * px;
+    launchDenoisePrepare(c->stream, c->W, c->H, frame, c->aov.plane[HR_AOV_PLANE_ALBEDO], c->aov.plane[HR_AOV_PLANE_NORMAL_DEPTH], moments, b);
     int first = 0; // the half of the ping-pong the iterations start from
     if (spatial) {
-        HIP_TRY(c, c->dnSpatial.zero(c->stream));
-        launchDenoiseSpatial(c->stream, c->W, c->H, frame, b, p, spatial->p, c->dnSpatial.dev); // cv[0] -> cv[1]: the same colour, the estimated variance
+        HIP_TRY(c, c->denoise.spatial.zero(c->stream));
+        launchDenoiseSpatial(c->stream, c->W, c->H, frame, b, p, spatial->p, c->denoise.spatial.dev); // cv[0] -> cv[1]: the same colour, the estimated variance
         first = 1;
     }
     const int iterations = (spatial && spatial->varianceOnly) ? -1 : p.iterations;
@@ -95,7 +95,7 @@ static void denoiseSpatialFill(const hr_ctx *c, hr_denoise_spatial_result *out)
 {
     if (!out) return;
     *out = hr_denoise_spatial_result{};
-    out->spatial_pixels = c->dnSpatial.host[0], out->estimated_pixels = c->dnSpatial.host[1], out->starved_pixels = c->dnSpatial.host[2];
+    out->spatial_pixels = c->denoise.spatial.host[0], out->estimated_pixels = c->denoise.spatial.host[1], out->starved_pixels = c->denoise.spatial.host[2];
 }
 
 // The three calls of include/hrcore_denoise.h behind their argument checks.  hr_denoise_spatial.inl's calls are the same with `spatial`
@@ -107,12 +107,12 @@ static int denoiseToDevice(hr_ctx *c, const hr_denoise_params *params, const Den
     const bool foreign = stream && (hipStream_t)stream != c->stream;
     int rc = denoiseRun(c, params, foreign ? nullptr : (float *)device_out, passes, spatial, source);
     if (rc == HR_OK && result) { // (a result asked for: the call waits for the kernels)
-        HIP_TRY(c, c->dnSpatial.fetch(c->stream));
+        HIP_TRY(c, c->denoise.spatial.fetch(c->stream));
         HIP_TRY(c, hipStreamSynchronize(c->stream));
         denoiseSpatialFill(c, result);
     }
     if (rc || !foreign) return rc;
-    return copyOutOnStream(c, device_out, c->dnOut, (size_t)c->W * c->H * 16, stream);
+    return copyOutOnStream(c, device_out, c->denoise.out, (size_t)c->W * c->H * 16, stream);
 }
 
 static int denoiseReadback(hr_ctx *c, const hr_denoise_params *params, const DenoiseSpatialRun *spatial, const float **rgba, int32_t *w, int32_t *h, uint32_t *passes,
@@ -120,13 +120,13 @@ static int denoiseReadback(hr_ctx *c, const hr_denoise_params *params, const Den
 {
     int rc = denoiseRun(c, params, nullptr, passes, spatial, source);
     const size_t bytes = (size_t)c->W * c->H * 16;
-    if (rc == HR_OK) rc = growPinned(c, c->dnPinned, c->dnPinnedBytes, bytes);
+    if (rc == HR_OK) rc = c->denoise.pinned.grow(c, bytes);
     if (rc) return rc;
-    HIP_TRY(c, hipMemcpyAsync(c->dnPinned, c->dnOut, bytes, hipMemcpyDeviceToHost, c->stream));
-    if (spatial) HIP_TRY(c, c->dnSpatial.fetch(c->stream));
+    HIP_TRY(c, hipMemcpyAsync(c->denoise.pinned.ptr, c->denoise.out, bytes, hipMemcpyDeviceToHost, c->stream));
+    if (spatial) HIP_TRY(c, c->denoise.spatial.fetch(c->stream));
     HIP_TRY(c, hipStreamSynchronize(c->stream)); // (one wait for the image and the counters)
     denoiseSpatialFill(c, result);
-    *rgba = c->dnPinned;
+    *rgba = c->denoise.pinned.ptr;
     if (w) *w = c->W;
     if (h) *h = c->H;
     return HR_OK;
@@ -138,7 +138,7 @@ static int denoiseDisplay(hr_ctx *c, const hr_denoise_params *params, const Deno
     int rc = denoiseRun(c, params, nullptr, passes_shown, spatial);
     if (rc) return rc;
     FrameDev fr = c->frame; // (denoiseRun has refused world > 1: every pixel is this context's; a group's frame is rank 0 of 1)
-    fr.fb = c->dnOut;
+    fr.fb = c->denoise.out;
     launchDisplay(c->cfg(c->stream), fr, *display, format, device_out);
     HIP_TRY(c, hipGetLastError());
     return HR_OK;

@@ -72,8 +72,8 @@ int hr_denoise_spatial_variance(hr_ctx *c, const hr_denoise_params *dparams, con
     if (rc) return rc;
     const size_t px = (size_t)c->W * c->H;
     std::vector<float> cv(px * 4); // (cv[1]: colour + variance; a call for inspection, not a hot path)
-    HIP_TRY(c, hipMemcpyAsync(cv.data(), c->dnWork + 4 * px, px * 16, hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(c, c->dnSpatial.fetch(c->stream));
+    HIP_TRY(c, hipMemcpyAsync(cv.data(), c->denoise.work + 4 * px, px * 16, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, c->denoise.spatial.fetch(c->stream));
     HIP_TRY(c, hipStreamSynchronize(c->stream));
     for (size_t i = 0; i < px; ++i) host_out[i] = cv[4 * i + 3];
     denoiseSpatialFill(c, result);

@@ -29,26 +29,26 @@ static void despeckleFill(const hr_ctx *c, hr_despeckle_result *out)
     if (!out) return;
     *out = hr_despeckle_result{};
     for (int s = 0; s < kDespeckleSlots; ++s) { // (the workgroups' adds are spread over copies of the counters: hr_kernels.h)
-        const unsigned long long *h = c->dk.host + (size_t)s * kDespeckleSlotStride;
+        const unsigned long long *h = c->despeckle.result.host + (size_t)s * kDespeckleSlotStride;
         out->valid_pixels += h[0], out->clamped_pixels += h[1], out->kept_pixels += h[2], out->starved_pixels += h[3], out->nonfinite_pixels += h[4];
     }
 }
 
 static int despeckleEnsurePlanes(hr_ctx *c)
 {
-    if (!c->dkPlanes) HIP_TRY(c, hipMalloc((void **)&c->dkPlanes, (size_t)c->W * c->H * 32));
+    if (!c->despeckle.planes) HIP_TRY(c, hipMalloc((void **)&c->despeckle.planes, (size_t)c->W * c->H * 32));
     return HR_OK;
 }
-static float *despeckleMomentsPlane(const hr_ctx *c) { return c->dkPlanes + (size_t)c->W * c->H * 4; }
+static float *despeckleMomentsPlane(const hr_ctx *c) { return c->despeckle.planes + (size_t)c->W * c->H * 4; }
 
 // the kernel over a ready pair, on the ctx stream; with `fetch` the counters' copy to the host is enqueued behind it (the caller waits)
 static int despeckleLaunch(hr_ctx *c, const hr_despeckle_params &p, const float *frame, const float *moments, float *out, float *momentsOut, bool fetch)
 {
-    HIP_TRY(c, c->dk.ensure(kDespeckleResultWords));
-    HIP_TRY(c, c->dk.zero(c->stream));
-    launchDespeckle(c->stream, c->W, c->H, frame, moments, p, out, momentsOut, c->dk.dev);
+    HIP_TRY(c, c->despeckle.result.ensure(kDespeckleResultWords));
+    HIP_TRY(c, c->despeckle.result.zero(c->stream));
+    launchDespeckle(c->stream, c->W, c->H, frame, moments, p, out, momentsOut, c->despeckle.result.dev);
     HIP_TRY(c, hipGetLastError());
-    if (fetch) HIP_TRY(c, c->dk.fetch(c->stream));
+    if (fetch) HIP_TRY(c, c->despeckle.result.fetch(c->stream));
     return HR_OK;
 }
 
@@ -63,11 +63,11 @@ static int despeckleOwnFrame(hr_ctx *c, const hr_despeckle_params &p, uint32_t a
     const float *frame = nullptr;
     int rc = frameReady(c, need, &frame, passes);
     if (rc) return rc;
-    const float *moments = c->aovPlane[HR_AOV_PLANE_MOMENTS];
+    const float *moments = c->aov.plane[HR_AOV_PLANE_MOMENTS];
     if (!out) {
         rc = despeckleEnsurePlanes(c);
         if (rc) return rc;
-        out = c->dkPlanes, momentsOut = despeckleMomentsPlane(c);
+        out = c->despeckle.planes, momentsOut = despeckleMomentsPlane(c);
     }
     return despeckleLaunch(c, p, frame, moments, out, momentsOut, fetch);
 }
@@ -86,7 +86,7 @@ static int despeckleDenoiseSource(hr_ctx *c, const hr_despeckle_params *params, 
     uint32_t n = 0;
     rc = despeckleOwnFrame(c, p, HR_AOV_SURFACE | HR_AOV_MOMENTS, fetch, nullptr, nullptr, &n);
     if (rc) return rc;
-    *source = DenoiseSource{c->dkPlanes, despeckleMomentsPlane(c), n};
+    *source = DenoiseSource{c->despeckle.planes, despeckleMomentsPlane(c), n};
     return HR_OK;
 }
 
@@ -110,7 +110,7 @@ int hr_despeckle(hr_ctx *c, const hr_despeckle_params *params, const void *devic
         FAIL(c, HR_ERR_INVALID, std::string("despeckle: device_frame and device_moments go together, and ") + (device_frame ? "device_moments" : "device_frame") + " is null");
     if (device_out == device_moments_out) FAIL(c, HR_ERR_INVALID, "despeckle: device_out and device_moments_out are the same memory");
     // the inputs as the kernel will read them (the ctx's own: null while there is no frame or no plane, which no output equals)
-    const void *inFrame = device_frame ? device_frame : (c->grp ? c->fbInternal : c->fb()), *inMoments = device_frame ? device_moments : c->aovPlane[HR_AOV_PLANE_MOMENTS];
+    const void *inFrame = device_frame ? device_frame : (c->grp ? c->fbInternal : c->fb()), *inMoments = device_frame ? device_moments : c->aov.plane[HR_AOV_PLANE_MOMENTS];
     if (device_out == inFrame || device_out == inMoments) FAIL(c, HR_ERR_INVALID, "despeckle: device_out is one of the inputs (the kernel reads neighbours)");
     if (device_moments_out && (device_moments_out == inFrame || device_moments_out == inMoments))
         FAIL(c, HR_ERR_INVALID, "despeckle: device_moments_out is one of the inputs (the kernel reads neighbours)");
@@ -126,7 +126,7 @@ int hr_despeckle(hr_ctx *c, const hr_despeckle_params *params, const void *devic
         rc = frameKindReady(c, need);
         if (rc == HR_OK && foreign) rc = despeckleEnsurePlanes(c);
         if (rc) return rc;
-        if (foreign) out = c->dkPlanes, momentsOut = despeckleMomentsPlane(c);
+        if (foreign) out = c->despeckle.planes, momentsOut = despeckleMomentsPlane(c);
         rc = despeckleLaunch(c, p, (const float *)device_frame, (const float *)device_moments, out, momentsOut, result != nullptr);
     } else {
         rc = despeckleOwnFrame(c, p, HR_AOV_MOMENTS, result != nullptr, out, momentsOut, &n);
@@ -134,7 +134,7 @@ int hr_despeckle(hr_ctx *c, const hr_despeckle_params *params, const void *devic
     if (rc) return rc;
     if (foreign) {
         const size_t bytes = (size_t)c->W * c->H * 16;
-        rc = copyOutOnStream(c, device_out, c->dkPlanes, bytes, stream);
+        rc = copyOutOnStream(c, device_out, c->despeckle.planes, bytes, stream);
         if (rc == HR_OK && device_moments_out) rc = copyOutOnStream(c, device_moments_out, despeckleMomentsPlane(c), bytes, stream);
         if (rc) return rc;
     }
@@ -156,13 +156,13 @@ int hr_despeckle_readback(hr_ctx *c, const hr_despeckle_params *params, const fl
     uint32_t n = 0;
     if (rc == HR_OK) rc = despeckleOwnFrame(c, p, HR_AOV_MOMENTS, true, nullptr, nullptr, &n);
     const size_t bytes = (size_t)c->W * c->H * 16;
-    if (rc == HR_OK) rc = growPinned(c, c->dkPinned, c->dkPinnedBytes, 2 * bytes);
+    if (rc == HR_OK) rc = c->despeckle.pinned.grow(c, 2 * bytes);
     if (rc) return rc;
-    HIP_TRY(c, hipMemcpyAsync(c->dkPinned, c->dkPlanes, moments ? 2 * bytes : bytes, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipMemcpyAsync(c->despeckle.pinned.ptr, c->despeckle.planes, moments ? 2 * bytes : bytes, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(c, hipStreamSynchronize(c->stream)); // (one wait for the images and the counters)
     despeckleFill(c, result);
-    *rgba = c->dkPinned;
-    if (moments) *moments = c->dkPinned + bytes / sizeof(float);
+    *rgba = c->despeckle.pinned.ptr;
+    if (moments) *moments = c->despeckle.pinned.ptr + bytes / sizeof(float);
     if (w) *w = c->W;
     if (h) *h = c->H;
     if (passes) *passes = n;

@@ -42,7 +42,7 @@ static int exposureWindow(hr_ctx *c, const hr_exposure_params &p, ExWindow *win)
 // the one place that reads the host words: the last fetched metering -> the result (and the bins)
 static void exposureFill(const hr_ctx *c, hr_exposure_result *out, uint64_t *bins)
 {
-    const unsigned long long *h = c->ex.host;
+    const unsigned long long *h = c->exposure.bins.host;
     const auto f = [h](int word) {
         const uint32_t b = (uint32_t)h[word];
         float v;
@@ -84,23 +84,23 @@ static int exposureRun(hr_ctx *c, const hr_exposure_params *params, const void *
     ExWindow win;
     rc = exposureWindow(c, p, &win);
     if (rc) return rc;
-    HIP_TRY(c, c->ex.ensure(kExWords));
-    if (!c->exState) {
-        HIP_TRY(c, hipMalloc((void **)&c->exState, 2 * sizeof(uint32_t)));
-        HIP_TRY(c, hipMemsetAsync(c->exState, 0, 2 * sizeof(uint32_t), c->stream));
+    HIP_TRY(c, c->exposure.bins.ensure(kExWords));
+    if (!c->exposure.state) {
+        HIP_TRY(c, hipMalloc((void **)&c->exposure.state, 2 * sizeof(uint32_t)));
+        HIP_TRY(c, hipMemsetAsync(c->exposure.state, 0, 2 * sizeof(uint32_t), c->stream));
     }
-    HIP_TRY(c, c->ex.zero(c->stream));
-    launchExposureMeter(c->stream, c->numCUs, c->W, c->H, *image, win, ExParams{p.key, p.low_permille, p.high_permille, p.min_scale, p.max_scale, p.adapt}, c->ex.dev,
-                        c->exState);
+    HIP_TRY(c, c->exposure.bins.zero(c->stream));
+    launchExposureMeter(c->stream, c->numCUs, c->W, c->H, *image, win, ExParams{p.key, p.low_permille, p.high_permille, p.min_scale, p.max_scale, p.adapt}, c->exposure.bins.dev,
+                        c->exposure.state);
     HIP_TRY(c, hipGetLastError());
-    c->exMetered = true;
+    c->exposure.metered = true;
     return HR_OK;
 }
 
 // the last metering, fetched and waited for, -> out
 static int exposureFetch(hr_ctx *c, hr_exposure_result *out, uint64_t *bins)
 {
-    HIP_TRY(c, c->ex.fetch(c->stream));
+    HIP_TRY(c, c->exposure.bins.fetch(c->stream));
     HIP_TRY(c, hipStreamSynchronize(c->stream));
     exposureFill(c, out, bins);
     return HR_OK;
@@ -143,7 +143,7 @@ int hr_exposure_display(hr_ctx *c, const hr_exposure_params *params, const hr_di
     if (rc) return rc;
     FrameDev fr = c->frame; // (exposureRun has refused world > 1: every pixel is this context's; a group's frame is rank 0 of 1)
     fr.fb = const_cast<float *>(image);
-    launchExposureDisplay(c->stream, fr, *display, format, c->ex.dev, device_out);
+    launchExposureDisplay(c->stream, fr, *display, format, c->exposure.bins.dev, device_out);
     HIP_TRY(c, hipGetLastError());
     if (passes_shown) *passes_shown = n;
     return HR_OK;
@@ -153,14 +153,14 @@ int hr_exposure_last(hr_ctx *c, hr_exposure_result *out, uint64_t *bins)
 {
     ENTER(c);
     if (!out) FAIL(c, HR_ERR_INVALID, "null output");
-    if (!c->exMetered) FAIL(c, HR_ERR_INVALID, "exposure: nothing has been metered yet (hr_exposure_meter, hr_exposure_display)");
+    if (!c->exposure.metered) FAIL(c, HR_ERR_INVALID, "exposure: nothing has been metered yet (hr_exposure_meter, hr_exposure_display)");
     return exposureFetch(c, out, bins);
 }
 
 int hr_exposure_reset(hr_ctx *c)
 {
     ENTER(c);
-    if (c->exState) HIP_TRY(c, hipMemsetAsync(c->exState, 0, 2 * sizeof(uint32_t), c->stream));
+    if (c->exposure.state) HIP_TRY(c, hipMemsetAsync(c->exposure.state, 0, 2 * sizeof(uint32_t), c->stream));
     return HR_OK;
 }
 

@@ -181,13 +181,11 @@ static int groupDestroy(hr_ctx *c)
     if (g->evGathered) hipEventDestroy(g->evGathered);
     freeLagged(c->progFrame), freeLagged(c->progDisplay);
     hipFree(c->fbInternal);
-    if (c->pinned) hipHostFree(c->pinned);
+    c->pinned.release();
     hipFree(c->dDisplay);
-    if (c->pinnedDisplay) hipHostFree(c->pinnedDisplay);
-    aovFree(c);
-    adaptiveFree(c);
-    exposureFree(c);
-    metricFree(c);
+    c->pinnedDisplay.release();
+    if (c->evCopyOut) hipEventDestroy(c->evCopyOut);
+    featuresDestroyed(c);
     delete g;
     delete c;
     return HR_OK;
@@ -227,16 +225,11 @@ static int groupResize(hr_ctx *c, int32_t w, int32_t h)
     freeLagged(c->progFrame), freeLagged(c->progDisplay);
     hipFree(c->fbInternal);
     c->fbInternal = nullptr;
-    adaptiveFree(c); // (the group's copy of the sample mask; the members' went with their frames)
+    featuresFrameResized(c); // (the group's copy of the sample mask; the members' went with their frames)
     const size_t fbBytes = (size_t)w * h * 4 * sizeof(float);
     HIP_TRY(c, hipMalloc(&c->fbInternal, fbBytes));
     HIP_TRY(c, hipMemsetAsync(c->fbInternal, 0, fbBytes, c->stream));
-    if (c->pinnedBytes < fbBytes) {
-        if (c->pinned) hipHostFree(c->pinned);
-        c->pinned = nullptr, c->pinnedBytes = 0;
-        HIP_TRY(c, hipHostMalloc((void **)&c->pinned, fbBytes, hipHostMallocDefault));
-        c->pinnedBytes = fbBytes;
-    }
+    if ((rc = c->pinned.grow(c, fbBytes))) return rc;
     FrameDev &f = c->frame; // the assembled frame: rank 0 of world 1
     f.W = w, f.H = h, f.rank = 0, f.world = 1, f.tile = c->tile;
     f.tilesX = (w + c->tile - 1) / c->tile, f.tilesY = (h + c->tile - 1) / c->tile;
@@ -299,9 +292,9 @@ static int groupReadback(hr_ctx *c, const float **rgba, int32_t *w, int32_t *h)
     if (c->W <= 0 || !rgba) FAIL(c, HR_ERR_INVALID, "no frame");
     int rc = groupAssemble(c, true, nullptr, nullptr);
     if (rc) return rc;
-    HIP_TRY(c, hipMemcpyAsync(c->pinned, c->fbInternal, (size_t)c->W * c->H * 4 * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipMemcpyAsync(c->pinned.ptr, c->fbInternal, (size_t)c->W * c->H * 4 * sizeof(float), hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(c, hipStreamSynchronize(c->stream));
-    *rgba = c->pinned;
+    *rgba = c->pinned.ptr;
     if (w) *w = c->W;
     if (h) *h = c->H;
     return HR_OK;
@@ -371,19 +364,12 @@ static int groupDisplayReadback(hr_ctx *c, const hr_display_params *params, int3
         for (size_t i = 0; i < sizeof(*params) / 4; ++i) key = key * 31 + ((const int32_t *)params)[i];
         rc = finishLaggedAt(c, c->progDisplay, k, key, pixels, shown, passes, idle);
     } else {
-        if (c->displayBytes < need) {
-            hipFree(c->dDisplay);
-            if (c->pinnedDisplay) hipHostFree(c->pinnedDisplay);
-            c->dDisplay = nullptr, c->pinnedDisplay = nullptr, c->displayBytes = 0;
-            HIP_TRY(c, hipMalloc(&c->dDisplay, need));
-            HIP_TRY(c, hipHostMalloc(&c->pinnedDisplay, need, hipHostMallocDefault));
-            c->displayBytes = need;
-        }
+        if ((rc = growDisplay(c, need))) return rc;
         rc = groupDisplayTo(c, params, format, c->dDisplay, &passes, nullptr);
         if (rc) return rc;
-        HIP_TRY(c, hipMemcpyAsync(c->pinnedDisplay, c->dDisplay, bytes, hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(c, hipMemcpyAsync(c->pinnedDisplay.ptr, c->dDisplay, bytes, hipMemcpyDeviceToHost, c->stream));
         HIP_TRY(c, hipStreamSynchronize(c->stream));
-        *pixels = c->pinnedDisplay;
+        *pixels = c->pinnedDisplay.ptr;
         if (shown) *shown = passes;
     }
     if (rc) return rc;
@@ -433,7 +419,7 @@ static int groupClear(hr_ctx *c)
     const int rc = groupAll(c, [](hr_ctx *m, int) { return hr_clear(m); });
     if (rc) return rc;
     HIP_TRY(c, hipMemsetAsync(c->fbInternal, 0, (size_t)c->W * c->H * 4 * sizeof(float), c->stream));
-    c->frame.mask = nullptr; // (hr_clear has removed the members' sample masks)
+    featuresFrameCleared(c); // (hr_clear has removed the members' sample masks: the group's copy goes too)
     c->snapshotEpoch++;
     return HR_OK;
 }

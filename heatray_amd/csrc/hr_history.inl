@@ -58,13 +58,13 @@ int hr_history_capture(hr_ctx *c, const hr_pass_params *camera)
     uint32_t n = 0;
     rc = historyCheckFrame(c, "history capture", &n);
     if (rc) return rc;
-    if (!c->hsHist) HIP_TRY(c, hipMalloc((void **)&c->hsHist, (size_t)c->W * c->H * kHistoryBytesPerPixel));
-    c->hsCaptured = false;
-    launchHistoryCapture(c->stream, c->W, c->H, c->fb(), c->aovPlane[HR_AOV_PLANE_ALBEDO], c->aovPlane[HR_AOV_PLANE_NORMAL_DEPTH], c->aovPlane[HR_AOV_PLANE_MOMENTS], c->hsHist);
+    if (!c->history.hist) HIP_TRY(c, hipMalloc((void **)&c->history.hist, (size_t)c->W * c->H * kHistoryBytesPerPixel));
+    c->history.captured = false;
+    launchHistoryCapture(c->stream, c->W, c->H, c->fb(), c->aov.plane[HR_AOV_PLANE_ALBEDO], c->aov.plane[HR_AOV_PLANE_NORMAL_DEPTH], c->aov.plane[HR_AOV_PLANE_MOMENTS], c->history.hist);
     HIP_TRY(c, hipGetLastError());
-    std::memcpy(c->hsView, camera->view_matrix, sizeof(c->hsView));
-    c->hsFovTan = camera->fov_tan, c->hsAspect = camera->aspect_ratio;
-    c->hsPasses = n, c->hsCaptured = true;
+    std::memcpy(c->history.view, camera->view_matrix, sizeof(c->history.view));
+    c->history.fovTan = camera->fov_tan, c->history.aspect = camera->aspect_ratio;
+    c->history.passes = n, c->history.captured = true;
     return HR_OK;
 }
 
@@ -78,23 +78,23 @@ int hr_history_merge(hr_ctx *c, const hr_pass_params *camera, const hr_history_p
     uint32_t n = 0;
     rc = historyCheckFrame(c, "history merge", &n);
     if (rc) return rc;
-    if (!c->hsCaptured) FAIL(c, HR_ERR_INVALID, "history merge: no captured history (hr_history_capture; hr_frame_resize and hr_history_drop remove it)");
-    if (c->hsMerged) FAIL(c, HR_ERR_INVALID, "history merge: the history has already been merged into this frame (one merge per hr_clear: a second would count it twice)");
-    HIP_TRY(c, c->hs.ensure(kHistoryResultWords));
-    HIP_TRY(c, c->hs.zero(c->stream));
-    const HsCam cam = hsCameras(c->hsView, c->hsAspect, c->hsFovTan, camera->view_matrix, camera->aspect_ratio, camera->fov_tan);
+    if (!c->history.captured) FAIL(c, HR_ERR_INVALID, "history merge: no captured history (hr_history_capture; hr_frame_resize and hr_history_drop remove it)");
+    if (c->history.merged) FAIL(c, HR_ERR_INVALID, "history merge: the history has already been merged into this frame (one merge per hr_clear: a second would count it twice)");
+    HIP_TRY(c, c->history.result.ensure(kHistoryResultWords));
+    HIP_TRY(c, c->history.result.zero(c->stream));
+    const HsCam cam = hsCameras(c->history.view, c->history.aspect, c->history.fovTan, camera->view_matrix, camera->aspect_ratio, camera->fov_tan);
     const HsParams P{(float)p.max_history, p.normal_cos, p.plane_tol, p.min_weight};
-    launchHistoryMerge(c->stream, c->W, c->H, cam, P, c->hsHist, c->fb(), c->aovPlane[HR_AOV_PLANE_ALBEDO], c->aovPlane[HR_AOV_PLANE_NORMAL_DEPTH],
-                       c->aovPlane[HR_AOV_PLANE_MOMENTS], c->hs.dev);
+    launchHistoryMerge(c->stream, c->W, c->H, cam, P, c->history.hist, c->fb(), c->aov.plane[HR_AOV_PLANE_ALBEDO], c->aov.plane[HR_AOV_PLANE_NORMAL_DEPTH],
+                       c->aov.plane[HR_AOV_PLANE_MOMENTS], c->history.result.dev);
     HIP_TRY(c, hipGetLastError());
-    c->hsMerged = true;
+    c->history.merged = true;
     c->snapshotEpoch++; // (progressive snapshots taken before the merge are not handed out any more)
-    HIP_TRY(c, c->hs.fetch(c->stream));
+    HIP_TRY(c, c->history.result.fetch(c->stream));
     HIP_TRY(c, hipStreamSynchronize(c->stream));
     if (out) {
         *out = hr_history_result{};
-        out->reused_pixels = c->hs.host[0], out->rejected_pixels = c->hs.host[1], out->history_samples = c->hs.host[2];
-        out->history_passes = c->hsPasses, out->passes = n;
+        out->reused_pixels = c->history.result.host[0], out->rejected_pixels = c->history.result.host[1], out->history_samples = c->history.result.host[2];
+        out->history_passes = c->history.passes, out->passes = n;
     }
     return HR_OK;
 }
@@ -103,20 +103,20 @@ int hr_history_drop(hr_ctx *c)
 {
     ENTER(c);
     if (c->grp) return HR_OK; // (a group never holds one)
-    const int rc = c->hsHist ? quiesce(c) : HR_OK;
+    const int rc = c->history.hist ? quiesce(c) : HR_OK;
     if (rc) return rc;
-    const bool merged = c->hsMerged; // (the frame has still been merged into: dropping the history does not allow a second merge of a new one)
-    historyFree(c);
-    c->hsMerged = merged;
+    const bool merged = c->history.merged; // (the frame has still been merged into: dropping the history does not allow a second merge of a new one)
+    c->history.release();
+    c->history.merged = merged;
     return HR_OK;
 }
 
 int hr_history_info(hr_ctx *c, int32_t *captured, uint32_t *passes)
 {
     ENTER(c);
-    const bool have = !c->grp && c->hsCaptured;
+    const bool have = !c->grp && c->history.captured;
     if (captured) *captured = have ? 1 : 0;
-    if (passes) *passes = have ? c->hsPasses : 0u;
+    if (passes) *passes = have ? c->history.passes : 0u;
     return HR_OK;
 }
 
@@ -124,8 +124,8 @@ int hr_history_readback(hr_ctx *c, float *host_out)
 {
     ENTER(c);
     if (!host_out) FAIL(c, HR_ERR_INVALID, "null output");
-    if (c->grp || !c->hsCaptured) FAIL(c, HR_ERR_INVALID, "history: no captured history");
-    HIP_TRY(c, hipMemcpyAsync(host_out, c->hsHist, (size_t)c->W * c->H * kHistoryBytesPerPixel, hipMemcpyDeviceToHost, c->stream));
+    if (c->grp || !c->history.captured) FAIL(c, HR_ERR_INVALID, "history: no captured history");
+    HIP_TRY(c, hipMemcpyAsync(host_out, c->history.hist, (size_t)c->W * c->H * kHistoryBytesPerPixel, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(c, hipStreamSynchronize(c->stream));
     return HR_OK;
 }

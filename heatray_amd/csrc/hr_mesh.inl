@@ -98,14 +98,14 @@ static int meshPrepareOn(hr_ctx *c, const hr_mesh_desc *d, const hr_mesh_params 
     const size_t oPerm = reserve(V * 4), oGroupOf = reserve(V * 4), oStart = reserve((V + 1) * 4), oScan = reserve(V * 4), oNG = reserve(4);
     const size_t oGN = reserve(V * 12), oGC = reserve(V);
     const size_t oOutN = reserve(normals ? V * 12 : 0), oOutT = reserve(tangents ? V * 12 : 0), oOutB = reserve(tangents ? V * 12 : 0);
-    if (c->msScratchBytes < total) {
+    if (c->meshPrep.scratchBytes < total) {
         HIP_TRY(c, hipStreamSynchronize(c->stream)); // (an earlier call's kernels have been waited for; the ring's copies too)
-        hipFree(c->msScratch);
-        c->msScratch = nullptr, c->msScratchBytes = 0;
-        HIP_TRY(c, hipMalloc((void **)&c->msScratch, total));
-        c->msScratchBytes = total;
+        hipFree(c->meshPrep.scratch);
+        c->meshPrep.scratch = nullptr, c->meshPrep.scratchBytes = 0;
+        HIP_TRY(c, hipMalloc((void **)&c->meshPrep.scratch, total));
+        c->meshPrep.scratchBytes = total;
     }
-    char *base = c->msScratch;
+    char *base = c->meshPrep.scratch;
     const auto F32 = [&](size_t o) { return (float *)(base + o); };
     const auto U32 = [&](size_t o) { return (uint32_t *)(base + o); };
     b.pos = F32(oPos), b.uv = tangents ? F32(oUv) : nullptr, b.nrmIn = tangents && !normals ? F32(oNrm) : nullptr, b.idx = U32(oIdx);
@@ -122,19 +122,19 @@ static int meshPrepareOn(hr_ctx *c, const hr_mesh_desc *d, const hr_mesh_params 
     if (rc == HR_OK && nIdx) rc = stagedUpload(c, base + oIdx, (const char *)d->indices, nIdx * 4);
     if (rc) return rc;
     // ---- the kernels, the copies back, one wait
-    HIP_TRY(c, c->ms.ensure(kMsCounterWords));
-    HIP_TRY(c, c->ms.zero(c->stream));
-    b.counters = c->ms.dev;
+    HIP_TRY(c, c->meshPrep.counters.ensure(kMsCounterWords));
+    HIP_TRY(c, c->meshPrep.counters.zero(c->stream));
+    b.counters = c->meshPrep.counters.dev;
     launchMeshPrepare(c->stream, b);
     HIP_TRY(c, hipGetLastError());
-    HIP_TRY(c, c->ms.fetch(c->stream));
+    HIP_TRY(c, c->meshPrep.counters.fetch(c->stream));
     if (normals) HIP_TRY(c, hipMemcpyAsync(nOut, b.outN, V * 12, hipMemcpyDeviceToHost, c->stream));
     if (tangents) {
         HIP_TRY(c, hipMemcpyAsync(tOut, b.outT, V * 12, hipMemcpyDeviceToHost, c->stream));
         HIP_TRY(c, hipMemcpyAsync(bOut, b.outB, V * 12, hipMemcpyDeviceToHost, c->stream));
     }
     HIP_TRY(c, hipStreamSynchronize(c->stream));
-    const unsigned long long *h = c->ms.host;
+    const unsigned long long *h = c->meshPrep.counters.host;
     *res = hr_mesh_result{};
     res->triangles = nTris, res->degenerate_triangles = h[kMsDegenerate], res->degenerate_uv_triangles = h[kMsDegenerateUv];
     res->weld_groups = normals ? h[kMsGroups] : 0, res->unreferenced_vertices = h[kMsUnreferenced], res->cancelled_vertices = h[kMsCancelled];
@@ -166,7 +166,7 @@ int hr_mesh_prepare(hr_ctx *c, const hr_mesh_desc *desc, const hr_mesh_params *p
     else
         rc = meshPrepareOn(c, desc, p, nTris, normals_out, tangents_out, bitangents_out, &r);
     if (rc) return rc;
-    c->msLast = r, c->msPrepared = true;
+    c->meshPrep.last = r, c->meshPrep.prepared = true;
     if (out) *out = r;
     return HR_OK;
 }
@@ -175,8 +175,8 @@ int hr_mesh_last(hr_ctx *c, hr_mesh_result *out)
 {
     ENTER(c);
     if (!out) FAIL(c, HR_ERR_INVALID, "mesh_last: null output");
-    if (!c->msPrepared) FAIL(c, HR_ERR_INVALID, "mesh_last: no mesh has been prepared on this context");
-    *out = c->msLast;
+    if (!c->meshPrep.prepared) FAIL(c, HR_ERR_INVALID, "mesh_last: no mesh has been prepared on this context");
+    *out = c->meshPrep.last;
     return HR_OK;
 }
 

@@ -34,14 +34,14 @@ static int metricWindow(hr_ctx *c, const hr_metric_params &p, MtWindow *win)
 // the one place that reads the host words: the last fetched measurement -> the result (and the bins), through hr_metric.h's fold (mtFinish)
 static void metricFill(const hr_ctx *c, hr_metric_result *out, uint64_t *numBins, uint64_t *denBins)
 {
-    const unsigned long long *h = c->mt.host;
+    const unsigned long long *h = c->metric.bins.host;
     *out = hr_metric_result{};
-    const MtFolded f = mtFinish(h, c->mtKind);
+    const MtFolded f = mtFinish(h, c->metric.kind);
     out->num = f.num, out->den = f.den, out->value = f.value, out->mse = f.mse, out->flags = f.flags;
     out->counted = h[kMtWordCounted], out->differing = h[kMtWordDiffering], out->nonfinite = h[kMtWordNonfinite], out->skipped = h[kMtWordSkipped];
     const uint32_t maxBits = (uint32_t)h[kMtWordMaxAbs];
     std::memcpy(&out->max_abs, &maxBits, 4);
-    out->passes = c->mtPasses, out->kind = c->mtKind;
+    out->passes = c->metric.passes, out->kind = c->metric.kind;
     for (int k = 0; k < kMtBins; ++k) {
         if (numBins) numBins[k] = h[kMtWordNum + k];
         if (denBins) denBins[k] = h[kMtWordDen + k];
@@ -51,7 +51,7 @@ static void metricFill(const hr_ctx *c, hr_metric_result *out, uint64_t *numBins
 // the last measurement, fetched and waited for, -> out
 static int metricFetch(hr_ctx *c, hr_metric_result *out, uint64_t *numBins, uint64_t *denBins)
 {
-    HIP_TRY(c, c->mt.fetch(c->stream));
+    HIP_TRY(c, c->metric.bins.fetch(c->stream));
     HIP_TRY(c, hipStreamSynchronize(c->stream));
     metricFill(c, out, numBins, denBins);
     return HR_OK;
@@ -72,7 +72,7 @@ static int metricRun(hr_ctx *c, uint32_t kind, const hr_metric_params *params, c
         const FrameNeed need{HR_AOV_MOMENTS, "metric", "the sum", true, true, "metric: the estimate needs the sample moments: hr_aov_enable(HR_AOV_MOMENTS)",
                              "metric: the MOMENTS plane was enabled after the frame's first pass and does not hold"};
         rc = frameReady(c, need, &image, &passes);
-        other = c->aovPlane[HR_AOV_PLANE_MOMENTS];
+        other = c->aov.plane[HR_AOV_PLANE_MOMENTS];
     } else {
         const FrameNeed need{0, "metric", "the sum", true, false, "", ""};
         if (device_image) {
@@ -86,11 +86,11 @@ static int metricRun(hr_ctx *c, uint32_t kind, const hr_metric_params *params, c
     MtWindow win;
     rc = metricWindow(c, p, &win);
     if (rc) return rc;
-    HIP_TRY(c, c->mt.ensure(kMtWords));
-    HIP_TRY(c, c->mt.zero(c->stream));
-    launchMetricAccumulate(c->stream, c->numCUs, c->W, c->H, (int)kind, image, other, win, c->mt.dev);
+    HIP_TRY(c, c->metric.bins.ensure(kMtWords));
+    HIP_TRY(c, c->metric.bins.zero(c->stream));
+    launchMetricAccumulate(c->stream, c->numCUs, c->W, c->H, (int)kind, image, other, win, c->metric.bins.dev);
     HIP_TRY(c, hipGetLastError());
-    c->mtMeasured = true, c->mtKind = kind, c->mtPasses = passes;
+    c->metric.measured = true, c->metric.kind = kind, c->metric.passes = passes;
     return metricFetch(c, out, nullptr, nullptr);
 }
 
@@ -120,7 +120,7 @@ int hr_metric_last(hr_ctx *c, hr_metric_result *out, uint64_t *num_bins, uint64_
 {
     ENTER(c);
     if (!out) FAIL(c, HR_ERR_INVALID, "null output");
-    if (!c->mtMeasured) FAIL(c, HR_ERR_INVALID, "metric: nothing has been measured yet (hr_metric_compare, hr_metric_estimate)");
+    if (!c->metric.measured) FAIL(c, HR_ERR_INVALID, "metric: nothing has been measured yet (hr_metric_compare, hr_metric_estimate)");
     return metricFetch(c, out, num_bins, den_bins);
 }
 

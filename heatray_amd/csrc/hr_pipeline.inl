@@ -13,12 +13,10 @@ int hr_clear(hr_ctx *c)
     }
     HIP_TRY(c, hipMemsetAsync(c->fb(), 0, (size_t)c->W * c->H * 4 * sizeof(float), c->stream));
     HIP_TRY(c, hipMemsetAsync(c->dStats, 0, sizeof(Stats) * kStatSlots, c->stream));
-    for (float *plane : c->aovPlane)
+    for (float *plane : c->aov.plane)
         if (plane) HIP_TRY(c, hipMemsetAsync(plane, 0, (size_t)c->W * c->H * 4 * sizeof(float), c->stream));
-    c->resolvedAtClear = c->aovZeroedAt = c->frameZeroedAt = c->nextResolveOrder;
-    c->frame.mask = nullptr; // (include/hrcore_adaptive.h: a new frame starts without a sample mask)
-    c->hsMerged = false;     // (include/hrcore_history.h: ... and may take over a captured history once)
-    c->rpMerged = false, c->rpStale = true; // (include/hrcore_reproject.h: ... or progressively: no pixel of the new frame has been examined)
+    c->resolvedAtClear = c->aov.zeroedAt = c->frameZeroedAt = c->nextResolveOrder;
+    featuresFrameCleared(c);
     c->snapshotEpoch++;
     if (c->tune.debugPipe) fprintf(stderr, "hr_clear %p: ray-memory growths so far %llu, waits %llu (%.2f ms)\n", (void *)c, c->dbgGrowths, c->dbgWaits, (double)c->dbgWaitNs * 1e-6);
     c->drainTimes();
@@ -32,7 +30,7 @@ static int allocSlot(hr_ctx *c, hr_ctx::PassSlot &ps, hipStream_t st)
     const size_t sums = c->allLightsUsed ? 4 : 1;
     // (with HR_ESTIMATOR_ALL_LIGHTS the sample's further partial sums lie right behind the first: k_trace indexes one buffer; the AOV record
     // of HR_AOV_SURFACE behind them)
-    const hipError_t e = hipMalloc(&ps.passbuf, fbBytes * (sums + c->aovFramesPerSlot()));
+    const hipError_t e = hipMalloc(&ps.passbuf, fbBytes * (sums + c->aov.framesPerSlot()));
     if (e != hipSuccess) { // say what ran out: a pass slot is the unit the pipeline's memory grows in
         size_t freeB = 0, totalB = 0;
         hipMemGetInfo(&freeB, &totalB);
@@ -41,9 +39,9 @@ static int allocSlot(hr_ctx *c, hr_ctx::PassSlot &ps, hipStream_t st)
         return HR_ERR_DEVICE;
     }
     if (c->allLightsUsed) ps.passbufB = ps.passbuf + (size_t)c->W * c->H * 4;
-    if (c->aovFramesPerSlot()) { // zeroed once here (complete before any stream uses the slot); from then on the resolve that reads a pass's record zeroes it
+    if (c->aov.framesPerSlot()) { // zeroed once here (complete before any stream uses the slot); from then on the resolve that reads a pass's record zeroes it
         ps.aov = ps.passbuf + sums * (size_t)c->W * c->H * 4;
-        HIP_TRY(c, hipMemsetAsync(ps.aov, 0, fbBytes * c->aovFramesPerSlot(), st));
+        HIP_TRY(c, hipMemsetAsync(ps.aov, 0, fbBytes * c->aov.framesPerSlot(), st));
         HIP_TRY(c, hipStreamSynchronize(st));
     }
     ps.ctr = c->dCounters + (&ps - c->slots);
@@ -159,9 +157,9 @@ static int resolveReady(hr_ctx *c)
             if (!seen) HIP_TRY(c, hipStreamWaitEvent(c->stream, ready[k]->finalEv, 0));
         }
         c->timeBegin(HR_KERNEL_RESOLVE, c->stream);
-        if (c->aovMask) {
+        if (c->aov.mask) {
             AovList aov{};
-            aov.albedo = c->aovPlane[HR_AOV_PLANE_ALBEDO], aov.normalDepth = c->aovPlane[HR_AOV_PLANE_NORMAL_DEPTH], aov.moments = c->aovPlane[HR_AOV_PLANE_MOMENTS];
+            aov.albedo = c->aov.plane[HR_AOV_PLANE_ALBEDO], aov.normalDepth = c->aov.plane[HR_AOV_PLANE_NORMAL_DEPTH], aov.moments = c->aov.plane[HR_AOV_PLANE_MOMENTS];
             for (int k = 0; k < bufs.n; ++k) aov.pass[k] = ready[k]->aov;
             launchResolveAov(cfg, fr, bufs, aov);
         } else {
@@ -667,7 +665,7 @@ static bool packetsInUse(const hr_ctx *c) { return c->tune.packets == 1 || (c->t
 static double budgetBytesPerPass(const hr_ctx *c, int stages)
 {
     const double P = (double)(c->queueCapacity ? c->queueCapacity : 1u), kS = c->allLightsUsed ? 4.0 : 1.0;
-    const double fb = (double)c->W * c->H * 16.0 * ((c->allLightsUsed ? 4.0 : 1.0) + (double)c->aovFramesPerSlot());
+    const double fb = (double)c->W * c->H * 16.0 * ((c->allLightsUsed ? 4.0 : 1.0) + (double)c->aov.framesPerSlot());
     double arena = 0.0, scratch = 0.0;
     for (int st = 0; st + 1 < stages && st < kMaxBounceSlots; ++st) { // (the last stage traces occlusion rays only)
         arena += c->stageSeen[st] ? 1.1 * c->stageArenaSeen[st] : P * (64.0 + 48.0 * kS);

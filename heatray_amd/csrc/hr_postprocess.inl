@@ -1,6 +1,6 @@
 // hr_postprocess.inl — a section of hr_core.hip (included before the feature sections): the host plumbing that the AOV planes, the
-// denoiser, adaptive sampling, history reprojection, the progressive merge, auto-exposure, the convergence metric and firefly suppression share ("Adding a post-process feature"); the
-// result counters' type, ResultCounters, is in hr_ctx.h beside the context's fields of it.
+// denoiser, adaptive sampling, history reprojection, the progressive merge, auto-exposure, the convergence metric and firefly suppression share ("Adding a post-process feature"), and
+// the one table of when each feature's state goes; the state itself, with ResultCounters and PinnedBuf, is in hr_features.h.
 
 // `bytes` of device memory that is complete on the ctx stream -> dst, on `stream` (null: the ctx stream).  On a foreign stream the copy
 // waits for everything enqueued on the ctx stream so far, and the ctx's next work goes behind the copy: the next resolve, filter or update
@@ -12,24 +12,49 @@ static int copyOutOnStream(hr_ctx *c, void *dst, const void *src, size_t bytes, 
         HIP_TRY(c, hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToDevice, st));
         return HR_OK;
     }
-    if (!c->evAov) HIP_TRY(c, hipEventCreateWithFlags(&c->evAov, hipEventDisableTiming));
-    HIP_TRY(c, hipEventRecord(c->evAov, c->stream));
-    HIP_TRY(c, hipStreamWaitEvent(st, c->evAov, 0));
+    if (!c->evCopyOut) HIP_TRY(c, hipEventCreateWithFlags(&c->evCopyOut, hipEventDisableTiming));
+    HIP_TRY(c, hipEventRecord(c->evCopyOut, c->stream));
+    HIP_TRY(c, hipStreamWaitEvent(st, c->evCopyOut, 0));
     HIP_TRY(c, hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToDevice, st));
-    HIP_TRY(c, hipEventRecord(c->evAov, st));
-    HIP_TRY(c, hipStreamWaitEvent(c->stream, c->evAov, 0));
+    HIP_TRY(c, hipEventRecord(c->evCopyOut, st));
+    HIP_TRY(c, hipStreamWaitEvent(c->stream, c->evCopyOut, 0));
     return HR_OK;
 }
 
-// a read-back's pinned host buffer, at least `bytes` long; it only grows
-static int growPinned(hr_ctx *c, float *&pinned, size_t &have, size_t bytes)
+// ---- when the features' state goes.  These four are the only callers of a feature's release() (hr_history_drop apart) and the only
+// code that resets a feature's flags; a plain context, a group's handle and its members all come through them.  Every caller has
+// drained or synchronised what could still use the memory.
+// The AOV planes are going (aovAllocPlanes: hr_frame_resize, hr_aov_enable): so does what was computed from them at their size.
+static void featuresPlanesGone(hr_ctx *c)
 {
-    if (have >= bytes) return HR_OK;
-    if (pinned) hipHostFree(pinned);
-    pinned = nullptr, have = 0;
-    HIP_TRY(c, hipHostMalloc((void **)&pinned, bytes, hipHostMallocDefault));
-    have = bytes;
-    return HR_OK;
+    c->denoise.release();   // (the denoiser's buffers live and die with the planes it reads)
+    c->despeckle.release(); // (... and so do the despeckled frame and moments the denoiser can be run from)
+    c->aov.pinned.release();
+}
+// The frame has another size (hr_frame_resize, groupResize): what was made for the old one goes, an installed sample mask included.
+static void featuresFrameResized(hr_ctx *c)
+{
+    c->adaptive.release();
+    c->frame.mask = nullptr;
+    c->history.release();
+    c->reproject.release();
+}
+// The frame starts afresh (hr_clear, groupClear).
+static void featuresFrameCleared(hr_ctx *c)
+{
+    c->frame.mask = nullptr;       // (include/hrcore_adaptive.h: a new frame starts without a sample mask)
+    c->history.merged = false;     // (include/hrcore_history.h: ... and may take over a captured history once)
+    c->reproject.merged = false, c->reproject.stale = true; // (include/hrcore_reproject.h: ... or progressively: no pixel of the new frame has been examined)
+}
+// The context goes (hr_ctx_destroy, groupDestroy).
+static void featuresDestroyed(hr_ctx *c)
+{
+    featuresPlanesGone(c);
+    featuresFrameResized(c);
+    c->aov.release();
+    c->exposure.release();
+    c->metric.release();
+    c->meshPrep.release();
 }
 
 // ---- "a full-frame post-process wants this frame"
@@ -51,9 +76,9 @@ static int groupAovAssemble(hr_ctx *c, int32_t plane, uint64_t *passes); // hr_a
 static int framePlanesReady(hr_ctx *c, const FrameNeed &need)
 {
     if (need.aov == 0) return HR_OK; // (it reads no plane: whether and when they were enabled is not its business)
-    if ((c->aovMask & need.aov) != need.aov)
-        FAIL(c, HR_ERR_INVALID, need.needs + " before the frame's first pass (enabled mask: " + std::to_string(c->aovMask) + ")");
-    if (c->aovZeroedAt != c->frameZeroedAt) FAIL(c, HR_ERR_INVALID, need.late + " the frame's passes: hr_clear, or hr_aov_enable before rendering");
+    if ((c->aov.mask & need.aov) != need.aov)
+        FAIL(c, HR_ERR_INVALID, need.needs + " before the frame's first pass (enabled mask: " + std::to_string(c->aov.mask) + ")");
+    if (c->aov.zeroedAt != c->frameZeroedAt) FAIL(c, HR_ERR_INVALID, need.late + " the frame's passes: hr_clear, or hr_aov_enable before rendering");
     return HR_OK;
 }
 

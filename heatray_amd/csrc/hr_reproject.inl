@@ -13,8 +13,8 @@ static int reprojectPrepare(hr_ctx *c, const char *what, const hr_pass_params *c
     if (rc) return rc;
     rc = historyCheckFrame(c, what, passes);
     if (rc) return rc;
-    if (!c->hsCaptured) FAIL(c, HR_ERR_INVALID, std::string(what) + ": no captured history (hr_history_capture; hr_frame_resize and hr_history_drop remove it)");
-    HIP_TRY(c, c->rp.ensure(kReprojectResultWords));
+    if (!c->history.captured) FAIL(c, HR_ERR_INVALID, std::string(what) + ": no captured history (hr_history_capture; hr_frame_resize and hr_history_drop remove it)");
+    HIP_TRY(c, c->reproject.result.ensure(kReprojectResultWords));
     return HR_OK;
 }
 
@@ -23,10 +23,10 @@ static void previewFill(const hr_ctx *c, hr_reproject_preview_result *out)
 {
     if (!out) return;
     *out = hr_reproject_preview_result{};
-    out->own_pixels = c->rp.host[0], out->previewed_pixels = c->rp.host[1], out->empty_pixels = c->rp.host[2];
+    out->own_pixels = c->reproject.result.host[0], out->previewed_pixels = c->reproject.result.host[1], out->empty_pixels = c->reproject.result.host[2];
 }
 
-// Checks, and enqueues the preview on the ctx stream; the image goes to `dst`, or to c->rpOut when dst is null.  With `out` it waits.
+// Checks, and enqueues the preview on the ctx stream; the image goes to `dst`, or to c->reproject.out when dst is null.  With `out` it waits.
 static int previewRun(hr_ctx *c, const hr_pass_params *camera, const hr_history_params *params, float *dst, hr_reproject_preview_result *out)
 {
     hr_history_params p;
@@ -34,16 +34,16 @@ static int previewRun(hr_ctx *c, const hr_pass_params *camera, const hr_history_
     int rc = reprojectPrepare(c, "reproject preview", camera, params, &p, &n);
     if (rc) return rc;
     if (!dst) {
-        if (!c->rpOut) HIP_TRY(c, hipMalloc((void **)&c->rpOut, (size_t)c->W * c->H * 16));
-        dst = c->rpOut;
+        if (!c->reproject.out) HIP_TRY(c, hipMalloc((void **)&c->reproject.out, (size_t)c->W * c->H * 16));
+        dst = c->reproject.out;
     }
-    const HsCam cam = hsCameras(c->hsView, c->hsAspect, c->hsFovTan, camera->view_matrix, camera->aspect_ratio, camera->fov_tan);
+    const HsCam cam = hsCameras(c->history.view, c->history.aspect, c->history.fovTan, camera->view_matrix, camera->aspect_ratio, camera->fov_tan);
     const HsParams P{(float)p.max_history, p.normal_cos, p.plane_tol, p.min_weight};
-    HIP_TRY(c, c->rp.zero(c->stream));
-    launchReprojectPreview(c->stream, c->W, c->H, cam, P, c->hsHist, c->fb(), c->aovPlane[HR_AOV_PLANE_ALBEDO], c->aovPlane[HR_AOV_PLANE_NORMAL_DEPTH], dst, c->rp.dev);
+    HIP_TRY(c, c->reproject.result.zero(c->stream));
+    launchReprojectPreview(c->stream, c->W, c->H, cam, P, c->history.hist, c->fb(), c->aov.plane[HR_AOV_PLANE_ALBEDO], c->aov.plane[HR_AOV_PLANE_NORMAL_DEPTH], dst, c->reproject.result.dev);
     HIP_TRY(c, hipGetLastError());
     if (out) {
-        HIP_TRY(c, c->rp.fetch(c->stream));
+        HIP_TRY(c, c->reproject.result.fetch(c->stream));
         HIP_TRY(c, hipStreamSynchronize(c->stream));
         previewFill(c, out);
     }
@@ -61,30 +61,30 @@ int hr_reproject_merge(hr_ctx *c, const hr_pass_params *camera, const hr_history
     uint32_t n = 0;
     int rc = reprojectPrepare(c, "reproject merge", camera, params, &p, &n);
     if (rc) return rc;
-    if (c->hsMerged && !c->rpMerged)
+    if (c->history.merged && !c->reproject.merged)
         FAIL(c, HR_ERR_INVALID, "reproject merge: hr_history_merge has already merged the history into this frame (a progressive merge would count it twice): hr_clear first");
     const size_t words = rpExaminedWords(c->W, c->H);
-    if (!c->rpExamined) {
-        HIP_TRY(c, hipMalloc((void **)&c->rpExamined, words * 8));
-        c->rpStale = true;
+    if (!c->reproject.examined) {
+        HIP_TRY(c, hipMalloc((void **)&c->reproject.examined, words * 8));
+        c->reproject.stale = true;
     }
-    if (c->rpStale) HIP_TRY(c, hipMemsetAsync(c->rpExamined, 0, words * 8, c->stream));
-    c->rpStale = false;
-    const HsCam cam = hsCameras(c->hsView, c->hsAspect, c->hsFovTan, camera->view_matrix, camera->aspect_ratio, camera->fov_tan);
+    if (c->reproject.stale) HIP_TRY(c, hipMemsetAsync(c->reproject.examined, 0, words * 8, c->stream));
+    c->reproject.stale = false;
+    const HsCam cam = hsCameras(c->history.view, c->history.aspect, c->history.fovTan, camera->view_matrix, camera->aspect_ratio, camera->fov_tan);
     const HsParams P{(float)p.max_history, p.normal_cos, p.plane_tol, p.min_weight};
-    HIP_TRY(c, c->rp.zero(c->stream));
-    launchReprojectMerge(c->stream, c->W, c->H, cam, P, c->hsHist, c->fb(), c->aovPlane[HR_AOV_PLANE_ALBEDO], c->aovPlane[HR_AOV_PLANE_NORMAL_DEPTH],
-                         c->aovPlane[HR_AOV_PLANE_MOMENTS], c->rpExamined, c->rp.dev);
+    HIP_TRY(c, c->reproject.result.zero(c->stream));
+    launchReprojectMerge(c->stream, c->W, c->H, cam, P, c->history.hist, c->fb(), c->aov.plane[HR_AOV_PLANE_ALBEDO], c->aov.plane[HR_AOV_PLANE_NORMAL_DEPTH],
+                         c->aov.plane[HR_AOV_PLANE_MOMENTS], c->reproject.examined, c->reproject.result.dev);
     HIP_TRY(c, hipGetLastError());
-    c->hsMerged = c->rpMerged = true;
+    c->history.merged = c->reproject.merged = true;
     c->snapshotEpoch++; // (progressive snapshots taken before the merge are not handed out any more)
-    HIP_TRY(c, c->rp.fetch(c->stream));
+    HIP_TRY(c, c->reproject.result.fetch(c->stream));
     HIP_TRY(c, hipStreamSynchronize(c->stream));
     if (out) {
         *out = hr_reproject_result{};
-        out->reused_pixels = c->rp.host[0], out->rejected_pixels = c->rp.host[1], out->history_samples = c->rp.host[2];
-        out->pending_pixels = c->rp.host[3], out->examined_pixels = c->rp.host[4];
-        out->history_passes = c->hsPasses, out->passes = n;
+        out->reused_pixels = c->reproject.result.host[0], out->rejected_pixels = c->reproject.result.host[1], out->history_samples = c->reproject.result.host[2];
+        out->pending_pixels = c->reproject.result.host[3], out->examined_pixels = c->reproject.result.host[4];
+        out->history_passes = c->history.passes, out->passes = n;
     }
     return HR_OK;
 }
@@ -97,9 +97,9 @@ int hr_reproject_examined_get(hr_ctx *c, uint8_t *host_out)
     if (c->W <= 0) FAIL(c, HR_ERR_INVALID, "no frame");
     const size_t px = (size_t)c->W * c->H;
     std::memset(host_out, 0, px);
-    if (!c->rpExamined || c->rpStale) return HR_OK; // (no pixel of this frame has been examined)
+    if (!c->reproject.examined || c->reproject.stale) return HR_OK; // (no pixel of this frame has been examined)
     std::vector<unsigned long long> words(rpExaminedWords(c->W, c->H));
-    HIP_TRY(c, hipMemcpyAsync(words.data(), c->rpExamined, words.size() * 8, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipMemcpyAsync(words.data(), c->reproject.examined, words.size() * 8, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(c, hipStreamSynchronize(c->stream));
     const int blocksX = (c->W + 7) / 8;
     for (int y = 0; y < c->H; ++y)
@@ -115,7 +115,7 @@ int hr_reproject_preview(hr_ctx *c, const hr_pass_params *camera, const hr_histo
     // a foreign stream: the kernel on the ctx stream into the ctx's image, and the copy out over there
     int rc = previewRun(c, camera, params, nullptr, out);
     if (rc) return rc;
-    return copyOutOnStream(c, device_out, c->rpOut, (size_t)c->W * c->H * 16, stream);
+    return copyOutOnStream(c, device_out, c->reproject.out, (size_t)c->W * c->H * 16, stream);
 }
 
 int hr_reproject_preview_readback(hr_ctx *c, const hr_pass_params *camera, const hr_history_params *params, const float **rgba, int32_t *w, int32_t *h,
@@ -126,13 +126,13 @@ int hr_reproject_preview_readback(hr_ctx *c, const hr_pass_params *camera, const
     int rc = previewRun(c, camera, params, nullptr, nullptr);
     if (rc) return rc;
     const size_t bytes = (size_t)c->W * c->H * 16;
-    rc = growPinned(c, c->rpPinned, c->rpPinnedBytes, bytes);
+    rc = c->reproject.pinned.grow(c, bytes);
     if (rc) return rc;
-    HIP_TRY(c, hipMemcpyAsync(c->rpPinned, c->rpOut, bytes, hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(c, c->rp.fetch(c->stream));
+    HIP_TRY(c, hipMemcpyAsync(c->reproject.pinned.ptr, c->reproject.out, bytes, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, c->reproject.result.fetch(c->stream));
     HIP_TRY(c, hipStreamSynchronize(c->stream)); // (one wait for the image and the counters)
     previewFill(c, out);
-    *rgba = c->rpPinned;
+    *rgba = c->reproject.pinned.ptr;
     if (w) *w = c->W;
     if (h) *h = c->H;
     return HR_OK;
