@@ -6,6 +6,7 @@
 //
 //   hr_ctx.h          the context (what the opaque handle points to), the error macros
 //   hr_features.h     the state of the post-process features, one struct per feature with a release(); PinnedBuf, ResultCounters
+//   hr_step_memory.h  the bytes a macro step takes from scratch and from the step arena, stated once (host-only, like hr_tune.h)
 //   hr_core.hip       this file: context life cycle, frame, display, read-backs, statistics
 //   hr_scene.inl      geometry ingest, commit (build / refit / tree cache), textures, materials, lights, sample tables
 //   hr_pipeline.inl   ray memory, the macro step, batching and the packet selector, hr_render_pass, the step log
@@ -134,7 +135,7 @@ static void freeQueues(hr_ctx *c)
     }
     c->nSlotsAllocated = 0;
     c->queueCapacity = 0;
-    std::memset(c->stageSeen, 0, sizeof(c->stageSeen)); // (memory budget: back to the guarantee until the stages have been seen again)
+    c->budgetSeen.forget(); // (memory budget: back to the guarantee until the stages have been seen again)
 }
 
 // how many passes may be in flight: a slot holds a pass buffer (four partial sums once HR_ESTIMATOR_ALL_LIGHTS has been used); the rays
@@ -293,9 +294,9 @@ int hr_ctx_create(const hr_ctx_desc *desc, hr_ctx **out)
     if (groupsOk) c->hOverflow[0] = c->hOverflow[1] = c->hOverflow[2] = c->hOverflow[3] = 0u;
     if (!groupsOk || hipMalloc(&c->dScene, sizeof(SceneDev)) != hipSuccess ||
         hipMalloc(&c->dStats, sizeof(Stats) * kStatSlots) != hipSuccess || hipMalloc(&c->dScratch, sizeof(uint32_t) * 6 * kBoundSlots) != hipSuccess ||
-        hipMalloc(&c->dZero, 64) != hipSuccess || hipMalloc(&c->dProbe, 64) != hipSuccess || hipMemset(c->dProbe, 0, 64) != hipSuccess ||
-        hipStreamCreateWithFlags(&c->probeStream, hipStreamNonBlocking) != hipSuccess || hipEventCreateWithFlags(&c->evProbeA, hipEventDisableTiming) != hipSuccess ||
-        hipEventCreateWithFlags(&c->evProbeB, hipEventDisableTiming) != hipSuccess || hipMalloc(&c->dCounters, sizeof(Counters) * kMaxSlots) != hipSuccess ||
+        hipMalloc(&c->dZero, 64) != hipSuccess || hipMalloc(&c->selector.dProbe, 64) != hipSuccess || hipMemset(c->selector.dProbe, 0, 64) != hipSuccess ||
+        hipStreamCreateWithFlags(&c->selector.probeStream, hipStreamNonBlocking) != hipSuccess || hipEventCreateWithFlags(&c->selector.evProbeA, hipEventDisableTiming) != hipSuccess ||
+        hipEventCreateWithFlags(&c->selector.evProbeB, hipEventDisableTiming) != hipSuccess || hipMalloc(&c->dCounters, sizeof(Counters) * kMaxSlots) != hipSuccess ||
         hipMalloc(&c->dStepLog, sizeof(unsigned long long) * 3 * kStepLogCap) != hipSuccess) {
         delete c;
         return HR_ERR_DEVICE;
@@ -316,9 +317,9 @@ int hr_ctx_destroy(hr_ctx *c)
                 c->dbgGrowths, (double)c->dbgGrowBytes / 1048576.0, c->dbgWaits, c->dbgWaitSpun, (double)c->dbgWaitNs * 1e-6);
     drainPipeline(c);
     hipStreamSynchronize(c->stream);
-    if (c->probeStream) hipStreamSynchronize(c->probeStream), hipStreamDestroy(c->probeStream);
-    if (c->evProbeA) hipEventDestroy(c->evProbeA);
-    if (c->evProbeB) hipEventDestroy(c->evProbeB);
+    if (c->selector.probeStream) hipStreamSynchronize(c->selector.probeStream), hipStreamDestroy(c->selector.probeStream);
+    if (c->selector.evProbeA) hipEventDestroy(c->selector.evProbeA);
+    if (c->selector.evProbeB) hipEventDestroy(c->selector.evProbeB);
     c->drainTimes();
     for (hipEvent_t e : c->eventPool) hipEventDestroy(e);
     if (c->evPack) hipEventDestroy(c->evPack);
@@ -342,7 +343,7 @@ int hr_ctx_destroy(hr_ctx *c)
     hipFree(c->dMaterials), hipFree(c->dTextures), hipFree(c->dSeq), hipFree(c->dAperture), hipFree(c->dSeqOffsets);
     hipFree(c->dTexDensity);
     for (Texture &t : c->textures) hipFree(t.dmips);
-    hipFree(c->dScene), hipFree(c->dStats), hipFree(c->dScratch), hipFree(c->dZero), hipFree(c->dProbe), hipFree(c->dCounters), hipFree(c->dStepLog);
+    hipFree(c->dScene), hipFree(c->dStats), hipFree(c->dScratch), hipFree(c->dZero), hipFree(c->selector.dProbe), hipFree(c->dCounters), hipFree(c->dStepLog);
     if (c->hOverflow) hipHostFree((void *)c->hOverflow);
     for (hr_ctx::Group &G : c->groups) {
         if (G.hQCount) hipHostFree(G.hQCount);
@@ -533,7 +534,7 @@ int hr_frame_resize(hr_ctx *c, int32_t w, int32_t h)
     QUIESCE(c);
     c->W = w, c->H = h;
     c->snapshotEpoch++;
-    c->probeCountdown = 0; // (packet selector: another resolution)
+    c->selector.sceneOrSizeChanged(); // (another resolution)
     freeLagged(c->progFrame), freeLagged(c->progDisplay);
     hipFree(c->fbInternal);
     c->fbInternal = nullptr;

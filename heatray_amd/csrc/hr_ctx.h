@@ -6,6 +6,7 @@
 #include "hr_kernels.h"
 #include "hr_trace.h"
 #include "hr_tune.h"
+#include "hr_step_memory.h"
 #include "hr_features.h"
 
 #include <algorithm>
@@ -205,9 +206,19 @@ struct hr_ctx {
     // pipeline has shown the real lengths — by what it was seen to need (rayBytesSeen / batchSeen), with a fifth on top.
     unsigned long long memBudget = 0;
     // ray memory a pass needs at stage s of its life — what a step carves for it in the arena / in scratch —, the largest per-pass average
-    // seen so far (0: that stage has not been seen since the last resize / commit: it counts as long as it can possibly get)
-    double stageArenaSeen[kMaxBounceSlots] = {0}, stageScratchSeen[kMaxBounceSlots] = {0};
-    bool stageSeen[kMaxBounceSlots] = {false};
+    // seen so far (not seen since the last resize / commit: the stage counts as long as it can possibly get, budgetBytesPerPass)
+    struct BudgetSeen {
+        double stageArenaSeen[kMaxBounceSlots] = {0}, stageScratchSeen[kMaxBounceSlots] = {0};
+        bool stageSeen[kMaxBounceSlots] = {false};
+        void forget() { std::memset(stageSeen, 0, sizeof(stageSeen)); } // back to the guarantee until the stages have been seen again
+        void record(int st, double arena, double scratch)
+        {
+            stageArenaSeen[st] = (stageSeen[st] && stageArenaSeen[st] > arena) ? stageArenaSeen[st] : arena;
+            stageScratchSeen[st] = (stageSeen[st] && stageScratchSeen[st] > scratch) ? stageScratchSeen[st] : scratch;
+            stageSeen[st] = true;
+        }
+    };
+    BudgetSeen budgetSeen;
 
     // Mesh blocks come out of an arena of 64 MB chunks (bump allocation inside a chunk): a hipMalloc per submesh is a device-wide
     // synchronisation of ~0.1 ms each, which adds up for the scenes the reference loads (hundreds of submeshes).  A chunk whose last
@@ -304,22 +315,77 @@ struct hr_ctx {
     // DESIGN §2) instead of once per ray.  That walk enters a superset of the children; how much more is the scene's and the camera's:
     // the selector's probe walks both ways and reports F = children entered by the interval step / by the per-ray step (c3 1.05,
     // c3d 1.02, c2 1.01: +3..7 %; terrain 1.2, its short walks mostly leaves, where every extra child is a triangle test: -3.7 %): tune.pstep, tune.pstepf.
-    double lastLooseness = 0.0; // F of the last probe (0: none has reported)
-    bool useIntervalStep() const { return tune.pstep != 0 && (tune.pstepf <= 0 || lastLooseness == 0.0 || lastLooseness * 100.0 < (double)tune.pstepf); }
-    bool packetsOn = false;
-    uint32_t lastCameraCount = 0; // camera rays per pass behind the root cull, as last reported
-    int probeCountdown = 0;              // injecting steps until the next probe
-    bool probePending = false;
-    unsigned long long probeStep = 0;    // step (of group 0) that carried the pending probe
-    unsigned long long probeSeen[5] = {0, 0, 0, 0, 0}; // totals of the report the last decision was taken on
-    double lastOwnPerRay = 0.0;         // child boxes a probed camera ray entered: how long the scene's traversals are
-    unsigned long long probeWaves = 0;   // waves of the pending probe: it is complete when the third total has grown by as many
-    double lastUnion = 0.0;              // U of the last probe (HR_DEBUG_PIPE prints it)
-    float probeCamera[21] = {0};         // fov, aspect, focus distance, aperture, view matrix, interactive mode of the probed pass
-    unsigned long long *dProbe = nullptr; // five device counters (of eight words) the probe launches add to (never reset)
-    hipStream_t probeStream = nullptr;   // the probe runs beside the pipeline: it makes its own camera rays and writes only the counters
-    hipEvent_t evProbeA = nullptr, evProbeB = nullptr; // scene and tables as the group's stream sees them -> probe may start; probe done
-    bool probeGuard = false;             // evProbeB has not been waited for yet (drainPipeline does: the scene may change afterwards)
+    struct PacketSelector {
+        static const int kProbeEvery = 64; // injecting steps between two probes
+        double lastLooseness = 0.0; // F of the last probe (0: none has reported)
+        bool packetsOn = false;
+        uint32_t lastCameraCount = 0; // camera rays per pass behind the root cull, as last reported
+        int probeCountdown = 0;              // injecting steps until the next probe
+        bool probePending = false;
+        unsigned long long probeStep = 0;    // step (of group 0) that carried the pending probe
+        unsigned long long probeSeen[5] = {0, 0, 0, 0, 0}; // totals of the report the last decision was taken on
+        double lastOwnPerRay = 0.0;         // child boxes a probed camera ray entered: how long the scene's traversals are
+        unsigned long long probeWaves = 0;   // waves of the pending probe: it is complete when the third total has grown by as many
+        double lastUnion = 0.0;              // U of the last probe (HR_DEBUG_PIPE prints it)
+        float probeCamera[21] = {0};         // fov, aspect, focus distance, aperture, view matrix, interactive mode of the probed pass
+        unsigned long long *dProbe = nullptr; // five device counters (of eight words) the probe launches add to (never reset)
+        hipStream_t probeStream = nullptr;   // the probe runs beside the pipeline: it makes its own camera rays and writes only the counters
+        hipEvent_t evProbeA = nullptr, evProbeB = nullptr; // scene and tables as the group's stream sees them -> probe may start; probe done
+        bool probeGuard = false;             // evProbeB has not been waited for yet (drainPipeline does: the scene may change afterwards)
+
+        void sceneOrSizeChanged() { probeCountdown = 0; } // another tree, another resolution: the next injecting step probes
+        bool useIntervalStep(const Tune &tune) const { return tune.pstep != 0 && (tune.pstepf <= 0 || lastLooseness == 0.0 || lastLooseness * 100.0 < (double)tune.pstepf); }
+        bool packetsInUse(const Tune &tune) const { return tune.packets == 1 || (tune.packets == 2 && packetsOn); }
+        // Passes injected together when their camera rays travel as packets: a wave holds 2^k passes of 64 >> k pixels (hr_raygen.hip:
+        // k_raygen_packets), so the batch is the power of two next to the usual one (12 -> 16, 3 -> 4, 5 -> 4), sixteen per launch at most.
+        static int packetBatch(int injectBatch)
+        {
+            const int b = injectBatch < 1 ? 1 : injectBatch;
+            int up = 1;
+            while (up < b) up <<= 1;
+            return (4 * b >= 3 * up) ? up : up / 2;
+        }
+        static int packetLog2(int injectBatch)
+        {
+            int k = 0;
+            while ((2 << k) <= packetBatch(injectBatch) && k < 4) ++k;
+            return k;
+        }
+        // The pending probe's totals as group 0's step `stepIdx` found them with the queue lengths (Group::hProbe; steps from the probe's own on
+        // report them): complete once every wave of the probe has counted itself, and then the decision for the steps that follow.
+        void takeReport(const volatile unsigned long long *totals, unsigned long long stepIdx, const Tune &tune)
+        {
+            if (!probePending || stepIdx <= probeStep) return;
+            const unsigned long long pk = totals[0], ry = totals[1], done = totals[2], nr = totals[3], iv = totals[4];
+            if (done - probeSeen[2] < probeWaves) return;
+            const unsigned long long dPk = pk - probeSeen[0], dRy = ry - probeSeen[1], dNr = nr - probeSeen[3], dIv = iv - probeSeen[4];
+            probePending = false, probeSeen[0] = pk, probeSeen[1] = ry, probeSeen[2] = done, probeSeen[3] = nr, probeSeen[4] = iv;
+            if (dPk > 0) lastLooseness = (double)dIv / (double)dPk; // F: children entered, interval step / per-ray step
+            if (dRy > 0) {
+                lastUnion = (double)dPk / (double)dRy;
+                packetsOn = lastUnion * 100.0 < (double)tune.punion;
+                lastOwnPerRay = dNr ? (double)dRy / (double)dNr : 0.0;
+            }
+            if (tune.debugPipe) fprintf(stderr, "packet probe of step %llu (seen at step %llu): union %.3f, %.1f child boxes entered per ray -> packets %s; interval step F %.3f -> %s\n", probeStep, stepIdx, lastUnion, lastOwnPerRay, packetsOn ? "on" : "off", lastLooseness, useIntervalStep(tune) ? "on" : "off");
+        }
+        // Does group 0's step that injects passes with these parameters carry a probe?  (Counts the step, remembers the probed camera.)
+        bool wantsProbe(const hr_pass_params &pp, const Tune &tune)
+        {
+            if (tune.packets != 2 || probePending || pp.interactive_mode != 0) return false;
+            float cam[21] = {pp.fov_tan, pp.aspect_ratio, pp.focus_distance, pp.aperture_radius};
+            std::memcpy(cam + 4, pp.view_matrix, sizeof(pp.view_matrix));
+            cam[20] = (float)pp.interactive_mode;
+            // another camera sees another part of the tree: probe again, but not more often than every eighth injecting step (a camera in motion)
+            if (std::memcmp(cam, probeCamera, sizeof(cam)) != 0 && probeCountdown > 0 && probeCountdown <= kProbeEvery - 8) probeCountdown = 0;
+            if (probeCountdown > 0) {
+                probeCountdown--;
+                return false;
+            }
+            std::memcpy(probeCamera, cam, sizeof(cam));
+            return true;
+        }
+    };
+    PacketSelector selector;
     // persistent device arrays of the committed scene (grow-only capacities, reused across commits)
     GeomDev *dG = nullptr;
     size_t dGCap = 0;
@@ -437,7 +503,7 @@ struct hr_ctx {
     GroupState *grp = nullptr;
     LaunchCfg cfg(hipStream_t st) const
     {
-        return LaunchCfg{st, numCUs, traceBlocks, tune.sblocks, collectStats, textureLodUsed, allLightsUsed, hasGlass, tune.pswz, useIntervalStep() ? 1 : 0, (aov.mask & HR_AOV_SURFACE) != 0};
+        return LaunchCfg{st, numCUs, traceBlocks, tune.sblocks, collectStats, textureLodUsed, allLightsUsed, hasGlass, tune.pswz, selector.useIntervalStep(tune) ? 1 : 0, (aov.mask & HR_AOV_SURFACE) != 0};
     }
 };
 

@@ -46,7 +46,7 @@ struct LaunchCfg {
     bool allLights;  // some pass has asked for HR_ESTIMATOR_ALL_LIGHTS: the shading kernel that can emit two occlusion rays per vertex
     bool hasGlass;   // some material of the scene is glass: the glass shading kernel is launched too
     int packetSwizzle = 0; // k_raygen_packets deals whole 32x32 tiles to the XCDs instead of consecutive 16-pixel patches (HR_TUNE pswz)
-    int packetStep = 1;    // k_raygen_packets tests a node's children once per packet against the packet's bounds (hr_ctx::useIntervalStep; hr_packet_interval.h)
+    int packetStep = 1;    // k_raygen_packets tests a node's children once per packet against the packet's bounds (hr_ctx::PacketSelector::useIntervalStep; hr_packet_interval.h)
     bool aovSurface = false; // HR_AOV_SURFACE is enabled: launch the shading kernel that records the first visible surface (include/hrcore_aov.h)
     bool packetLens = false; // (LAST: hr_ctx::cfg fills the fields above by position)  a pass injected this step has a lens: k_raygen_packets_rays<.., false>, and SegDev::listed stays 0 (hr_pipeline.inl)
 };

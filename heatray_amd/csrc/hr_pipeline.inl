@@ -1,5 +1,9 @@
 // hr_pipeline.inl — a section of hr_core.hip (included there, inside its extern "C" block): the pass pipeline — pass slots and ray memory,
 // the macro step (tables, launches, the packet selector), batching, hr_render_pass / hr_flush, statistics of the pipeline itself.
+// macroStep is its stages in order, handing on a StepPlan: 1 injectPasses (pickSlot) — 2 endDrainedPassthrough — 3 listInFlight —
+// 4 boundQueues (waitCounts, PacketSelector::takeReport) — 5 sizeStepMemory (hr_step_memory.h, BudgetSeen::record, ensureRegion,
+// takeBackInjection) — 6 buildTable (the carve and its check) — 7 decidePackets (PacketSelector::wantsProbe) — 8 launchStep
+// (launchCameraRays, launchProbe, corunTraceBlocks) — 9 advancePasses; then resolveReady.
 int hr_clear(hr_ctx *c)
 {
     ENTER(c);
@@ -52,24 +56,21 @@ static int allocSlot(hr_ctx *c, hr_ctx::PassSlot &ps, hipStream_t st)
     return HR_OK;
 }
 
-// ---- the groups' ray memory (hr_ctx::Group::arena / scratch)
-static size_t align256(size_t b) { return (b + 255) & ~(size_t)255; }
-static size_t rayQueueBytes(size_t cap) { return 4 * align256(cap * 16); }
-static size_t shadowQueueBytes(size_t cap) { return 3 * align256(cap * 16); }
+// ---- the groups' ray memory (hr_ctx::Group::arena / scratch); the sizes are hr_step_memory.h's
 static RayQueue carveRayQueue(char *&p, size_t cap)
 {
     RayQueue q;
-    const size_t n = align256(cap * 16);
+    const size_t n = queuePlaneBytes(cap);
     q.A = (float4 *)p, q.B = (float4 *)(p + n), q.C = (float4 *)(p + 2 * n), q.D = (int4 *)(p + 3 * n);
-    p += 4 * n;
+    p += kRayQueuePlanes * n;
     return q;
 }
 static ShadowQueue carveShadowQueue(char *&p, size_t cap)
 {
     ShadowQueue q;
-    const size_t n = align256(cap * 16);
+    const size_t n = queuePlaneBytes(cap);
     q.A = (float4 *)p, q.B = (float4 *)(p + n), q.C = (float4 *)(p + 2 * n);
-    p += 3 * n;
+    p += kShadowQueuePlanes * n;
     return q;
 }
 // a region that is too small is replaced once everything the group has enqueued is done (what it held is dead by then: a step's
@@ -200,50 +201,79 @@ static int waitCounts(hr_ctx *c, hr_ctx::Group &G, int ring, unsigned long long 
     return HR_OK;
 }
 
-// One macro step of pipeline group g: (raygen of the injected passes) -> trace of every in-flight pass of the group ->
-// shade; passes whose last stage this was become `finished`.
-static const int kProbeEvery = 64; // injecting steps between two probes of the packet selector
+// ---- One macro step of pipeline group g: (raygen of the injected passes) -> trace of every in-flight pass of the group ->
+// shade; passes whose last stage this was become `finished`.  macroStep (below) is the list of its stages; StepPlan is what they hand on.
 static int stagesOf(const hr_ctx *c, const hr_pass_params &pp);
-static int packetLog2(const hr_ctx *c);
-static bool packetsInUse(const hr_ctx *c);
-static int macroStep(hr_ctx *c, int g, int nInject)
+struct StepPlan {
+    int g;
+    hr_ctx::Group *G;
+    LaunchCfg cfg; // as the step began: a probe report the step itself evaluates (boundQueues) bears on the launches of the steps after it
+    FrameDev fr;
+    unsigned long long stepIdx;
+    int ring;   // the step's entry of the table ring
+    uint32_t P; // camera rays an injected pass can have
+    size_t kS;  // occlusion rays per closest-hit ray
+    int order[kMaxSlots], n;    // the group's in-flight passes (their slots), oldest first: the step table's entries
+    uint32_t boundIn[kMaxSegs]; // per entry, an upper bound of the closest-hit rays it traces in this step
+    int injectedSlots[kMaxSegs], nInjected;
+    int injectedSegs[kMaxSegs], nInjectedSegs; // ... and their entries of the table
+    bool packetsNow, corunNow, anyLens;        // the selector's decision for this step (decidePackets)
+    int probeSeg;                              // table entry whose pass the step's probe looks through, -1: no probe
+    size_t needArena, needScratch;             // bytes the step carves
+};
+// HR_DEBUG_STEPTIMES: host time at the stages' borders
+struct StepClock {
+    bool on;
+    double t[5];
+    int n;
+    static double nowUs() { return (double)std::chrono::duration_cast<std::chrono::nanoseconds>(std::chrono::steady_clock::now().time_since_epoch()).count() * 1e-3; }
+    void mark()
+    {
+        if (on && n < 5) t[n++] = nowUs();
+    }
+    void print(unsigned long long stepIdx, int nInject) const
+    {
+        if (on) fprintf(stderr, "step %llu (inject %d): begin %.1f us | injected +%.1f | counts known +%.1f | table built +%.1f | copy enqueued +%.1f | launched +%.1f\n", stepIdx, nInject, t[0], t[1] - t[0], t[2] - t[1], t[3] - t[2], t[4] - t[3], nowUs() - t[4]);
+    }
+};
+static bool tracesClosest(const hr_ctx *c, const hr_ctx::PassSlot &ps) { return c->hasPassthrough || ps.step < ps.nIter; }
+
+// The slot an injected pass takes: the free one whose pass was resolved longest ago: the injection waits for that resolve, and a slot
+// freed by the step just enqueued would chain this group's step behind the other group's (no overlap).  A slot resolved only recently
+// is passed over for fresh memory while the slot budget allows.  -1: none is free.
+static int pickSlot(const hr_ctx *c, int nInject)
 {
-    const bool dbgT = c->tune.debugStepTimes;
-    auto nowUs = [] { return (double)std::chrono::duration_cast<std::chrono::nanoseconds>(std::chrono::steady_clock::now().time_since_epoch()).count() * 1e-3; };
-    const double tA = dbgT ? nowUs() : 0.0;
-    double tB = 0, tC = 0, tD = 0, tE = 0;
-    hr_ctx::Group &G = c->groups[g];
-    const LaunchCfg cfg = c->cfg(G.stream);
-    FrameDev fr = c->frame;
-    fr.fb = c->fb();
+    int slot = -1, fresh = -1;
+    for (int i = 0; i < kMaxSlots; ++i) {
+        const hr_ctx::PassSlot &cand = c->slots[i];
+        if (cand.active || cand.finished) continue;
+        if (!cand.allocated) {
+            if (fresh < 0) fresh = i;
+        } else if (slot < 0 || cand.resolvedAt < c->slots[slot].resolvedAt) {
+            slot = i;
+        }
+    }
+    const unsigned long long recent = 2ull * (unsigned long long)c->nGroups * (unsigned long long)(nInject > 0 ? nInject : 1);
+    if (fresh >= 0 && c->nSlotsAllocated < slotLimit(c) && (slot < 0 || (c->nGroups > 1 && c->nextResolveOrder - c->slots[slot].resolvedAt < recent)))
+        slot = fresh;
+    return slot < 0 ? fresh : slot;
+}
+
+// stage 1: what the caller's stream set up becomes visible, the waiting passes take their slots, their counters go back to zero
+static int injectPasses(hr_ctx *c, StepPlan &S, int nInject)
+{
+    hr_ctx::Group &G = *S.G;
     if (G.needUserSync) { // state set up on the caller's stream (scene, tables, cleared buffers) must be visible
         HIP_TRY(c, hipEventRecord(G.evUser, c->stream));
         HIP_TRY(c, hipStreamWaitEvent(G.stream, G.evUser, 0));
         G.needUserSync = false;
     }
-    int injectedSlots[kMaxSegs];
     hipEvent_t waited[kMaxSegs];
-    int nInjected = 0;
+    S.nInjected = 0;
     for (int k = 0; k < nInject; ++k) {
         const hr_pass_params pp = c->pendingInject.front();
         c->pendingInject.pop_front();
-        // Reuse the free slot whose pass was resolved longest ago: the injection waits for that resolve, and a slot freed
-        // by the step just enqueued would chain this group's step behind the other group's (no overlap).  A slot resolved
-        // only recently is passed over for fresh memory while the slot budget allows.
-        int slot = -1, fresh = -1;
-        for (int i = 0; i < kMaxSlots; ++i) {
-            const hr_ctx::PassSlot &cand = c->slots[i];
-            if (cand.active || cand.finished) continue;
-            if (!cand.allocated) {
-                if (fresh < 0) fresh = i;
-            } else if (slot < 0 || cand.resolvedAt < c->slots[slot].resolvedAt) {
-                slot = i;
-            }
-        }
-        const unsigned long long recent = 2ull * (unsigned long long)c->nGroups * (unsigned long long)(nInject > 0 ? nInject : 1);
-        if (fresh >= 0 && c->nSlotsAllocated < slotLimit(c) && (slot < 0 || (c->nGroups > 1 && c->nextResolveOrder - c->slots[slot].resolvedAt < recent)))
-            slot = fresh;
-        if (slot < 0) slot = fresh;
+        const int slot = pickSlot(c, nInject);
         if (slot < 0) FAIL(c, HR_ERR_INVALID, "internal: no free pass slot");
         hr_ctx::PassSlot &ps = c->slots[slot];
         if (!ps.allocated) {
@@ -252,161 +282,155 @@ static int macroStep(hr_ctx *c, int g, int nInject)
         }
         if (ps.everResolved) { // the pass buffer is free again once the launch that resolved it has run
             bool seen = false;
-            for (int j = 0; j < nInjected; ++j) seen = seen || waited[j] == ps.resolvedEv;
+            for (int j = 0; j < S.nInjected; ++j) seen = seen || waited[j] == ps.resolvedEv;
             if (!seen) HIP_TRY(c, hipStreamWaitEvent(G.stream, ps.resolvedEv, 0));
         }
-        waited[nInjected] = ps.everResolved ? ps.resolvedEv : nullptr;
-        ps.active = true, ps.finished = false, ps.group = g, ps.step = 0, ps.nIter = pp.max_ray_depth + 1, ps.pp = pp;
+        waited[S.nInjected] = ps.everResolved ? ps.resolvedEv : nullptr;
+        ps.active = true, ps.finished = false, ps.group = S.g, ps.step = 0, ps.nIter = pp.max_ray_depth + 1, ps.pp = pp;
         ps.qcur = RayQueue{}, ps.scur = ShadowQueue{}, ps.capCur = 0, ps.sCapCur = 0;
         ps.order = c->injected++;
-        injectedSlots[nInjected++] = slot;
+        S.injectedSlots[S.nInjected++] = slot;
     }
-    for (int j0 = 0; j0 < nInjected; j0 += kMaxBatch) { // the injected passes' counters back to zero, one launch
+    for (int j0 = 0; j0 < S.nInjected; j0 += kMaxBatch) { // the injected passes' counters back to zero, one launch
         CounterList cl{};
-        for (int j = j0; j < nInjected && cl.n < kMaxBatch; ++j) cl.ctr[cl.n++] = c->slots[injectedSlots[j]].ctr;
-        launchZeroCounters(cfg, cl);
+        for (int j = j0; j < S.nInjected && cl.n < kMaxBatch; ++j) cl.ctr[cl.n++] = c->slots[S.injectedSlots[j]].ctr;
+        launchZeroCounters(S.cfg, cl);
     }
-    // Pass-through rays (back faces of single-sided materials, alpha masks: physicallyBased.rlsl:70-108) are not bounded by
-    // maxRayDepth, so in such scenes a pass runs until its closest-hit queue is empty.  The queue lengths come from the snapshot
-    // taken two macro steps ago (see Group::hQCount): a slot about to run stage `st` then knows the lengths of stages <= st - 1;
-    // if stage st - 1 had no rays, it emitted nothing and the pass was complete with the steps already enqueued.
-    if (c->hasPassthrough) {
-        const unsigned long long N = G.stepCounter;
-        if (N >= 2 && G.statusUsed[(N - 2) % kTableRing]) {
-            const int ring = (int)((N - 2) % kTableRing);
-            HIP_TRY(c, hipEventSynchronize(G.statusEv[ring]));
-            hr_ctx::PassSlot *endedEarly[kMaxSlots];
-            int nEndedEarly = 0;
-            const uint32_t *snap = G.hQCount + (size_t)ring * kMaxSlots * kMaxBounceSlots;
-            for (int i = 0; i < kMaxSlots; ++i) {
-                hr_ctx::PassSlot &ps = c->slots[i];
-                if (!ps.active || ps.group != g || G.statusOrder[ring][i] != ps.order + 1ull) continue;
-                const int st = ps.step;
-                const bool empty = st >= 2 && snap[(size_t)i * kMaxBounceSlots + ((st - 1) % kMaxBounceSlots)] == 0u;
-                if (empty) {
-                    ps.active = false, ps.finished = true;
-                    endedEarly[nEndedEarly++] = &ps;
-                }
-            }
-            hr_ctx::PassSlot *owner = nullptr; // the newest of them: it is resolved last, so its event outlives the others' waits
-            for (int k = 0; k < nEndedEarly; ++k)
-                if (!owner || endedEarly[k]->order > owner->order) owner = endedEarly[k];
-            if (owner) HIP_TRY(c, hipEventRecord(owner->evFinal, G.stream));
-            for (int k = 0; k < nEndedEarly; ++k) endedEarly[k]->finalEv = owner->evFinal;
+    return HR_OK;
+}
+// Nothing of the step has been enqueued except the counters' reset: the passes it was to inject go back to the head of the request queue
+// (their slots are free again), so that a later call injects them properly instead of tracing queues no k_raygen ever filled.
+static void takeBackInjection(hr_ctx *c, StepPlan &S)
+{
+    for (int j = S.nInjected - 1; j >= 0; --j) {
+        hr_ctx::PassSlot &ps = c->slots[S.injectedSlots[j]];
+        c->pendingInject.push_front(ps.pp);
+        ps.active = false;
+        c->injected--;
+    }
+    S.G->stepCounter--;
+}
+
+// stage 2.  Pass-through rays (back faces of single-sided materials, alpha masks: physicallyBased.rlsl:70-108) are not bounded by
+// maxRayDepth, so in such scenes a pass runs until its closest-hit queue is empty.  The queue lengths come from the snapshot
+// taken two macro steps ago (see Group::hQCount): a slot about to run stage `st` then knows the lengths of stages <= st - 1;
+// if stage st - 1 had no rays, it emitted nothing and the pass was complete with the steps already enqueued.
+static int endDrainedPassthrough(hr_ctx *c, StepPlan &S)
+{
+    hr_ctx::Group &G = *S.G;
+    const unsigned long long N = G.stepCounter;
+    if (!c->hasPassthrough || N < 2 || !G.statusUsed[(N - 2) % kTableRing]) return HR_OK;
+    const int ring = (int)((N - 2) % kTableRing);
+    HIP_TRY(c, hipEventSynchronize(G.statusEv[ring]));
+    hr_ctx::PassSlot *endedEarly[kMaxSlots];
+    int nEndedEarly = 0;
+    const uint32_t *snap = G.hQCount + (size_t)ring * kMaxSlots * kMaxBounceSlots;
+    for (int i = 0; i < kMaxSlots; ++i) {
+        hr_ctx::PassSlot &ps = c->slots[i];
+        if (!ps.active || ps.group != S.g || G.statusOrder[ring][i] != ps.order + 1ull) continue;
+        const int st = ps.step;
+        const bool empty = st >= 2 && snap[(size_t)i * kMaxBounceSlots + ((st - 1) % kMaxBounceSlots)] == 0u;
+        if (empty) {
+            ps.active = false, ps.finished = true;
+            endedEarly[nEndedEarly++] = &ps;
         }
     }
-    if (dbgT) tB = nowUs();
-    // table of the group's in-flight passes, oldest first
-    int order[kMaxSlots], n = 0;
+    hr_ctx::PassSlot *owner = nullptr; // the newest of them: it is resolved last, so its event outlives the others' waits
+    for (int k = 0; k < nEndedEarly; ++k)
+        if (!owner || endedEarly[k]->order > owner->order) owner = endedEarly[k];
+    if (owner) HIP_TRY(c, hipEventRecord(owner->evFinal, G.stream));
+    for (int k = 0; k < nEndedEarly; ++k) endedEarly[k]->finalEv = owner->evFinal;
+    return HR_OK;
+}
+
+// stage 3: the group's in-flight passes, oldest first
+static void listInFlight(const hr_ctx *c, StepPlan &S)
+{
+    S.n = 0;
     for (int i = 0; i < kMaxSlots; ++i)
-        if (c->slots[i].active && c->slots[i].group == g) order[n++] = i;
-    for (int a = 1; a < n; ++a)
-        for (int b = a; b > 0 && c->slots[order[b]].order < c->slots[order[b - 1]].order; --b) std::swap(order[b], order[b - 1]);
-    if (n == 0) return resolveReady(c);
-    if (n > kMaxSegs) FAIL(c, HR_ERR_INVALID, "internal: too many passes in one group");
-    const unsigned long long stepIdx = G.stepCounter++;
-    const int ring = (int)(stepIdx % kTableRing);
-    if (G.tableUsed[ring]) HIP_TRY(c, hipEventSynchronize(G.tableCopied[ring])); // staging entry free again (4 steps old)
-    // ---- ray memory of this step (Group::arena): every queue sized by an upper bound of what can arrive in it
-    const uint32_t P = c->tune.ovf == 1 ? c->queueCapacity / 8u + 1u : (c->queueCapacity ? c->queueCapacity : 1u); // (ovf=1, TEST ONLY: camera rays do not fit)
-    const size_t kS = c->allLightsUsed ? 4 : 1;
-    uint32_t boundIn[kMaxSegs];
-    {
-        bool wanted = false;
-        for (int k = 0; k < n; ++k) wanted = wanted || c->slots[order[k]].step > 0;
-        int idxOfSlot[kMaxSlots];
-        const int prev = (int)((stepIdx + kTableRing - 1) % kTableRing);
-        if (wanted && stepIdx > 0) {
-            int rc = waitCounts(c, G, prev, stepIdx); // (step stepIdx - 1 wrote stepIdx: its number + 1)
-            if (rc) return rc;
-            if (g == 0 && c->probePending && stepIdx > c->probeStep) { // (steps from the probe's own on report the totals) complete once every wave of the probe has counted itself
-                const unsigned long long pk = G.hProbe[8 * prev], ry = G.hProbe[8 * prev + 1], done = G.hProbe[8 * prev + 2], nr = G.hProbe[8 * prev + 3], iv = G.hProbe[8 * prev + 4];
-                if (done - c->probeSeen[2] >= c->probeWaves) {
-                    const unsigned long long dPk = pk - c->probeSeen[0], dRy = ry - c->probeSeen[1], dNr = nr - c->probeSeen[3], dIv = iv - c->probeSeen[4];
-                    c->probePending = false, c->probeSeen[0] = pk, c->probeSeen[1] = ry, c->probeSeen[2] = done, c->probeSeen[3] = nr, c->probeSeen[4] = iv;
-                    if (dPk > 0) c->lastLooseness = (double)dIv / (double)dPk; // F: children entered, interval step / per-ray step
-                    if (dRy > 0) {
-                        c->lastUnion = (double)dPk / (double)dRy;
-                        c->packetsOn = c->lastUnion * 100.0 < (double)c->tune.punion;
-                        c->lastOwnPerRay = dNr ? (double)dRy / (double)dNr : 0.0;
-                    }
-                    if (c->tune.debugPipe) fprintf(stderr, "packet probe of step %llu (seen at step %llu): union %.3f, %.1f child boxes entered per ray -> packets %s; interval step F %.3f -> %s\n", c->probeStep, stepIdx, c->lastUnion, c->lastOwnPerRay, c->packetsOn ? "on" : "off", c->lastLooseness, c->useIntervalStep() ? "on" : "off");
-                }
-            }
-            for (int i = 0; i < kMaxSlots; ++i) idxOfSlot[i] = -1;
-            for (int j = 0; j < G.countN[prev]; ++j) idxOfSlot[G.countSlot[prev][j]] = j;
-        }
-        for (int k = 0; k < n; ++k) {
-            const hr_ctx::PassSlot &ps = c->slots[order[k]];
-            uint32_t b = P;
-            if (ps.step > 0) {
-                b = ps.capCur; // (what its queue can hold is a bound too: used when the pass was not in the previous step's table)
-                const int j = (wanted && stepIdx > 0) ? idxOfSlot[order[k]] : -1;
-                if (j >= 0 && G.countOrder[prev][j] == ps.order + 1ull) {
-                    const uint32_t seen = G.hCounts[(size_t)prev * kMaxSegs + j]; // length of its closest-hit queue one stage ago
-                    b = seen < b ? seen : b;
-                    if (ps.step == 1 && seen < P) c->lastCameraCount = seen; // (camera rays that passed the root cull: what a packet kernel traces per pass)
-                }
-            }
-            // TEST ONLY (HR_TUNE="ovf=": tests/test_gpu_parity.py forces every kind of overflow once): half of what the bound should be
-            if (c->tune.ovf == 2 && ps.step == 1) b = b / 2u + 1u;
-            boundIn[k] = b;
-        }
+        if (c->slots[i].active && c->slots[i].group == S.g) S.order[S.n++] = i;
+    for (int a = 1; a < S.n; ++a)
+        for (int b = a; b > 0 && c->slots[S.order[b]].order < c->slots[S.order[b - 1]].order; --b) std::swap(S.order[b], S.order[b - 1]);
+}
+
+// stage 4: every queue of the step is sized by an upper bound of what can arrive in it (Group::arena): wait for the lengths the previous
+// step's k_trace reported — the packet probe's totals come with them — and bound each pass's closest-hit queue
+static int boundQueues(hr_ctx *c, StepPlan &S)
+{
+    hr_ctx::Group &G = *S.G;
+    bool wanted = false;
+    for (int k = 0; k < S.n; ++k) wanted = wanted || c->slots[S.order[k]].step > 0;
+    int idxOfSlot[kMaxSlots];
+    const int prev = (int)((S.stepIdx + kTableRing - 1) % kTableRing);
+    if (wanted && S.stepIdx > 0) {
+        int rc = waitCounts(c, G, prev, S.stepIdx); // (step stepIdx - 1 wrote stepIdx: its number + 1)
+        if (rc) return rc;
+        if (S.g == 0) c->selector.takeReport(G.hProbe + 8 * prev, S.stepIdx, c->tune);
+        for (int i = 0; i < kMaxSlots; ++i) idxOfSlot[i] = -1;
+        for (int j = 0; j < G.countN[prev]; ++j) idxOfSlot[G.countSlot[prev][j]] = j;
     }
-    if (dbgT) tC = nowUs();
-    size_t needArena = 0, needScratch = 0;
-    for (int k = 0; k < n; ++k) {
-        const hr_ctx::PassSlot &ps = c->slots[order[k]];
-        const bool closest = c->hasPassthrough || ps.step < ps.nIter;
-        if (ps.step == 0) needScratch += rayQueueBytes(P);
-        if (closest) {
-            needScratch += align256((size_t)boundIn[k] * hitRecordSize()) + align256((size_t)boundIn[k] * 4);
-            needArena += rayQueueBytes(boundIn[k]) + shadowQueueBytes((size_t)boundIn[k] * kS);
+    for (int k = 0; k < S.n; ++k) {
+        const hr_ctx::PassSlot &ps = c->slots[S.order[k]];
+        uint32_t b = S.P;
+        if (ps.step > 0) {
+            b = ps.capCur; // (what its queue can hold is a bound too: used when the pass was not in the previous step's table)
+            const int j = (wanted && S.stepIdx > 0) ? idxOfSlot[S.order[k]] : -1;
+            if (j >= 0 && G.countOrder[prev][j] == ps.order + 1ull) {
+                const uint32_t seen = G.hCounts[(size_t)prev * kMaxSegs + j]; // length of its closest-hit queue one stage ago
+                b = seen < b ? seen : b;
+                if (ps.step == 1 && seen < S.P) c->selector.lastCameraCount = seen; // (camera rays that passed the root cull: what a packet kernel traces per pass)
+            }
         }
+        // TEST ONLY (HR_TUNE="ovf=": tests/test_gpu_parity.py forces every kind of overflow once): half of what the bound should be
+        if (c->tune.ovf == 2 && ps.step == 1) b = b / 2u + 1u;
+        S.boundIn[k] = b;
+    }
+    return HR_OK;
+}
+
+// what table entry k takes from scratch and from the arena (hr_step_memory.h): the need, the budget's record and the carve all ask here
+static SegmentBytes segmentBytesOf(const hr_ctx *c, const StepPlan &S, int k)
+{
+    const hr_ctx::PassSlot &ps = c->slots[S.order[k]];
+    return segmentBytes(S.P, S.boundIn[k], S.kS, hitRecordSize(), ps.step == 0, tracesClosest(c, ps));
+}
+// stage 5: the step's bytes, what the memory budget learns from them, and regions that hold them.  Out of device memory: the injection
+// is taken back, so that a later call — after the caller has released memory — finds the pipeline as this one did.
+static int sizeStepMemory(hr_ctx *c, StepPlan &S)
+{
+    hr_ctx::Group &G = *S.G;
+    S.needArena = S.needScratch = 0;
+    for (int k = 0; k < S.n; ++k) {
+        const SegmentBytes b = segmentBytesOf(c, S, k);
+        S.needScratch += b.scratch, S.needArena += b.arena;
     }
     if (c->memBudget) { // what this step carves per pass and stage (budgetBytesPerPass)
         double sumA[kMaxBounceSlots] = {0}, sumS[kMaxBounceSlots] = {0};
         int cnt[kMaxBounceSlots] = {0};
-        for (int k = 0; k < n; ++k) {
-            const hr_ctx::PassSlot &ps = c->slots[order[k]];
-            const int st = ps.step < kMaxBounceSlots ? ps.step : kMaxBounceSlots - 1;
-            const bool closest = c->hasPassthrough || ps.step < ps.nIter;
+        for (int k = 0; k < S.n; ++k) {
+            const int step = c->slots[S.order[k]].step, st = step < kMaxBounceSlots ? step : kMaxBounceSlots - 1;
+            const SegmentBytes b = segmentBytesOf(c, S, k);
             cnt[st]++;
-            if (ps.step == 0) sumS[st] += (double)rayQueueBytes(P);
-            if (closest) {
-                sumS[st] += (double)(align256((size_t)boundIn[k] * hitRecordSize()) + align256((size_t)boundIn[k] * 4));
-                sumA[st] += (double)(rayQueueBytes(boundIn[k]) + shadowQueueBytes((size_t)boundIn[k] * kS));
-            }
+            sumS[st] += (double)b.scratch, sumA[st] += (double)b.arena;
         }
         for (int st = 0; st < kMaxBounceSlots; ++st)
-            if (cnt[st]) {
-                const double a = sumA[st] / cnt[st], sc = sumS[st] / cnt[st];
-                c->stageArenaSeen[st] = (c->stageSeen[st] && c->stageArenaSeen[st] > a) ? c->stageArenaSeen[st] : a;
-                c->stageScratchSeen[st] = (c->stageSeen[st] && c->stageScratchSeen[st] > sc) ? c->stageScratchSeen[st] : sc;
-                c->stageSeen[st] = true;
-            }
+            if (cnt[st]) c->budgetSeen.record(st, sumA[st] / cnt[st], sumS[st] / cnt[st]);
     }
-    hr_ctx::Group::Region &arena = G.arena[stepIdx & 1ull];
-    {
-        G.arenaHighWater = needArena > G.arenaHighWater ? needArena : G.arenaHighWater;
-        int rc = ensureRegion(c, G, arena, G.arenaHighWater, "rays emitted by a step");
-        if (rc == HR_OK) rc = ensureRegion(c, G, G.scratch, needScratch, "camera rays and hit records of a step");
-        if (rc) {
-            // out of device memory: nothing of this step has been enqueued except the counters' reset.  The passes it was to inject go
-            // back to the head of the request queue (their slots are free again), so that a later call — after the caller has released
-            // memory — injects them properly instead of tracing queues no k_raygen ever filled.
-            for (int j = nInjected - 1; j >= 0; --j) {
-                hr_ctx::PassSlot &ps = c->slots[injectedSlots[j]];
-                c->pendingInject.push_front(ps.pp);
-                ps.active = false;
-                c->injected--;
-            }
-            G.stepCounter--;
-            return rc;
-        }
-    }
+    G.arenaHighWater = S.needArena > G.arenaHighWater ? S.needArena : G.arenaHighWater;
+    int rc = ensureRegion(c, G, G.arena[S.stepIdx & 1ull], G.arenaHighWater, "rays emitted by a step");
+    if (rc == HR_OK) rc = ensureRegion(c, G, G.scratch, S.needScratch, "camera rays and hit records of a step");
+    if (rc) takeBackInjection(c, S);
+    return rc;
+}
+
+// stage 6: the step table — every entry's queues carved out of the step's memory, its counters, its pass
+static int buildTable(hr_ctx *c, StepPlan &S)
+{
+    hr_ctx::Group &G = *S.G;
+    hr_ctx::Group::Region &arena = G.arena[S.stepIdx & 1ull];
     char *pArena = arena.base, *pScratch = G.scratch.base;
-    StepTable &tbl = G.hTables[ring];
+    StepTable &tbl = G.hTables[S.ring];
+    const int n = S.n;
     std::memset(tbl.heads, 0, sizeof(tbl.heads));
     std::memset(tbl.clkStart, 0xFF, sizeof(tbl.clkStart)), std::memset(tbl.clkEnd, 0, sizeof(tbl.clkEnd));
     tbl.headsLog2 = (uint32_t)c->tune.heads;
@@ -415,27 +439,39 @@ static int macroStep(hr_ctx *c, int g, int nInject)
     tbl.fetchMax = c->tune.fmax, tbl.fetchMin = c->tune.fmin;
     tbl.staticPerWave = c->tune.sdeal, tbl.hasGlass = c->hasGlass ? 1 : 0;
     tbl.primaryFromSeg = n, tbl.fetchMaxPrimary = (c->tune.fprim & 0xFFFF) | ((c->tune.fgate & 0xFFFF) << 16); // (primaryFromSeg is set below, once the injected passes' places in the table are known)
-    int injectedSegs[kMaxSegs];
-    int nInjectedSegs = 0;
-    for (int k = 0; k < n; ++k) {
-        hr_ctx::PassSlot &ps = c->slots[order[k]];
+    for (int k = 0; k < n; ++k) { // the carve: nothing but the table is written yet
+        const hr_ctx::PassSlot &ps = c->slots[S.order[k]];
         SegDev &sg = tbl.seg[k];
         const int st = ps.step;
-        const bool closest = c->hasPassthrough || st < ps.nIter;
-        sg.qin = st == 0 ? carveRayQueue(pScratch, P) : ps.qcur; // (a new pass's camera rays live for this step only)
-        sg.sqIn = ps.scur;                                        // (nothing to trace there in a pass's first step: sCountIn is the zero word)
-        sg.qinCap = st == 0 ? P : ps.capCur, sg.sInCap = st == 0 ? 0u : ps.sCapCur, sg.sOutCap = 0u;
+        const uint32_t bound = S.boundIn[k];
+        sg.qin = st == 0 ? carveRayQueue(pScratch, S.P) : ps.qcur; // (a new pass's camera rays live for this step only)
+        sg.sqIn = ps.scur;                                         // (nothing to trace there in a pass's first step: sCountIn is the zero word)
+        sg.qinCap = st == 0 ? S.P : ps.capCur, sg.sInCap = st == 0 ? 0u : ps.sCapCur, sg.sOutCap = 0u;
         sg.qout = RayQueue{}, sg.sqOut = ShadowQueue{}, sg.hits = nullptr, sg.hitIdx = nullptr;
-        if (closest) {
-            sg.hits = (HitRec *)pScratch, pScratch += align256((size_t)boundIn[k] * hitRecordSize());
-            sg.hitIdx = (uint32_t *)pScratch, pScratch += align256((size_t)boundIn[k] * 4);
-            sg.qout = carveRayQueue(pArena, boundIn[k]);
-            sg.sqOut = carveShadowQueue(pArena, (size_t)boundIn[k] * kS);
-            ps.qcur = sg.qout, ps.scur = sg.sqOut, ps.capCur = boundIn[k];
-            sg.sOutCap = (uint32_t)((size_t)boundIn[k] * kS);
+        sg.closestEnabled = tracesClosest(c, ps) ? 1 : 0;
+        if (sg.closestEnabled) {
+            sg.hits = (HitRec *)pScratch, pScratch += align256((size_t)bound * hitRecordSize());
+            sg.hitIdx = (uint32_t *)pScratch, pScratch += align256((size_t)bound * kHitListEntryBytes);
+            sg.qout = carveRayQueue(pArena, bound);
+            sg.sqOut = carveShadowQueue(pArena, (size_t)bound * S.kS);
+            sg.sOutCap = (uint32_t)((size_t)bound * S.kS);
             if (c->tune.ovf == 3 && st == 0) sg.sOutCap = sg.sOutCap / 8u + 1u; // TEST ONLY: the first hits' occlusion rays do not fit
-            ps.sCapCur = sg.sOutCap;
         }
+        sg.hitCap = sg.closestEnabled ? bound : 0u; // (capacity of hits, the hit list and qout: what was carved above)
+    }
+    // both cursors advanced by what sizeStepMemory provided for, or a kernel of this step would write past a region
+    const size_t carved[2] = {(size_t)(pArena - arena.base), (size_t)(pScratch - G.scratch.base)}, sized[2] = {S.needArena, S.needScratch};
+    for (int r = 0; r < 2; ++r)
+        if (carved[r] != sized[r]) {
+            takeBackInjection(c, S);
+            FAIL(c, HR_ERR_DEVICE, "internal: a step carved " + std::to_string(carved[r]) + " bytes of " + (r ? "scratch" : "the step arena") + " but sized " + std::to_string(sized[r]));
+        }
+    S.nInjectedSegs = 0;
+    for (int k = 0; k < n; ++k) {
+        hr_ctx::PassSlot &ps = c->slots[S.order[k]];
+        SegDev &sg = tbl.seg[k];
+        const int st = ps.step;
+        if (sg.closestEnabled) ps.qcur = sg.qout, ps.scur = sg.sqOut, ps.capCur = S.boundIn[k], ps.sCapCur = sg.sOutCap;
         sg.passbuf = ps.passbuf;
         sg.passbufB = ps.pp.estimator == HR_ESTIMATOR_ALL_LIGHTS ? ps.passbufB : nullptr;
         sg.aov = ps.aov;
@@ -456,75 +492,67 @@ static int macroStep(hr_ctx *c, int g, int nInject)
         sg.qCountOut = &ps.ctr->qCount[(st + 1) % R];
         sg.sCountOut = &ps.ctr->sCount[st % R];
         sg.pCount = &ps.ctr->pCount[st % R], sg.gCount = &ps.ctr->gCount[st % R];
-        sg.listed = 0;
-        sg.hitCap = closest ? boundIn[k] : 0u, sg.packets = 0; // (capacity of hits, the hit list and qout: what was carved above)
+        sg.listed = 0, sg.packets = 0;
         sg.pp = ps.pp;
-        sg.closestEnabled = closest ? 1 : 0;
-        G.countSlot[ring][k] = order[k], G.countOrder[ring][k] = ps.order + 1ull;
-        for (int j = 0; j < nInjected; ++j)
-            if (order[k] == injectedSlots[j]) injectedSegs[nInjectedSegs++] = k;
+        G.countSlot[S.ring][k] = S.order[k], G.countOrder[S.ring][k] = ps.order + 1ull;
+        for (int j = 0; j < S.nInjected; ++j)
+            if (S.order[k] == S.injectedSlots[j]) S.injectedSegs[S.nInjectedSegs++] = k;
     }
-    if (nInjectedSegs > 0) tbl.primaryFromSeg = injectedSegs[0]; // (the table is in pass order: the passes injected now are its last entries)
-    // packet selector (above): do the injected passes' camera rays travel as packets (k_raygen_packets), beside k_trace or in front of it, and does this step carry a probe?
-    int probeSeg = -1;
-    bool packetsNow = packetsInUse(c) && nInjectedSegs > 0 && tbl.seg[injectedSegs[0]].pp.interactive_mode == 0; // (interactive sub-passes of one sample share no pixels)
-    if (c->tune.packets == 2 && g == 0 && nInjectedSegs > 0 && !c->probePending && tbl.seg[injectedSegs[0]].pp.interactive_mode == 0) {
-        const hr_pass_params &pp = tbl.seg[injectedSegs[0]].pp;
-        float cam[21] = {pp.fov_tan, pp.aspect_ratio, pp.focus_distance, pp.aperture_radius};
-        std::memcpy(cam + 4, pp.view_matrix, sizeof(pp.view_matrix));
-        cam[20] = (float)pp.interactive_mode;
-        // another camera sees another part of the tree: probe again, but not more often than every eighth injecting step (a camera in motion)
-        if (std::memcmp(cam, c->probeCamera, sizeof(cam)) != 0 && c->probeCountdown > 0 && c->probeCountdown <= kProbeEvery - 8) c->probeCountdown = 0;
-        if (c->probeCountdown <= 0) {
-            probeSeg = injectedSegs[0];
-            std::memcpy(c->probeCamera, cam, sizeof(cam));
-        } else {
-            c->probeCountdown--;
-        }
-    }
-    const bool corunNow = packetsNow && (c->tune.corun == 2 || (c->tune.corun == 1 && c->lastOwnPerRay >= (double)c->tune.cmin));
-    for (int j = 0; j < nInjectedSegs; ++j)
-        if (packetsNow) tbl.seg[injectedSegs[j]].packets = corunNow ? 2 : 1;
-    bool anyLens = false; // (one decision per step: the table is copied before the launches are put together)
-    for (int j = 0; j < nInjectedSegs; ++j) anyLens = anyLens || tbl.seg[injectedSegs[j]].pp.aperture_radius > 1e-30f;
-    for (int j = 0; j < nInjectedSegs; ++j)
-        if (packetsNow && (!anyLens || cfg.collectStats)) tbl.seg[injectedSegs[j]].listed = 1; // (the kernels with the endings: hr_raygen.hip, launchRaygenPackets)
-    tbl.hostCameraCount = corunNow ? G.dCounts + (size_t)kTableRing * kMaxSegs : nullptr;
-    tbl.probe = c->dProbe, tbl.hostProbe = (g == 0 && (c->probePending || probeSeg >= 0)) ? G.dProbeHost + 8 * ring : nullptr; // (reported only while a probe is awaited)
-    G.countN[ring] = n;
-    tbl.hostCounts = G.dCounts + (size_t)ring * kMaxSegs, tbl.hostSeq = G.dSeq + ring, tbl.seqValue = stepIdx + 1ull;
-    tbl.stepLog = c->dStepLog, tbl.nInjectedNow = (uint32_t)nInjected, tbl.group = (uint32_t)g;
+    if (S.nInjectedSegs > 0) tbl.primaryFromSeg = S.injectedSegs[0]; // (the table is in pass order: the passes injected now are its last entries)
+    G.countN[S.ring] = n;
+    tbl.hostCounts = G.dCounts + (size_t)S.ring * kMaxSegs, tbl.hostSeq = G.dSeq + S.ring, tbl.seqValue = S.stepIdx + 1ull;
+    tbl.stepLog = c->dStepLog, tbl.nInjectedNow = (uint32_t)S.nInjected, tbl.group = (uint32_t)S.g;
     tbl.hostOverflow = c->dOverflowHost;
-    StepTable *dTbl = G.dTables + ring;
-    const size_t tblBytes = offsetof(StepTable, seg) + (size_t)n * sizeof(SegDev);
-    if (dbgT) tD = nowUs();
-    launchFetchTable(G.stream, G.dTablesHost + ring, dTbl, (tblBytes + 15) & ~(size_t)15);
-    if (dbgT) tE = nowUs();
-    HIP_TRY(c, hipEventRecord(G.tableCopied[ring], G.stream));
-    G.tableUsed[ring] = true;
-    if (c->pending.size() > 8192) c->drainTimes();
-    bool timing = false; // (the kernels of a step are enqueued back to back: n + 1 timing events for n kernels)
-    bool forked = false;
-    for (int j0 = 0; j0 < nInjectedSegs;) { // one launch for the passes injected this step
-        // (as packets: ray generation and the camera rays' traversal in one launch per group of 16, 8, 4, 2, 1 passes — the bucket
-        // HR_KERNEL_RAYGEN then holds both, HR_KERNEL_TRACE and the step's device clock stay k_trace's own)
+    return HR_OK;
+}
+
+// stage 7, the packet selector (hr_ctx::PacketSelector): do the injected passes' camera rays travel as packets (k_raygen_packets), beside
+// k_trace or in front of it, and does this step carry a probe?  One decision per step: the table is copied before the launches are put together.
+static void decidePackets(hr_ctx *c, StepPlan &S)
+{
+    hr_ctx::PacketSelector &sel = c->selector;
+    StepTable &tbl = S.G->hTables[S.ring];
+    const hr_pass_params *first = S.nInjectedSegs > 0 ? &tbl.seg[S.injectedSegs[0]].pp : nullptr;
+    S.packetsNow = sel.packetsInUse(c->tune) && first && first->interactive_mode == 0; // (interactive sub-passes of one sample share no pixels)
+    S.probeSeg = (S.g == 0 && first && sel.wantsProbe(*first, c->tune)) ? S.injectedSegs[0] : -1;
+    S.corunNow = S.packetsNow && (c->tune.corun == 2 || (c->tune.corun == 1 && sel.lastOwnPerRay >= (double)c->tune.cmin));
+    S.anyLens = false;
+    for (int j = 0; j < S.nInjectedSegs; ++j) S.anyLens = S.anyLens || tbl.seg[S.injectedSegs[j]].pp.aperture_radius > 1e-30f;
+    for (int j = 0; j < S.nInjectedSegs && S.packetsNow; ++j) {
+        SegDev &sg = tbl.seg[S.injectedSegs[j]];
+        sg.packets = S.corunNow ? 2 : 1;
+        if (!S.anyLens || S.cfg.collectStats) sg.listed = 1; // (the kernels with the endings: hr_raygen.hip, launchRaygenPackets)
+    }
+    tbl.hostCameraCount = S.corunNow ? S.G->dCounts + (size_t)kTableRing * kMaxSegs : nullptr;
+    tbl.probe = sel.dProbe, tbl.hostProbe = (S.g == 0 && (sel.probePending || S.probeSeg >= 0)) ? S.G->dProbeHost + 8 * S.ring : nullptr; // (reported only while a probe is awaited)
+}
+
+// stage 8a: one launch for the passes injected this step
+// (as packets: ray generation and the camera rays' traversal in one launch per group of 16, 8, 4, 2, 1 passes — the bucket
+// HR_KERNEL_RAYGEN then holds both, HR_KERNEL_TRACE and the step's device clock stay k_trace's own)
+static int launchCameraRays(hr_ctx *c, const StepPlan &S, bool &timing, bool &forked)
+{
+    hr_ctx::Group &G = *S.G;
+    const StepTable &tbl = G.hTables[S.ring];
+    StepTable *dTbl = G.dTables + S.ring;
+    for (int j0 = 0; j0 < S.nInjectedSegs;) {
         int take = 1;
-        if (packetsNow)
-            while (2 * take <= nInjectedSegs - j0 && 2 * take <= kMaxBatch) take *= 2;
+        if (S.packetsNow)
+            while (2 * take <= S.nInjectedSegs - j0 && 2 * take <= kMaxBatch) take *= 2;
         else
-            take = nInjectedSegs - j0 < kMaxBatch ? nInjectedSegs - j0 : kMaxBatch;
+            take = S.nInjectedSegs - j0 < kMaxBatch ? S.nInjectedSegs - j0 : kMaxBatch;
         SegList segs{};
-        for (int j = j0; j < j0 + take; ++j) segs.seg[segs.n++] = injectedSegs[j];
+        for (int j = j0; j < j0 + take; ++j) segs.seg[segs.n++] = S.injectedSegs[j];
         j0 += take;
-        bool uniformParams = packetsNow;
+        bool uniformParams = S.packetsNow;
         for (int j = 1; j < segs.n && uniformParams; ++j) { // (the usual batch: one camera, one set of options, consecutive sample indices)
             hr_pass_params a = tbl.seg[segs.seg[0]].pp, b = tbl.seg[segs.seg[j]].pp;
             a.sample_index = b.sample_index = 0;
             uniformParams = std::memcmp(&a, &b, sizeof(a)) == 0;
         }
-        LaunchCfg cfgP = cfg; // (a step with a lens: none of its packets has one origin, none can take the interval step)
-        if (anyLens) cfgP.packetStep = 0, cfgP.packetLens = true; // (k_raygen_packets_rays<.., false>, whose hits k_shade_sort lists: `listed` above)
-        if (corunNow) { // beside k_trace: fork after the table copy, join before the shading kernels
+        LaunchCfg cfgP = S.cfg; // (a step with a lens: none of its packets has one origin, none can take the interval step)
+        if (S.anyLens) cfgP.packetStep = 0, cfgP.packetLens = true; // (k_raygen_packets_rays<.., false>, whose hits k_shade_sort lists: `listed` above)
+        if (S.corunNow) { // beside k_trace: fork after the table copy, join before the shading kernels
             LaunchCfg cb = cfgP;
             cb.stream = G.streamB;
             if (!forked) {
@@ -532,7 +560,7 @@ static int macroStep(hr_ctx *c, int g, int nInject)
                 HIP_TRY(c, hipStreamWaitEvent(G.streamB, G.evFork, 0));
                 forked = true;
             }
-            launchRaygenPackets(cb, c->dScene, c->nodes, c->tris, dTbl, segs, fr, c->dStats, uniformParams);
+            launchRaygenPackets(cb, c->dScene, c->nodes, c->tris, dTbl, segs, S.fr, c->dStats, uniformParams);
             continue;
         }
         if (timing)
@@ -540,52 +568,88 @@ static int macroStep(hr_ctx *c, int g, int nInject)
         else
             c->timeBegin(HR_KERNEL_RAYGEN, G.stream);
         timing = true;
-        if (packetsNow)
-            launchRaygenPackets(cfgP, c->dScene, c->nodes, c->tris, dTbl, segs, fr, c->dStats, uniformParams);
+        if (S.packetsNow)
+            launchRaygenPackets(cfgP, c->dScene, c->nodes, c->tris, dTbl, segs, S.fr, c->dStats, uniformParams);
         else
-            launchRaygen(cfg, c->dScene, dTbl, segs, fr, c->dStats);
+            launchRaygen(S.cfg, c->dScene, dTbl, segs, S.fr, c->dStats);
     }
     if (forked) HIP_TRY(c, hipEventRecord(G.evJoin, G.streamB));
+    return HR_OK;
+}
+// stage 8b: the step's probe, on the selector's side stream
+static int launchProbe(hr_ctx *c, const StepPlan &S)
+{
+    hr_ctx::PacketSelector &sel = c->selector;
+    // (probeSeen holds the totals of the report the previous decision was taken on: probes never overlap, that probe was complete)
+    HIP_TRY(c, hipEventRecord(sel.evProbeA, S.G->stream));
+    HIP_TRY(c, hipStreamWaitEvent(sel.probeStream, sel.evProbeA, 0));
+    sel.probeWaves = (unsigned long long)launchPacketProbe(sel.probeStream, c->dScene, c->nodes, c->tris, S.G->hTables[S.ring].seg[S.probeSeg].pp, c->tune.plog >= 0 ? c->tune.plog : hr_ctx::PacketSelector::packetLog2(c->injectBatch), S.fr, sel.dProbe, c->tune.pprobe != 0);
+    HIP_TRY(c, hipEventRecord(sel.evProbeB, sel.probeStream));
+    sel.probeGuard = true, sel.probePending = true, sel.probeStep = S.stepIdx, sel.probeCountdown = hr_ctx::PacketSelector::kProbeEvery;
+    return HR_OK;
+}
+// k_trace's workgroups per CU while the step's packet kernel runs beside it: the camera rays of this step (what the passes injected before
+// sent through the root cull, or half the pixels while unknown) against the rays k_trace carries (two per entry of the closest-hit
+// queues' bounds: the ray and its occlusion ray)
+static int corunTraceBlocks(hr_ctx *c, const StepPlan &S)
+{
+    uint32_t &lastCameraCount = c->selector.lastCameraCount;
+    double others = 0.0;
+    for (int k = 0; k < S.n; ++k)
+        if (c->slots[S.order[k]].step > 0) others += 2.0 * (double)((c->slots[S.order[k]].step == 1 && lastCameraCount && S.boundIn[k] > lastCameraCount) ? lastCameraCount : S.boundIn[k]);
+    const uint32_t late = ((volatile uint32_t *)S.G->hCounts)[(size_t)kTableRing * kMaxSegs]; // (k_shade_sort's hint: camera rays per pass behind the root cull)
+    if (late) lastCameraCount = late;
+    const double cam = (double)S.nInjectedSegs * (double)(lastCameraCount ? lastCameraCount : S.P / 2u);
+    const int blocks = cam > 0.2 * others ? 3 : 4;
+    return c->tune.cblocks > 0 ? c->tune.cblocks : blocks;
+}
+// stage 8: the launches — table fetch, camera rays, probe, k_trace, shading — and their timing buckets
+static int launchStep(hr_ctx *c, const StepPlan &S, StepClock &clk)
+{
+    hr_ctx::Group &G = *S.G;
+    StepTable *dTbl = G.dTables + S.ring;
+    const size_t tblBytes = offsetof(StepTable, seg) + (size_t)S.n * sizeof(SegDev);
+    launchFetchTable(G.stream, G.dTablesHost + S.ring, dTbl, (tblBytes + 15) & ~(size_t)15);
+    clk.mark();
+    HIP_TRY(c, hipEventRecord(G.tableCopied[S.ring], G.stream));
+    G.tableUsed[S.ring] = true;
+    if (c->pending.size() > 8192) c->drainTimes();
+    bool timing = false; // (the kernels of a step are enqueued back to back: n + 1 timing events for n kernels)
+    bool forked = false;
+    int rc = launchCameraRays(c, S, timing, forked);
+    if (rc) return rc;
     if (timing)
         c->timeNext(HR_KERNEL_TRACE, G.stream);
     else
         c->timeBegin(HR_KERNEL_TRACE, G.stream);
-    if (probeSeg >= 0) {
-        // (probeSeen holds the totals of the report the previous decision was taken on: probes never overlap, that probe was complete)
-        HIP_TRY(c, hipEventRecord(c->evProbeA, G.stream));
-        HIP_TRY(c, hipStreamWaitEvent(c->probeStream, c->evProbeA, 0));
-        c->probeWaves = (unsigned long long)launchPacketProbe(c->probeStream, c->dScene, c->nodes, c->tris, tbl.seg[probeSeg].pp, c->tune.plog >= 0 ? c->tune.plog : packetLog2(c), fr, c->dProbe, c->tune.pprobe != 0);
-        HIP_TRY(c, hipEventRecord(c->evProbeB, c->probeStream));
-        c->probeGuard = true, c->probePending = true, c->probeStep = stepIdx, c->probeCountdown = kProbeEvery;
+    if (S.probeSeg >= 0) {
+        rc = launchProbe(c, S);
+        if (rc) return rc;
     }
-    {
-        LaunchCfg ct = cfg;
-        if (forked) {
-            // camera rays of this step (what the passes injected before sent through the root cull, or half the pixels while unknown)
-            // against the rays k_trace carries (two per entry of the closest-hit queues' bounds: the ray and its occlusion ray)
-            double others = 0.0;
-            for (int k = 0; k < n; ++k)
-                if (c->slots[order[k]].step > 0) others += 2.0 * (double)((c->slots[order[k]].step == 1 && c->lastCameraCount && boundIn[k] > c->lastCameraCount) ? c->lastCameraCount : boundIn[k]);
-            const uint32_t late = ((volatile uint32_t *)G.hCounts)[(size_t)kTableRing * kMaxSegs]; // (k_shade_sort's hint: camera rays per pass behind the root cull)
-            if (late) c->lastCameraCount = late;
-            const double cam = (double)nInjectedSegs * (double)(c->lastCameraCount ? c->lastCameraCount : P / 2u);
-            int blocks = cam > 0.2 * others ? 3 : 4;
-            if (c->tune.cblocks > 0) blocks = c->tune.cblocks;
-            if (blocks < ct.traceBlocksPerCU) ct.traceBlocksPerCU = blocks;
-        }
-        launchTrace(ct, c->dScene, c->tree.leafKeys, c->tree.nodes32, c->tris, dTbl, c->dStats);
+    LaunchCfg ct = S.cfg;
+    if (forked) {
+        const int blocks = corunTraceBlocks(c, S);
+        if (blocks < ct.traceBlocksPerCU) ct.traceBlocksPerCU = blocks;
     }
+    launchTrace(ct, c->dScene, c->tree.leafKeys, c->tree.nodes32, c->tris, dTbl, c->dStats);
     if (forked) { // (the bucket HR_KERNEL_TRACE stays k_trace's own launch; what the packet kernel beside it runs longer is booked as ray generation)
         c->timeNext(HR_KERNEL_RAYGEN, G.stream);
         HIP_TRY(c, hipStreamWaitEvent(G.stream, G.evJoin, 0));
     }
     c->timeNext(HR_KERNEL_SHADE, G.stream);
-    launchShade(cfg, c->dScene, dTbl, c->dStats);
+    launchShade(S.cfg, c->dScene, dTbl, c->dStats);
     c->timeEnd(G.stream);
+    return HR_OK;
+}
+
+// stage 9: every pass is a stage further or, past its last, finished; in pass-through scenes the snapshot endDrainedPassthrough reads
+static int advancePasses(hr_ctx *c, const StepPlan &S)
+{
+    hr_ctx::Group &G = *S.G;
     hr_ctx::PassSlot *ended[kMaxSegs];
     int nEnded = 0;
-    for (int k = 0; k < n; ++k) {
-        hr_ctx::PassSlot &ps = c->slots[order[k]];
+    for (int k = 0; k < S.n; ++k) {
+        hr_ctx::PassSlot &ps = c->slots[S.order[k]];
         if (!c->hasPassthrough && ps.step >= ps.nIter) {
             ps.active = false, ps.finished = true;
             ended[nEnded++] = &ps;
@@ -596,16 +660,51 @@ static int macroStep(hr_ctx *c, int g, int nInject)
     if (nEnded > 0) HIP_TRY(c, hipEventRecord(ended[nEnded - 1]->evFinal, G.stream)); // one event for the passes whose last stage this step was
     for (int k = 0; k < nEnded; ++k) ended[k]->finalEv = ended[nEnded - 1]->evFinal;
     if (c->hasPassthrough) { // snapshot of the queue lengths after this step, read two steps from now
-        uint32_t *dst = G.hQCount + (size_t)ring * kMaxSlots * kMaxBounceSlots;
+        uint32_t *dst = G.hQCount + (size_t)S.ring * kMaxSlots * kMaxBounceSlots;
         HIP_TRY(c, hipMemcpy2DAsync(dst, sizeof(uint32_t) * kMaxBounceSlots, &c->dCounters[0].qCount[0], sizeof(Counters),
                                     sizeof(uint32_t) * kMaxBounceSlots, kMaxSlots, hipMemcpyDeviceToHost, G.stream));
-        HIP_TRY(c, hipEventRecord(G.statusEv[ring], G.stream));
-        G.statusUsed[ring] = true;
+        HIP_TRY(c, hipEventRecord(G.statusEv[S.ring], G.stream));
+        G.statusUsed[S.ring] = true;
         for (int i = 0; i < kMaxSlots; ++i)
-            G.statusOrder[ring][i] = (c->slots[i].active && c->slots[i].group == g) ? c->slots[i].order + 1ull : 0ull;
+            G.statusOrder[S.ring][i] = (c->slots[i].active && c->slots[i].group == S.g) ? c->slots[i].order + 1ull : 0ull;
     }
+    return HR_OK;
+}
+
+static int macroStep(hr_ctx *c, int g, int nInject)
+{
+    StepClock clk{c->tune.debugStepTimes, {0, 0, 0, 0, 0}, 0};
+    clk.mark();
+    StepPlan S;
+    hr_ctx::Group &G = c->groups[g];
+    S.g = g, S.G = &G;
+    S.cfg = c->cfg(G.stream);
+    S.fr = c->frame, S.fr.fb = c->fb();
+    int rc = injectPasses(c, S, nInject);
+    if (rc == HR_OK) rc = endDrainedPassthrough(c, S);
+    if (rc) return rc;
+    clk.mark();
+    listInFlight(c, S);
+    if (S.n == 0) return resolveReady(c);
+    if (S.n > kMaxSegs) FAIL(c, HR_ERR_INVALID, "internal: too many passes in one group");
+    S.stepIdx = G.stepCounter++;
+    S.ring = (int)(S.stepIdx % kTableRing);
+    if (G.tableUsed[S.ring]) HIP_TRY(c, hipEventSynchronize(G.tableCopied[S.ring])); // staging entry free again (4 steps old)
+    S.P = c->tune.ovf == 1 ? c->queueCapacity / 8u + 1u : (c->queueCapacity ? c->queueCapacity : 1u); // (ovf=1, TEST ONLY: camera rays do not fit)
+    S.kS = c->allLightsUsed ? 4 : 1;
+    rc = boundQueues(c, S);
+    if (rc) return rc;
+    clk.mark();
+    rc = sizeStepMemory(c, S);
+    if (rc == HR_OK) rc = buildTable(c, S);
+    if (rc) return rc;
+    decidePackets(c, S);
+    clk.mark();
+    rc = launchStep(c, S, clk);
+    if (rc == HR_OK) rc = advancePasses(c, S);
+    if (rc) return rc;
     HIP_TRY(c, hipGetLastError());
-    if (dbgT) fprintf(stderr, "step %llu (inject %d): begin %.1f us | injected +%.1f | counts known +%.1f | table built +%.1f | copy enqueued +%.1f | launched +%.1f\n", stepIdx, nInject, tA, tB - tA, tC - tB, tD - tC, tE - tD, nowUs() - tE);
+    clk.print(S.stepIdx, nInject);
     return resolveReady(c);
 }
 
@@ -639,23 +738,6 @@ static int injectBatch(hr_ctx *c, int n, int perGroupLimit)
     return macroStep(c, g, n);
 }
 
-// Passes injected together when their camera rays travel as packets: a wave holds 2^k passes of 64 >> k pixels (hr_raygen.hip:
-// k_raygen_packets), so the batch is the power of two next to the usual one (12 -> 16, 3 -> 4, 5 -> 4), sixteen per launch at most.
-static int packetBatch(const hr_ctx *c)
-{
-    const int b = c->injectBatch < 1 ? 1 : c->injectBatch;
-    int up = 1;
-    while (up < b) up <<= 1;
-    return (4 * b >= 3 * up) ? up : up / 2;
-}
-static int packetLog2(const hr_ctx *c)
-{
-    int k = 0;
-    while ((2 << k) <= packetBatch(c) && k < 4) ++k;
-    return k;
-}
-static bool packetsInUse(const hr_ctx *c) { return c->tune.packets == 1 || (c->tune.packets == 2 && c->packetsOn); }
-
 // hr_ctx_desc::memory_budget: how many passes per step fit.  A pass of the batch holds, over the `stages` steps of its life, a pass buffer
 // (S + 2 of them per batch pass are kept: the pipeline's depth and the resolve lag), its camera rays and hit records (scratch), and
 // what each of its closest-hit stages emits (arena: two halves, each with a third of headroom).  A stage that has not been seen yet
@@ -668,8 +750,9 @@ static double budgetBytesPerPass(const hr_ctx *c, int stages)
     const double fb = (double)c->W * c->H * 16.0 * ((c->allLightsUsed ? 4.0 : 1.0) + (double)c->aov.framesPerSlot());
     double arena = 0.0, scratch = 0.0;
     for (int st = 0; st + 1 < stages && st < kMaxBounceSlots; ++st) { // (the last stage traces occlusion rays only)
-        arena += c->stageSeen[st] ? 1.1 * c->stageArenaSeen[st] : P * (64.0 + 48.0 * kS);
-        scratch += c->stageSeen[st] ? 1.1 * c->stageScratchSeen[st] : P * 20.0 + (st == 0 ? P * 64.0 : 0.0);
+        const hr_ctx::BudgetSeen &seen = c->budgetSeen; // (the guarantee: unaligned and in double, hr_step_memory.h)
+        arena += seen.stageSeen[st] ? 1.1 * seen.stageArenaSeen[st] : guaranteedArenaBytes(P, kS);
+        scratch += seen.stageSeen[st] ? 1.1 * seen.stageScratchSeen[st] : guaranteedScratchBytes(P, hitRecordSize(), st == 0);
     }
     return (double)c->nGroups * ((double)(stages + 2) * fb + (4.0 / 3.0) * (2.0 * arena + scratch));
 }
@@ -682,11 +765,11 @@ static int budgetBatch(const hr_ctx *c, int stages)
 
 static int batchFor(const hr_ctx *c, int stages)
 {
-    int batch = packetsInUse(c) ? packetBatch(c) : c->injectBatch;
+    int batch = c->selector.packetsInUse(c->tune) ? hr_ctx::PacketSelector::packetBatch(c->injectBatch) : c->injectBatch;
     const int fit = budgetBatch(c, stages);
     if (batch > fit) {
         batch = fit;
-        if (packetsInUse(c)) // (a packet holds a power of two of passes)
+        if (c->selector.packetsInUse(c->tune)) // (a packet holds a power of two of passes)
             while (batch & (batch - 1)) batch &= batch - 1;
     }
     int perGroup = slotLimit(c) / c->nGroups;
@@ -712,7 +795,7 @@ static int drainPipeline(hr_ctx *c)
         // where its (smaller, less coherent) packets run beside the k_trace that carries the first launches' first bounce instead of
         // lengthening the step that has nothing beside it.  A 1/8 shard's 20 passes as 16, then 4: 0.304 -> 0.294 ms/step; as 12 + 8,
         // 10 + 10, 8 + 8 + 4 (each of them smaller packets all round): 0.307 - 0.323 (profiles/r5g_burst_pmin.txt).
-        if (packetsInUse(c) && n > kMaxBatch && n % kMaxBatch) n -= n % kMaxBatch;
+        if (c->selector.packetsInUse(c->tune) && n > kMaxBatch && n % kMaxBatch) n -= n % kMaxBatch;
         int perGroup = batch * stages;
         int rc = injectBatch(c, n, perGroup);
         if (rc) return rc;
@@ -727,9 +810,9 @@ static int drainPipeline(hr_ctx *c)
     if (rc) return rc;
     if (occupiedSlots(c) > 0) FAIL(c, HR_ERR_DEVICE, "internal: finished passes left unresolved");
     c->oldestWaitingNs = 0;
-    if (c->probeGuard) { // (a probe nobody has waited for: whatever follows on the caller's stream — frees after a synchronise included — comes after it)
-        HIP_TRY(c, hipStreamWaitEvent(c->stream, c->evProbeB, 0));
-        c->probeGuard = false;
+    if (c->selector.probeGuard) { // (a probe nobody has waited for: whatever follows on the caller's stream — frees after a synchronise included — comes after it)
+        HIP_TRY(c, hipStreamWaitEvent(c->stream, c->selector.evProbeB, 0));
+        c->selector.probeGuard = false;
     }
     // whatever the caller does next on its stream (clear, scene edits, new tables) has to be seen by the groups
     for (int g = 0; g < kMaxGroups; ++g) c->groups[g].needUserSync = true;
@@ -876,8 +959,8 @@ int hr_get_kernel_times(hr_ctx *c, hr_kernel_times *out)
     for (const Stats &p : parts) ticks += p.traceTicks, launches += p.traceLaunches;
     out->trace_clock_ms = (float)((double)ticks * 1e-5); // 100 MHz: 10 ns per tick
     out->trace_clock_launches = (uint32_t)launches;
-    out->camera_packets = packetsInUse(c) ? (uint32_t)packetBatch(c) : 0u;
-    out->packet_union = (float)c->lastUnion;
+    out->camera_packets = c->selector.packetsInUse(c->tune) ? (uint32_t)hr_ctx::PacketSelector::packetBatch(c->injectBatch) : 0u;
+    out->packet_union = (float)c->selector.lastUnion;
     return HR_OK;
 }
 

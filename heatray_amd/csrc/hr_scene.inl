@@ -490,8 +490,8 @@ int hr_scene_commit(hr_ctx *c)
     HIP_TRY(c, hipEventSynchronize(cs.e1));
     hipEventElapsedTime(&c->info.build_ms, cs.e0, cs.e1);
     c->committed = true;
-    std::memset(c->stageSeen, 0, sizeof(c->stageSeen)); // (memory budget: another scene, other queue lengths)
-    c->probeCountdown = 0; // (packet selector: another tree)
+    c->budgetSeen.forget(); // (memory budget: another scene, other queue lengths)
+    c->selector.sceneOrSizeChanged(); // (another tree)
     c->sceneDirty = true;
     c->texDensityStale = true;
     c->topologyDirty = false, c->transformDirty = false;
