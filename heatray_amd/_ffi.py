@@ -378,6 +378,37 @@ class MeshResult(C.Structure):
         return {k: getattr(self, k) for k, _ in self._fields_}
 
 
+# every symbol include/hrcore_deform.h declares (deformable meshes: vertex updates in place, device posing, attribute read-back).
+# Resolved lazily like the AOV symbols
+HR_DEFORM_API_VERSION = 1
+(HR_GEOM_POSITIONS, HR_GEOM_NORMALS, HR_GEOM_UVS, HR_GEOM_TANGENTS, HR_GEOM_BITANGENTS, HR_GEOM_COLORS) = range(6)
+HR_DEFORM_NORMALS, HR_DEFORM_TANGENTS = 1, 2
+HR_DEFORM_MAX_MORPH, HR_DEFORM_MAX_JOINTS = 8, 1024
+DEFORM_SYMBOLS = ["deform_api_version", "deform_default_params", "geom_update", "geom_get_attribute", "deform_bind", "deform_pose", "deform_unbind", "deform_last"]
+
+
+class DeformParams(C.Structure):
+    """hr_deform_params"""
+    _fields_ = [("regenerate", C.c_int32), ("weight", C.c_int32), ("weld", C.c_int32), ("reserved", C.c_int32 * 5)]
+
+
+class DeformRig(C.Structure):
+    """hr_deform_rig"""
+    _fields_ = [("morph_positions", f32p), ("morph_normals", f32p), ("joints", u32p), ("weights", f32p), ("n_morph", C.c_int32), ("n_joints", C.c_int32),
+                ("reserved", C.c_int32 * 6)]
+
+
+class DeformResult(C.Structure):
+    """hr_deform_result"""
+    _fields_ = [("vertices", C.c_uint64), ("triangles", C.c_uint64), ("rejected_vertices", C.c_uint64), ("kept_directions", C.c_uint64),
+                ("regenerated", C.c_uint32), ("posed", C.c_uint32), ("mesh", MeshResult)]
+
+    def as_dict(self):
+        d = {k: getattr(self, k) for k, _ in self._fields_ if k != "mesh"}
+        d["mesh"] = self.mesh.as_dict()
+        return d
+
+
 # The optional headers: feature ->(its symbols, the version the binding was written against, what "this library has no ..." calls it);
 # the version function is <feature>_api_version.  Engine._feature_call checks a feature on its first call
 FEATURES = {
@@ -392,6 +423,7 @@ FEATURES = {
     "metric": (METRIC_SYMBOLS, HR_METRIC_API_VERSION, "convergence metric"),
     "despeckle": (DESPECKLE_SYMBOLS, HR_DESPECKLE_API_VERSION, "firefly suppression"),
     "mesh": (MESH_SYMBOLS, HR_MESH_API_VERSION, "mesh preparation"),
+    "deform": (DEFORM_SYMBOLS, HR_DEFORM_API_VERSION, "deformable meshes"),
 }
 
 
@@ -409,6 +441,17 @@ def _f32(a):
 
 def _ptr(a, typ=f32p):
     return a.ctypes.data_as(typ) if a is not None else typ()
+
+
+def _strided(a, comps):
+    """(the array as the C-ABI can read it, its stride in bytes): a float32 V x comps array whose last axis is contiguous goes as it
+    is, stride included; anything else is packed tight.  None -> (None, 0)."""
+    if a is None:
+        return None, 0
+    a = np.asarray(a)
+    if a.dtype != np.float32 or a.ndim != 2 or a.shape[1] != comps or a.strides[1] != 4 or a.strides[0] < 4 * comps:
+        a = _f32(a).reshape(-1, comps)
+    return a, a.strides[0]
 
 
 class Engine:
@@ -508,6 +551,7 @@ class Engine:
         d.front_face_cw, d.is_occluder, d.material_id = int(front_face_cw), int(is_occluder), material_id
         gid = C.c_int32()
         self._call("geom_add", C.byref(d), C.byref(gid))
+        self.__dict__.setdefault("_mesh_vertices", {})[gid.value] = d.n_vertices  # (mesh_attribute sizes its output by it)
         return gid.value
 
     def add_mesh_strided(self, buf, pos_off, nrm_off, uv_off, stride_floats, indices, mode=HR_TRIANGLES, world=None, is_occluder=True,
@@ -529,10 +573,13 @@ class Engine:
         d.front_face_cw, d.is_occluder, d.material_id = int(np.linalg.det(m.astype(np.float64)) < 0), int(is_occluder), material_id
         gid = C.c_int32(-1)
         self._call("geom_add", C.byref(d), C.byref(gid))
+        self.__dict__.setdefault("_mesh_vertices", {})[gid.value] = d.n_vertices
         return gid.value
 
     def remove_mesh(self, gid):
         self._call("geom_remove", C.c_int32(gid))
+        for notes in ("_mesh_vertices", "_deform_rigs"):  # (what mesh_attribute and deform_pose remember of a mesh)
+            self.__dict__.setdefault(notes, {}).pop(gid, None)
 
     def set_transform(self, gid, world):
         m = _f32(world).reshape(4, 4)
@@ -540,6 +587,8 @@ class Engine:
 
     def clear_scene(self):
         self._call("scene_clear")
+        for notes in ("_mesh_vertices", "_deform_rigs"):
+            self.__dict__.setdefault(notes, {}).clear()
 
     def set_scene_cache(self, path):
         self._call("scene_cache", None if not path else str(path).encode())
@@ -1038,6 +1087,72 @@ class Engine:
         """The last successful prepare_mesh's MeshResult as a dict."""
         r = MeshResult()
         self._feature_call("mesh", "mesh_last", C.byref(r))
+        return r.as_dict()
+
+    # -- deformable meshes (include/hrcore_deform.h)
+    def update_mesh(self, gid, positions, normals=None, uvs=None, tangents=None, bitangents=None, colors=None, params=None, with_result=False):
+        """New vertex data for mesh `gid`, in its device block: positions (V x 3) and whichever other attributes are given; None leaves
+        an attribute as it is.  Strided arrays go as they are (the last axis contiguous).  params: a DeformParams
+        (heatray_amd.deform.params(regenerate=...)), None = the defaults.  The scene needs a commit afterwards: it refits.
+        with_result: the DeformResult as a dict."""
+        arrays = [_strided(a, comps) for a, comps in zip((positions, normals, uvs, tangents, bitangents, colors), (3, 3, 2, 3, 3, 3))]
+        d = MeshDesc()
+        d.positions, d.normals, d.uvs, d.tangents, d.bitangents, d.colors = (_ptr(a) for a, _ in arrays)
+        d.position_stride, d.normal_stride, d.uv_stride, d.tangent_stride, d.bitangent_stride, d.color_stride = (s for _, s in arrays)
+        d.n_vertices = arrays[0][0].shape[0]
+        r = DeformResult()
+        self._feature_call("deform", "geom_update", C.c_int32(gid), C.byref(d), C.byref(params) if params is not None else None, C.byref(r))
+        self.__dict__.setdefault("_mesh_vertices", {})[gid] = d.n_vertices
+        return r.as_dict() if with_result else None
+
+    def mesh_attribute(self, gid, attribute, n_vertices=None):
+        """Attribute HR_GEOM_* of mesh `gid` as the device block holds it: V x 3 float32 (V x 2 for uvs).  The C call does not say how
+        many vertices the mesh has: add_mesh, add_mesh_strided and update_mesh remember it; n_vertices names it for any other mesh."""
+        V = n_vertices if n_vertices is not None else self.__dict__.setdefault("_mesh_vertices", {}).get(gid)
+        if V is None:
+            # (an id this engine does not know: the library names the cause, if the call fails; else the count is missing)
+            self._feature_call("deform", "geom_get_attribute", C.c_int32(gid), C.c_int32(attribute), f32p())
+            raise ValueError(f"mesh_attribute: give n_vertices for mesh {gid}")
+        out = np.empty((V, 2 if attribute == HR_GEOM_UVS else 3), dtype=np.float32)
+        self._feature_call("deform", "geom_get_attribute", C.c_int32(gid), C.c_int32(attribute), _ptr(out))
+        return out
+
+    def deform_bind(self, gid, morph_positions=None, morph_normals=None, joints=None, weights=None, n_joints=None):
+        """The mesh as it stands becomes the rest pose of a rig: morph_positions / morph_normals K x V x 3 deltas, joints V x 4 indices
+        and weights V x 4; n_joints: the rig's joint count, None = the highest index named + 1.  A second bind replaces the first."""
+        mp = None if morph_positions is None else _f32(morph_positions)
+        mn = None if morph_normals is None else _f32(morph_normals)
+        j = None if joints is None else np.ascontiguousarray(joints, dtype=np.uint32)
+        w = None if weights is None else _f32(weights)
+        rig = DeformRig()
+        rig.morph_positions, rig.morph_normals, rig.joints, rig.weights = _ptr(mp), _ptr(mn), _ptr(j, u32p), _ptr(w)
+        rig.n_morph = 0 if mp is None else mp.reshape(-1, *mp.shape[-2:]).shape[0]
+        if n_joints is None:
+            n_joints = 0 if j is None or not j.size else int(j.max()) + 1
+        rig.n_joints = n_joints
+        self._feature_call("deform", "deform_bind", C.c_int32(gid), C.byref(rig))
+        self.__dict__.setdefault("_deform_rigs", {})[gid] = (rig.n_morph, rig.n_joints)
+
+    def deform_pose(self, gid, morph_weights=None, joint_matrices=None, params=None, with_result=False):
+        """Pose the bound mesh `gid` on the device: morph_weights K floats, joint_matrices J x 4 x 4 (numpy's m[row][col]; the ABI's
+        column-major order is made here).  params as update_mesh's.  The scene needs a commit afterwards."""
+        mw = None if morph_weights is None else _f32(morph_weights).reshape(-1)
+        jm = None if joint_matrices is None else _f32(np.transpose(_f32(joint_matrices).reshape(-1, 4, 4), (0, 2, 1)))
+        K, J = self.__dict__.setdefault("_deform_rigs", {}).get(gid, (0, 0))  # (the library reads as many as the rig has)
+        if (mw is not None and mw.size < K) or (jm is not None and jm.shape[0] < J):
+            raise ValueError(f"deform_pose: mesh {gid} is bound to {K} morphs and {J} joints")
+        r = DeformResult()
+        self._feature_call("deform", "deform_pose", C.c_int32(gid), _ptr(mw), _ptr(jm), C.byref(params) if params is not None else None, C.byref(r))
+        return r.as_dict() if with_result else None
+
+    def deform_unbind(self, gid):
+        self._feature_call("deform", "deform_unbind", C.c_int32(gid))
+        self.__dict__.setdefault("_deform_rigs", {}).pop(gid, None)
+
+    def deform_last(self):
+        """The last successful update_mesh's or deform_pose's DeformResult as a dict."""
+        r = DeformResult()
+        self._feature_call("deform", "deform_last", C.byref(r))
         return r.as_dict()
 
     def debug_trace(self, origins, dirs, tmax=None, skip_prim=None, any_hit=False):

@@ -18,6 +18,7 @@
 //   hr_denoise_spatial.inl  the denoiser with a spatial variance estimate for pixels with few samples (include/hrcore_denoise_spatial.h)
 //   hr_despeckle.inl  firefly suppression: the outlier clamp the denoiser can be run behind (include/hrcore_despeckle.h)
 //   hr_mesh.inl       mesh preparation: smooth normals and tangent frames for a mesh without them (include/hrcore_mesh.h)
+//   hr_deform.inl     deformable meshes: vertex updates in place, device posing, read-back (include/hrcore_deform.h)
 //   hr_adaptive.inl   the sample mask and the error estimate that builds it (include/hrcore_adaptive.h)
 //   hr_history.inl    history reprojection across a camera change (include/hrcore_history.h)
 //   hr_reproject.inl  its progressive form and the preview of unsampled pixels (include/hrcore_reproject.h)
@@ -332,6 +333,7 @@ int hr_ctx_destroy(hr_ctx *c)
     hipFree(c->dDisplay);
     featuresDestroyed(c);
     c->meshReleaseAll();
+    for (Geom &g : c->geoms) deformRelease(g);
     for (int k = 0; k < 2; ++k) {
         if (c->stage[k]) hipHostFree(c->stage[k]);
         if (c->stageEv[k]) hipEventDestroy(c->stageEv[k]);
@@ -722,3 +724,6 @@ int hr_debug_trace(hr_ctx *c, int32_t n, const float *o, const float *d, const f
 
 // ------------------------------------------------------------------------------------------ mesh preparation
 #include "hr_mesh.inl"
+
+// ------------------------------------------------------------------------------------------ deformable meshes
+#include "hr_deform.inl"

@@ -35,6 +35,20 @@ struct Texture {
     bool alive = false;
 };
 
+// What hr_deform_bind keeps for a mesh (include/hrcore_deform.h): ONE device allocation cut into the rest pose's tight arrays, the rig's
+// arrays and a pose's weights and matrices.  Owned through Geom::deform, a plain pointer like Geom::chunk: a Geom is copied freely (the
+// vector grows, hr_geom_remove assigns Geom()), so nothing is freed by a destructor; deformRelease (hr_deform.inl) is called wherever
+// meshRelease or meshReleaseAll is, and by hr_deform_unbind and a second bind.
+struct DeformBinding {
+    char *dev = nullptr;
+    float *restP = nullptr, *restN = nullptr, *restT = nullptr, *restB = nullptr; // V x 3 each; restT / restB null without tangent frames
+    float *dP = nullptr, *dN = nullptr;                                         // nMorph x V x 3; dN null: normals are not morphed
+    uint32_t *joints = nullptr;                                                 // V x 4
+    float *weights = nullptr;                                                   // V x 4
+    float *pose = nullptr; // HR_DEFORM_MAX_MORPH morph weights, then nJoints x 16 matrix words: uploaded by every hr_deform_pose
+    int nMorph = 0, nJoints = 0;
+};
+
 // One submesh.  Its vertex attributes and indices live in ONE device block, uploaded when the mesh is added (straight from the
 // caller's planar buffers through a pinned staging ring, with the caller's strides: nothing is de-interleaved or kept on the host).
 struct Geom {
@@ -50,8 +64,18 @@ struct Geom {
     size_t off[7] = {0, 0, 0, 0, 0, 0, 0}; // byte offsets of pos, nrm, uv, tan, bit, col, idx in the block
     bool has[6] = {false, false, false, false, false, false};
     int stride[6] = {3, 3, 2, 3, 3, 3};     // floats between consecutive vertices
+    DeformBinding *deform = nullptr;        // hr_deform_bind's (null: not bound); see DeformBinding for who frees it
     uint32_t nTris() const { return mode == HR_TRIANGLE_STRIP ? (nIdx >= 3 ? nIdx - 2 : 0u) : nIdx / 3; }
 };
+
+// frees the mesh's binding, if it has one (hipFree waits for the kernels that still read it)
+inline void deformRelease(Geom &g)
+{
+    if (!g.deform) return;
+    hipFree(g.deform->dev);
+    delete g.deform;
+    g.deform = nullptr;
+}
 
 } // namespace
 
@@ -498,6 +522,7 @@ struct hr_ctx {
     MetricState metric;
     DespeckleState despeckle;
     MeshPrepState meshPrep;
+    DeformState deform;
     // Context group (include/hrcore_group.h): non-null when this handle is a group.  Its own fields then describe the ASSEMBLED frame on the
     // group's first device (W, H, frame, fbInternal, the read-back buffers) and `stream` is the assembly stream; no pass pipeline runs on it.
     GroupState *grp = nullptr;

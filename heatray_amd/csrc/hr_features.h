@@ -129,3 +129,12 @@ struct MeshPrepState {
     bool prepared = false;                       // ... there has been one (hr_mesh_last)
     void release() { hipFree(scratch), counters.free(), *this = MeshPrepState(); }
 };
+
+// Deformable meshes (include/hrcore_deform.h).  The bindings belong to their meshes (Geom::deform, hr_ctx.h); here are only the pose
+// kernel's two counters and the last result.  On a group's handle only `last` and `done` are used.
+struct DeformState {
+    ResultCounters<unsigned long long> counters; // kDfCounterWords
+    hr_deform_result last{};                     // the last successful hr_geom_update's or hr_deform_pose's result
+    bool done = false;                           // ... there has been one (hr_deform_last)
+    void release() { counters.free(), *this = DeformState(); }
+};

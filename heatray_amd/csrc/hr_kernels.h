@@ -14,6 +14,7 @@
 #include "../../include/hrcore_metric.h"
 #include "../../include/hrcore_despeckle.h"
 #include "../../include/hrcore_mesh.h"
+#include "../../include/hrcore_deform.h"
 
 #include <cstddef>
 
@@ -291,6 +292,31 @@ enum { kMsDegenerate = 0, kMsDegenerateUv = 1, kMsUnreferenced = 2, kMsCancelled
 static const size_t kMsCounterWords = 8;
 size_t meshSortBlocks(size_t n); // sort tiles of n keys
 void launchMeshPrepare(hipStream_t st, const MsBufs &b);
+
+// ---- hr_deform.hip (include/hrcore_deform.h)
+// Up to four attributes of V vertices between a mesh block (`strided`: `stride` floats from vertex to vertex) and tight arrays (`comps`
+// floats per vertex, 2 or 3): gather reads the strided side, scatter writes it.
+struct DfCopy {
+    float *strided[4], *tight[4];
+    int32_t stride[4], comps[4];
+    int32_t n; // attributes in use
+    uint32_t V;
+};
+// One hr_deform_pose: the binding's tight arrays in, tight arrays out.  restT / restB null: the mesh has no tangent frames.  dN null:
+// normals are not morphed.  pose: HR_DEFORM_MAX_MORPH morph weights, then nJoints x 16 matrix words.  outN / outT / outB null: not
+// written (outT and outB go together).  counters: {rejected vertices, kept directions}, zeroed by the caller.
+struct DfPoseArgs {
+    const float *restP, *restN, *restT, *restB, *dP, *dN, *weights, *pose;
+    const uint32_t *joints;
+    float *outP, *outN, *outT, *outB;
+    uint32_t V;
+    int32_t nMorph, nJoints;
+    unsigned long long *counters;
+};
+static const size_t kDfCounterWords = 2;
+void launchDeformGather(hipStream_t st, const DfCopy &s);
+void launchDeformScatter(hipStream_t st, const DfCopy &s);
+void launchDeformPose(hipStream_t st, const DfPoseArgs &s);
 
 // ---- hr_build.hip
 // Per-geometry descriptor for the assemble kernel; all pointers are device pointers.  Attributes are addressed with a stride

@@ -74,16 +74,13 @@ static const char *meshTight(const float *src, int32_t strideB, int comps, int n
     return (const char *)tmp.data();
 }
 
-// the device part, on a context that is no group; the inputs have passed meshCheck
-static int meshPrepareOn(hr_ctx *c, const hr_mesh_desc *d, const hr_mesh_params &p, uint64_t nTris, float *nOut, float *tOut, float *bOut, hr_mesh_result *res)
+// The scratch of one preparation of V vertices, T triangles and nIdx indices: one block cut in 256-byte steps, the context's own, grown
+// only; b's pointers are set into it (b.idx too: a caller whose indices are on the device already passes nIdx = 0 and points b.idx at
+// them).  `extraBytes` more are cut off behind it for the caller (hr_deform.inl's tight staging) and come back in *extra.
+static int meshScratch(hr_ctx *c, size_t V, size_t T, size_t nIdx, bool normals, bool tangents, size_t extraBytes, MsBufs *out, char **extra)
 {
-    HIP_TRY(c, hipSetDevice(c->device)); // (a group's member: the call arrives on its thread)
-    const bool normals = (p.want & HR_MESH_WANT_NORMALS) != 0, tangents = (p.want & HR_MESH_WANT_TANGENTS) != 0;
-    const size_t V = (size_t)d->n_vertices, T = (size_t)nTris, C = 3 * T, nIdx = (size_t)d->n_indices, S = C > V ? C : V;
-    MsBufs b{};
-    b.V = (uint32_t)V, b.T = (uint32_t)T, b.C = (uint32_t)C;
-    b.strip = d->mode == HR_TRIANGLE_STRIP, b.weight = p.weight, b.weld = p.weld, b.want = p.want;
-    // ---- the scratch: one block, cut in 256-byte steps
+    MsBufs &b = *out;
+    const size_t C = 3 * T, S = C > V ? C : V;
     size_t total = 0;
     const auto reserve = [&](size_t bytes) {
         const size_t at = total;
@@ -98,6 +95,7 @@ static int meshPrepareOn(hr_ctx *c, const hr_mesh_desc *d, const hr_mesh_params 
     const size_t oPerm = reserve(V * 4), oGroupOf = reserve(V * 4), oStart = reserve((V + 1) * 4), oScan = reserve(V * 4), oNG = reserve(4);
     const size_t oGN = reserve(V * 12), oGC = reserve(V);
     const size_t oOutN = reserve(normals ? V * 12 : 0), oOutT = reserve(tangents ? V * 12 : 0), oOutB = reserve(tangents ? V * 12 : 0);
+    const size_t oExtra = reserve(extraBytes);
     if (c->meshPrep.scratchBytes < total) {
         HIP_TRY(c, hipStreamSynchronize(c->stream)); // (an earlier call's kernels have been waited for; the ring's copies too)
         hipFree(c->meshPrep.scratch);
@@ -114,12 +112,30 @@ static int meshPrepareOn(hr_ctx *c, const hr_mesh_desc *d, const hr_mesh_params 
     b.vBegin = U32(oBegin), b.vEnd = U32(oEnd), b.vFirst = U32(oFirst), b.vS = F32(oS), b.vTa = F32(oTa), b.vBa = F32(oBa);
     b.perm = U32(oPerm), b.groupOf = U32(oGroupOf), b.groupStart = U32(oStart), b.scan = U32(oScan), b.nGroups = U32(oNG);
     b.gN = F32(oGN), b.gClass = (uint8_t *)(base + oGC), b.outN = F32(oOutN), b.outT = F32(oOutT), b.outB = F32(oOutB);
+    if (extra) *extra = base + oExtra;
+    return HR_OK;
+}
+
+// the device part, on a context that is no group; the inputs have passed meshCheck
+static int meshPrepareOn(hr_ctx *c, const hr_mesh_desc *d, const hr_mesh_params &p, uint64_t nTris, float *nOut, float *tOut, float *bOut, hr_mesh_result *res)
+{
+    HIP_TRY(c, hipSetDevice(c->device)); // (a group's member: the call arrives on its thread)
+    const bool normals = (p.want & HR_MESH_WANT_NORMALS) != 0, tangents = (p.want & HR_MESH_WANT_TANGENTS) != 0;
+    const size_t V = (size_t)d->n_vertices, T = (size_t)nTris, C = 3 * T, nIdx = (size_t)d->n_indices;
+    MsBufs b{};
+    b.V = (uint32_t)V, b.T = (uint32_t)T, b.C = (uint32_t)C;
+    b.strip = d->mode == HR_TRIANGLE_STRIP, b.weight = p.weight, b.weld = p.weld, b.want = p.want;
+    // ---- the scratch
+    const int src = meshScratch(c, V, T, nIdx, normals, tangents, 0, &b, nullptr);
+    if (src) return src;
+    float *const posAt = const_cast<float *>(b.pos), *const uvAt = const_cast<float *>(b.uv), *const nrmAt = const_cast<float *>(b.nrmIn);
+    uint32_t *const idxAt = const_cast<uint32_t *>(b.idx);
     // ---- uploads
     std::vector<float> tmp;
-    int rc = stagedUpload(c, base + oPos, meshTight(d->positions, d->position_stride, 3, (int)V, tmp), V * 12);
-    if (rc == HR_OK && tangents) rc = stagedUpload(c, base + oUv, meshTight(d->uvs, d->uv_stride, 2, (int)V, tmp), V * 8);
-    if (rc == HR_OK && tangents && !normals) rc = stagedUpload(c, base + oNrm, meshTight(d->normals, d->normal_stride, 3, (int)V, tmp), V * 12);
-    if (rc == HR_OK && nIdx) rc = stagedUpload(c, base + oIdx, (const char *)d->indices, nIdx * 4);
+    int rc = stagedUpload(c, (char *)posAt, meshTight(d->positions, d->position_stride, 3, (int)V, tmp), V * 12);
+    if (rc == HR_OK && tangents) rc = stagedUpload(c, (char *)uvAt, meshTight(d->uvs, d->uv_stride, 2, (int)V, tmp), V * 8);
+    if (rc == HR_OK && tangents && !normals) rc = stagedUpload(c, (char *)nrmAt, meshTight(d->normals, d->normal_stride, 3, (int)V, tmp), V * 12);
+    if (rc == HR_OK && nIdx) rc = stagedUpload(c, (char *)idxAt, (const char *)d->indices, nIdx * 4);
     if (rc) return rc;
     // ---- the kernels, the copies back, one wait
     HIP_TRY(c, c->meshPrep.counters.ensure(kMsCounterWords));

@@ -55,6 +55,7 @@ static void featuresDestroyed(hr_ctx *c)
     c->exposure.release();
     c->metric.release();
     c->meshPrep.release();
+    c->deform.release();
 }
 
 // ---- "a full-frame post-process wants this frame"

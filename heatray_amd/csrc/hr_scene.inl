@@ -146,6 +146,7 @@ int hr_geom_remove(hr_ctx *c, hr_geom_id id)
     for (int k = 0; k < 2; ++k) // an upload of this mesh may still be in flight (nothing to wait for when the staging ring is idle)
         if (c->stageBusy[k] && hipEventQuery(c->stageEv[k]) != hipSuccess) HIP_TRY(c, hipEventSynchronize(c->stageEv[k]));
     c->meshRelease(c->geoms[id].chunk);
+    deformRelease(c->geoms[id]);
     c->geoms[id] = Geom();
     c->committed = false, c->topologyDirty = true;
     return HR_OK;
@@ -170,6 +171,7 @@ int hr_scene_clear(hr_ctx *c)
     for (int k = 0; k < 2; ++k)
         if (c->stageBusy[k] && hipEventQuery(c->stageEv[k]) != hipSuccess) HIP_TRY(c, hipEventSynchronize(c->stageEv[k]));
     c->meshReleaseAll();
+    for (Geom &g : c->geoms) deformRelease(g);
     c->geoms.clear();
     c->committed = false, c->topologyDirty = true;
     return HR_OK;
