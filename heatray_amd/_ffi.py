@@ -409,6 +409,40 @@ class DeformResult(C.Structure):
         return d
 
 
+# every symbol include/hrcore_query.h declares (ray queries: the caller's rays traced on the device, with surface records).
+# Resolved lazily like the AOV symbols
+HR_QUERY_API_VERSION = 1
+HR_QUERY_ANY_HIT = 1
+HR_QUERY_INVALID_RAY = -2
+HR_QUERY_SF_FRONT, HR_QUERY_SF_HAS_UV, HR_QUERY_SF_NON_OCCLUDER = 1, 2, 4
+QUERY_SYMBOLS = ["query_api_version", "query_trace", "query_trace_host", "query_pixels", "query_last"]
+
+
+class QuerySurface(C.Structure):
+    """hr_query_surface"""
+    _fields_ = [("geom", C.c_int32), ("material", C.c_int32), ("prim_in_geom", C.c_int32), ("flags", C.c_uint32), ("position", C.c_float * 3),
+                ("normal", C.c_float * 3), ("geometric_normal", C.c_float * 3), ("uv", C.c_float * 2), ("reserved", C.c_float)]
+
+
+SURFACE_DTYPE = np.dtype([("geom", np.int32), ("material", np.int32), ("prim_in_geom", np.int32), ("flags", np.uint32), ("position", np.float32, (3,)),
+                          ("normal", np.float32, (3,)), ("geometric_normal", np.float32, (3,)), ("uv", np.float32, (2,)), ("reserved", np.float32)])
+
+
+class QueryDesc(C.Structure):
+    """hr_query_desc"""
+    _fields_ = [("n", C.c_int32), ("flags", C.c_uint32), ("origins", C.c_void_p), ("directions", C.c_void_p), ("tmax", C.c_void_p), ("skip_prim", C.c_void_p),
+                ("origin_stride", C.c_int32), ("direction_stride", C.c_int32), ("tmax_stride", C.c_int32), ("skip_stride", C.c_int32), ("tmin", C.c_float),
+                ("reserved", C.c_uint32 * 3), ("hits", C.c_void_p), ("surfaces", C.c_void_p)]
+
+
+class QueryResult(C.Structure):
+    """hr_query_result"""
+    _fields_ = [("rays", C.c_uint64), ("hits", C.c_uint64), ("invalid", C.c_uint64), ("reserved", C.c_uint64 * 5)]
+
+    def as_dict(self):
+        return {k: int(getattr(self, k)) for k in ("rays", "hits", "invalid")}
+
+
 # The optional headers: feature ->(its symbols, the version the binding was written against, what "this library has no ..." calls it);
 # the version function is <feature>_api_version.  Engine._feature_call checks a feature on its first call
 FEATURES = {
@@ -424,6 +458,7 @@ FEATURES = {
     "despeckle": (DESPECKLE_SYMBOLS, HR_DESPECKLE_API_VERSION, "firefly suppression"),
     "mesh": (MESH_SYMBOLS, HR_MESH_API_VERSION, "mesh preparation"),
     "deform": (DEFORM_SYMBOLS, HR_DEFORM_API_VERSION, "deformable meshes"),
+    "query": (QUERY_SYMBOLS, HR_QUERY_API_VERSION, "ray queries"),
 }
 
 
@@ -1153,6 +1188,77 @@ class Engine:
         """The last successful update_mesh's or deform_pose's DeformResult as a dict."""
         r = DeformResult()
         self._feature_call("deform", "deform_last", C.byref(r))
+        return r.as_dict()
+
+    # -- ray queries (include/hrcore_query.h)
+    @staticmethod
+    def _query_desc(n, origins, dirs, tmax, skip, strides, any_hit, tmin, hits, surfaces):
+        d = QueryDesc()
+        d.n, d.flags = int(n), HR_QUERY_ANY_HIT if any_hit else 0
+        d.origins, d.directions, d.tmax, d.skip_prim = origins or None, dirs or None, tmax or None, skip or None
+        d.origin_stride, d.direction_stride, d.tmax_stride, d.skip_stride = (int(v) for v in strides)
+        d.tmin = -1.0 if tmin is None else float(tmin)
+        d.hits, d.surfaces = hits or None, surfaces or None
+        return d
+
+    def query(self, origins, dirs, tmax=None, skip_prim=None, any_hit=False, surface=False, tmin=None):
+        """Trace the caller's rays (numpy, n x 3 each) against the committed scene: the hits (HIT_DTYPE, as debug_trace reports them;
+        prim = HR_QUERY_INVALID_RAY for a ray that is not finite), or (hits, surfaces) with surface=True (SURFACE_DTYPE: which mesh, which
+        triangle of it, where on it).  any_hit: an occlusion query (prim 0 blocked / -1 clear).  tmin=None: the scene's ray epsilon.
+        A float32 array whose rows are strided (a view into an interleaved buffer) goes to the library as it is, stride included."""
+        def rows(a, comps, dtype):
+            a = np.asarray(a)
+            shaped = a.ndim == 2 and a.shape[1] == comps and a.strides[1] == 4 if comps > 1 else a.ndim == 1
+            if a.dtype != dtype or not shaped or a.strides[0] % 4 or a.strides[0] < comps * 4:
+                a = np.ascontiguousarray(a, dtype=dtype).reshape((-1, comps) if comps > 1 else (-1,))
+            return a
+        o, d = rows(origins, 3, np.float32), rows(dirs, 3, np.float32)
+        n = o.shape[0]
+        if d.shape[0] != n:
+            raise ValueError(f"query: {n} origins but {d.shape[0]} directions")
+        tm = None if tmax is None else rows(tmax, 1, np.float32)
+        sk = None if skip_prim is None else rows(skip_prim, 1, np.int32)
+        for name, a in (("tmax", tm), ("skip_prim", sk)):
+            if a is not None and a.shape[0] != n:
+                raise ValueError(f"query: {n} rays but {a.shape[0]} entries of {name}")
+        hits = np.empty(n, dtype=HIT_DTYPE)
+        surf = np.empty(n, dtype=SURFACE_DTYPE) if surface else None
+        addr = lambda a: None if a is None else a.ctypes.data
+        stride = lambda a: 0 if a is None or a.shape[0] < 2 else a.strides[0]
+        desc = self._query_desc(n, addr(o), addr(d), addr(tm), addr(sk), (stride(o), stride(d), stride(tm), stride(sk)), any_hit, tmin, addr(hits), addr(surf))
+        nothing = C.c_float()
+        if n == 0:  # (an empty array's address may be null, which the library would call "null origins"; with n = 0 nothing is read or written)
+            desc.origins = desc.directions = desc.hits = C.addressof(nothing)
+        self._feature_call("query", "query_trace_host", C.byref(desc))
+        return (hits, surf) if surface else hits
+
+    def query_to_device(self, n, origins_ptr, dirs_ptr, hits_ptr=None, surfaces_ptr=None, tmax_ptr=None, skip_ptr=None, strides=(0, 0, 0, 0),
+                        any_hit=False, tmin=None, stream=None):
+        """Asynchronous: n rays in device memory (raw device pointers, e.g. torch tensors' data_ptr(); strides in bytes for origins,
+        directions, tmax, skip_prim, 0 = tight) -> n hr_hit at hits_ptr and / or n hr_query_surface at surfaces_ptr, on `stream` (None: the
+        context's).  Ordered behind the last commit; the next commit waits for it (include/hrcore_query.h, ORDERING)."""
+        desc = self._query_desc(n, origins_ptr, dirs_ptr, tmax_ptr, skip_ptr, strides, any_hit, tmin, hits_ptr, surfaces_ptr)
+        self._feature_call("query", "query_trace", C.byref(desc), C.c_void_p(stream or 0))
+
+    def query_pixels(self, pass_params, xy, surface=True, rays=False):
+        """The camera rays through the points xy (n x 2, pixel units: the centre of pixel x, y is x + 0.5, y + 0.5, row 0 at the bottom) of
+        the frame, traced with tmin = 0: hits, then surfaces with surface=True, then the rays (n x 6: o, d) with rays=True.  hits["t"] is
+        the focus_distance that focuses the lens on what the pixel shows."""
+        p = _f32(xy).reshape(-1, 2)
+        n = p.shape[0]
+        hits = np.empty(n, dtype=HIT_DTYPE)
+        surf = np.empty(n, dtype=SURFACE_DTYPE) if surface else None
+        ro = np.empty((n, 6), dtype=np.float32) if rays else None
+        self._feature_call("query", "query_pixels", C.byref(pass_params), C.c_int32(n), _ptr(p) if n else C.pointer(C.c_float()),
+                           hits.ctypes.data_as(C.c_void_p) if n else C.byref(Hit()), None if surf is None else surf.ctypes.data_as(C.c_void_p),
+                           None if ro is None else _ptr(ro))
+        out = (hits,) + ((surf,) if surface else ()) + ((ro,) if rays else ())
+        return out if len(out) > 1 else hits
+
+    def query_last(self):
+        """{"rays", "hits", "invalid"} of the last successful query; completes the queries in flight."""
+        r = QueryResult()
+        self._feature_call("query", "query_last", C.byref(r))
         return r.as_dict()
 
     def debug_trace(self, origins, dirs, tmax=None, skip_prim=None, any_hit=False):

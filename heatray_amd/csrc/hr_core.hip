@@ -19,6 +19,7 @@
 //   hr_despeckle.inl  firefly suppression: the outlier clamp the denoiser can be run behind (include/hrcore_despeckle.h)
 //   hr_mesh.inl       mesh preparation: smooth normals and tangent frames for a mesh without them (include/hrcore_mesh.h)
 //   hr_deform.inl     deformable meshes: vertex updates in place, device posing, read-back (include/hrcore_deform.h)
+//   hr_query.inl      ray queries: the caller's rays traced against the committed scene, with surface records (include/hrcore_query.h)
 //   hr_adaptive.inl   the sample mask and the error estimate that builds it (include/hrcore_adaptive.h)
 //   hr_history.inl    history reprojection across a camera change (include/hrcore_history.h)
 //   hr_reproject.inl  its progressive form and the preview of unsampled pixels (include/hrcore_reproject.h)
@@ -50,6 +51,7 @@ static int quiesce(hr_ctx *c)
     int rc = drainPipeline(c);
     if (rc) return rc;
     HIP_TRY(c, hipStreamSynchronize(c->stream));
+    HIP_TRY(c, c->query.wait()); // (include/hrcore_query.h: a ray query in flight on a caller's stream reads the committed scene)
     return HR_OK;
 }
 #define QUIESCE(ctx)              \
@@ -318,6 +320,7 @@ int hr_ctx_destroy(hr_ctx *c)
                 c->dbgGrowths, (double)c->dbgGrowBytes / 1048576.0, c->dbgWaits, c->dbgWaitSpun, (double)c->dbgWaitNs * 1e-6);
     drainPipeline(c);
     hipStreamSynchronize(c->stream);
+    c->query.wait(); // (ray queries in flight on a caller's stream)
     if (c->selector.probeStream) hipStreamSynchronize(c->selector.probeStream), hipStreamDestroy(c->selector.probeStream);
     if (c->selector.evProbeA) hipEventDestroy(c->selector.evProbeA);
     if (c->selector.evProbeB) hipEventDestroy(c->selector.evProbeB);
@@ -727,3 +730,6 @@ int hr_debug_trace(hr_ctx *c, int32_t n, const float *o, const float *d, const f
 
 // ------------------------------------------------------------------------------------------ deformable meshes
 #include "hr_deform.inl"
+
+// ------------------------------------------------------------------------------------------ ray queries
+#include "hr_query.inl"

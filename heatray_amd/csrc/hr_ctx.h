@@ -523,6 +523,7 @@ struct hr_ctx {
     DespeckleState despeckle;
     MeshPrepState meshPrep;
     DeformState deform;
+    QueryState query;
     // Context group (include/hrcore_group.h): non-null when this handle is a group.  Its own fields then describe the ASSEMBLED frame on the
     // group's first device (W, H, frame, fbInternal, the read-back buffers) and `stream` is the assembly stream; no pass pipeline runs on it.
     GroupState *grp = nullptr;

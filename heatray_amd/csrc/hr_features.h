@@ -138,3 +138,36 @@ struct DeformState {
     bool done = false;                           // ... there has been one (hr_deform_last)
     void release() { counters.free(), *this = DeformState(); }
 };
+
+// Ray queries (include/hrcore_query.h).  Nothing here depends on the frame: it goes with the context.  The scratch stages the host calls
+// (rays in, answers out), grown only, not counted against memBudget.  `geoms` is the table from a committed mesh's first triangle to its
+// hr_geom_id, uploaded by the first query after a commit (geomsStale).  evDone is recorded behind every query on the stream it ran on:
+// wait() is what quiesce and hr_ctx_destroy call before anything a query reads is rewritten or freed, and what hr_query_last waits on.
+// On a group's handle nothing is used: member 0 serves the calls.
+struct QueryState {
+    char *scratch = nullptr;
+    size_t scratchBytes = 0;
+    hr::QyGeom *geoms = nullptr;
+    size_t geomsCap = 0;
+    int nGeoms = 0;
+    bool geomsStale = true;
+    ResultCounters<unsigned long long> counters; // kQyCounterWords; the copy to `host` is enqueued behind every query
+    hipEvent_t evOrder = nullptr, evDone = nullptr;
+    hipStream_t lastStream = nullptr; // the stream evDone was last recorded on
+    bool inFlight = false;            // evDone has been recorded and not waited for
+    uint64_t lastRays = 0;            // n of the last successful call
+    bool done = false;                // ... there has been one (hr_query_last)
+    hipError_t wait()
+    {
+        if (!inFlight) return hipSuccess;
+        inFlight = false;
+        return hipEventSynchronize(evDone);
+    }
+    void release()
+    {
+        wait();
+        if (evOrder) hipEventDestroy(evOrder);
+        if (evDone) hipEventDestroy(evDone);
+        hipFree(scratch), hipFree(geoms), counters.free(), *this = QueryState();
+    }
+};

@@ -15,6 +15,7 @@
 #include "../../include/hrcore_despeckle.h"
 #include "../../include/hrcore_mesh.h"
 #include "../../include/hrcore_deform.h"
+#include "../../include/hrcore_query.h"
 
 #include <cstddef>
 
@@ -317,6 +318,39 @@ static const size_t kDfCounterWords = 2;
 void launchDeformGather(hipStream_t st, const DfCopy &s);
 void launchDeformScatter(hipStream_t st, const DfCopy &s);
 void launchDeformPose(hipStream_t st, const DfPoseArgs &s);
+
+// ---- hr_query.hip (include/hrcore_query.h)
+// first triangle (prim id) of a committed mesh -> its hr_geom_id, in the order of the commit's GeomDev list (triOffset ascending)
+struct QyGeom {
+    uint32_t triOffset;
+    int32_t id;
+};
+// One launch of ray queries; every pointer is device memory.  Rays are addressed in BYTES through the strides (never 0 here: the host
+// has put in the tight ones); tmax / skip null: none.  hits / surfaces: either may be null.  slotOfPrim null: `tris` is in prim order.
+// counters: kQySlots copies of one word (hits | invalid << 32), each on a 128-byte line of its own, zeroed by the caller: a wave adds to
+// copy blockIdx.x % kQySlots with ONE atomic and the host sums the copies.
+struct QyArgs {
+    const SceneDev *scene;
+    const char *origins, *directions, *tmax, *skip;
+    int32_t oStride, dStride, tStride, sStride;
+    int32_t n;
+    float tmin; // negative: the scene's ray epsilon
+    hr_hit *hits;
+    hr_query_surface *surfaces;
+    const uint32_t *slotOfPrim;
+    const QyGeom *geoms;
+    int32_t nGeoms;
+    unsigned long long *counters;
+};
+static const int kQySlots = 64, kQySlotStride = 16;
+static const size_t kQyCounterWords = (size_t)kQySlots * kQySlotStride;
+void launchQueryTrace(hipStream_t st, const QyArgs &a, bool anyHit);
+// the camera of hr_query_pixels as the kernel takes it; xy: n x 2 floats -> rays: n x 6 floats (o, d)
+struct QyCamera {
+    float view[16];
+    float fovTan, aspect, focus, W, H;
+};
+void launchQueryCamera(hipStream_t st, const QyCamera &cam, int n, const float *xy, float *rays);
 
 // ---- hr_build.hip
 // Per-geometry descriptor for the assemble kernel; all pointers are device pointers.  Attributes are addressed with a stride

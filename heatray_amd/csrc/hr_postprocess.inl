@@ -56,6 +56,7 @@ static void featuresDestroyed(hr_ctx *c)
     c->metric.release();
     c->meshPrep.release();
     c->deform.release();
+    c->query.release();
 }
 
 // ---- "a full-frame post-process wants this frame"

@@ -496,6 +496,7 @@ int hr_scene_commit(hr_ctx *c)
     c->selector.sceneOrSizeChanged(); // (another tree)
     c->sceneDirty = true;
     c->texDensityStale = true;
+    c->query.geomsStale = true; // (include/hrcore_query.h: the table from a mesh's first triangle to its id)
     c->topologyDirty = false, c->transformDirty = false;
     return HR_OK;
 }
