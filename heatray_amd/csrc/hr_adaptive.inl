@@ -25,8 +25,8 @@ static int adaptiveCheckParams(hr_ctx *c, const hr_adaptive_params *in, hr_adapt
 
 static int sampleMaskEnsure(hr_ctx *c, bool bytesToo)
 {
-    if (!c->adaptive.maskWords) HIP_TRY(c, hipMalloc((void **)&c->adaptive.maskWords, sampleMaskWords(c->W, c->H) * 4));
-    if (bytesToo && !c->adaptive.maskBytes) HIP_TRY(c, hipMalloc((void **)&c->adaptive.maskBytes, (size_t)c->W * c->H));
+    if (!c->adaptive.maskWords) HIP_TRY(c, c->adaptive.maskWords.alloc(sampleMaskWords(c->W, c->H)));
+    if (bytesToo && !c->adaptive.maskBytes) HIP_TRY(c, c->adaptive.maskBytes.alloc((size_t)c->W * c->H));
     return HR_OK;
 }
 
@@ -139,8 +139,8 @@ int hr_adaptive_update(hr_ctx *c, const hr_adaptive_params *params, int32_t inst
     rc = frameReady(c, need, &frame, &n);
     if (rc) return rc;
     const size_t px = (size_t)c->W * c->H, maskBytes = sampleMaskWords(c->W, c->H) * 4;
-    if (!c->adaptive.error) HIP_TRY(c, hipMalloc((void **)&c->adaptive.error, px * 4));
-    if (!c->adaptive.builtWords) HIP_TRY(c, hipMalloc((void **)&c->adaptive.builtWords, maskBytes));
+    if (!c->adaptive.error) HIP_TRY(c, c->adaptive.error.alloc(px));
+    if (!c->adaptive.builtWords) HIP_TRY(c, c->adaptive.builtWords.alloc(maskBytes / 4));
     HIP_TRY(c, c->adaptive.result.ensure(kAdaptiveResultWords));
     if (install) {
         rc = sampleMaskEnsure(c, false);

@@ -122,15 +122,15 @@ int hr_aov_readback(hr_ctx *c, int32_t plane, const float **rgba, int32_t *w, in
         rc = drainPipeline(c);
         n = c->nextResolveOrder - c->aov.zeroedAt;
     }
-    if (rc == HR_OK) rc = c->aov.pinned.grow(c, bytes);
+    if (rc == HR_OK) rc = growPinned(c, c->aov.pinned, bytes);
     if (rc) return rc;
-    HIP_TRY(c, hipMemcpyAsync(c->aov.pinned.ptr, c->aov.plane[plane], bytes, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipMemcpyAsync(c->aov.pinned.get(), c->aov.plane[plane], bytes, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(c, hipStreamSynchronize(c->stream));
     if (!c->grp) {
         rc = overflowCheck(c);
         if (rc) return rc;
     }
-    *rgba = c->aov.pinned.ptr;
+    *rgba = c->aov.pinned.get();
     if (w) *w = c->W;
     if (h) *h = c->H;
     if (passes) *passes = n;

@@ -5,7 +5,8 @@
 // that needs one fails with HR_ERR_DEVICE.
 //
 //   hr_ctx.h          the context (what the opaque handle points to), the error macros
-//   hr_features.h     the state of the post-process features, one struct per feature with a release(); PinnedBuf, ResultCounters
+//   hr_owned.h        the owning handles every device buffer, pinned buffer, event and stream is held through: the one place that frees them
+//   hr_features.h     the state of the post-process features, one struct per feature with a release(); ResultCounters
 //   hr_step_memory.h  the bytes a macro step takes from scratch and from the step arena, stated once (host-only, like hr_tune.h)
 //   hr_core.hip       this file: context life cycle, frame, display, read-backs, statistics
 //   hr_scene.inl      geometry ingest, commit (build / refit / tree cache), textures, materials, lights, sample tables
@@ -80,12 +81,7 @@ static int completeForSlowCaller(hr_ctx *c)
 }
 static void freeLagged(hr_ctx::Lagged &L)
 {
-    for (int k = 0; k < 3; ++k) {
-        if (L.pinned[k]) hipHostFree(L.pinned[k]);
-        hipFree(L.dev[k]);
-        if (L.ev[k]) hipEventDestroy(L.ev[k]);
-        L.pinned[k] = nullptr, L.dev[k] = nullptr, L.ev[k] = nullptr, L.pending[k] = false;
-    }
+    for (int k = 0; k < 3; ++k) L.pinned[k].reset(), L.dev[k].reset(), L.ev[k].reset(), L.pending[k] = false;
     L.bytes = 0;
 }
 
@@ -94,9 +90,9 @@ static int ensureLagged(hr_ctx *c, hr_ctx::Lagged &L, size_t bytes, bool withDev
     if (L.bytes >= bytes && (!withDevice || L.dev[0])) return HR_OK;
     freeLagged(L);
     for (int k = 0; k < 3; ++k) {
-        HIP_TRY(c, hipHostMalloc(&L.pinned[k], bytes, hipHostMallocDefault));
-        if (withDevice) HIP_TRY(c, hipMalloc(&L.dev[k], bytes));
-        HIP_TRY(c, hipEventCreateWithFlags(&L.ev[k], hipEventDisableTiming));
+        HIP_TRY(c, L.pinned[k].alloc(bytes));
+        if (withDevice) HIP_TRY(c, L.dev[k].alloc(bytes));
+        HIP_TRY(c, L.ev[k].create(hipEventDisableTiming));
     }
     L.bytes = bytes;
     return HR_OK;
@@ -125,15 +121,9 @@ static int finishLagged(hr_ctx *c, hr_ctx::Lagged &L, int k, int32_t format, con
 
 static void freeQueues(hr_ctx *c)
 {
-    for (hr_ctx::PassSlot &ps : c->slots) {
-        hipFree(ps.passbuf);
-        if (ps.evFinal) hipEventDestroy(ps.evFinal);
-        if (ps.evResolved) hipEventDestroy(ps.evResolved);
-        ps = hr_ctx::PassSlot();
-    }
+    for (hr_ctx::PassSlot &ps : c->slots) ps = hr_ctx::PassSlot();
     for (hr_ctx::Group &G : c->groups) {
-        hipFree(G.arena[0].base), hipFree(G.arena[1].base), hipFree(G.scratch.base);
-        G.arena[0] = G.arena[1] = G.scratch = hr_ctx::Group::Region();
+        G.arena[0] = hr_ctx::Group::Region(), G.arena[1] = hr_ctx::Group::Region(), G.scratch = hr_ctx::Group::Region();
         G.arenaHighWater = 0;
     }
     c->nSlotsAllocated = 0;
@@ -167,34 +157,22 @@ static int aovAllocPlanes(hr_ctx *c)
     const bool want[3] = {(c->aov.mask & HR_AOV_SURFACE) != 0, (c->aov.mask & HR_AOV_SURFACE) != 0, (c->aov.mask & HR_AOV_MOMENTS) != 0};
     for (int p = 0; p < 3; ++p) {
         if (!want[p]) continue;
-        HIP_TRY(c, hipMalloc(&c->aov.plane[p], bytes));
+        HIP_TRY(c, c->aov.plane[p].alloc(bytes / sizeof(float)));
         HIP_TRY(c, hipMemsetAsync(c->aov.plane[p], 0, bytes, c->stream));
     }
     return HR_OK;
 }
 
+// the one place that frees a tree (BuildResult is hr_kernels.h's, shared with the build unit: it stays raw)
+static void freeTree(BuildResult &br)
+{
+    hipFree(br.nodes), hipFree(br.nodes32), hipFree(br.leafKeys), hipFree(br.tris), hipFree(br.nodeBox), hipFree(br.slotOfPrim);
+    br = BuildResult{};
+}
 static void freeTree(hr_ctx *c)
 {
-    hipFree(c->tree.nodes), hipFree(c->tree.nodes32), hipFree(c->tree.leafKeys), hipFree(c->tree.tris), hipFree(c->tree.nodeBox), hipFree(c->tree.slotOfPrim);
-    c->tree = BuildResult{};
+    freeTree(c->tree);
     c->nodes = nullptr, c->tris = nullptr, c->treeTris = 0;
-}
-static void freeSceneDevice(hr_ctx *c)
-{
-    freeTree(c);
-    hipFree(c->attrs), hipFree(c->attrsExt), hipFree(c->trisPrim), hipFree(c->dG);
-    c->attrs = nullptr, c->attrsExt = nullptr, c->trisPrim = nullptr, c->dG = nullptr;
-    c->attrsCap = c->attrsExtCap = c->trisPrimCap = c->dGCap = 0;
-}
-
-template <class T> static int ensureCap(hr_ctx *c, T **p, size_t *cap, size_t need)
-{
-    if (*cap >= need && *p) return HR_OK;
-    hipFree(*p);
-    *p = nullptr, *cap = 0;
-    HIP_TRY(c, hipMalloc((void **)p, sizeof(T) * (need ? need : 1)));
-    *cap = need;
-    return HR_OK;
 }
 
 // Context groups (hr_group.inl, included at the end of this file): every entry point hands a group handle to one of these.
@@ -258,7 +236,14 @@ int hr_ctx_create(const hr_ctx_desc *desc, hr_ctx **out)
     // Memory the host READS WHILE A KERNEL THAT WRITES IT IS RUNNING (queue lengths, probe totals, the overflow report): coherent
     // (uncached on the device side, fine-grained) whatever HIP_HOST_COHERENT says — hipHostMallocDefault leaves that to the environment
     const unsigned kHostSpun = hipHostMallocCoherent | hipHostMallocMapped;
-    bool groupsOk = true;
+// (hr_ctx_create has no context to leave a message in: what was made so far goes with the context)
+#define CREATE_TRY(expr)                \
+    do {                                \
+        if ((expr) != hipSuccess) {     \
+            delete c;                   \
+            return HR_ERR_DEVICE;       \
+        }                               \
+    } while (0)
     for (int g = 0; g < kMaxGroups; ++g) {
         hr_ctx::Group &G = c->groups[g];
         // Worker streams at the highest stream priority, created before anything else uses the device queues: HIP maps the
@@ -266,50 +251,52 @@ int hr_ctx_create(const hr_ctx_desc *desc, hr_ctx **out)
         // overlap at all — which happened as soon as the application had a few streams of its own (torch side stream, RCCL).
         // The high-priority pool is practically empty, so the groups get a hardware queue each.  (Creating them lazily, at
         // the first macro step, measurably loses overlap on half- and quarter-frame shards.)
-        {
-            int least = 0, greatest = 0;
-            groupsOk = groupsOk && hipDeviceGetStreamPriorityRange(&least, &greatest) == hipSuccess;
-            groupsOk = groupsOk && hipStreamCreateWithPriority(&G.stream, hipStreamNonBlocking, c->tune.prio ? greatest : 0) == hipSuccess;
-            groupsOk = groupsOk && hipStreamCreateWithPriority(&G.streamB, hipStreamNonBlocking, c->tune.prio ? greatest : 0) == hipSuccess &&
-                       hipEventCreateWithFlags(&G.evFork, hipEventDisableTiming) == hipSuccess && hipEventCreateWithFlags(&G.evJoin, hipEventDisableTiming) == hipSuccess;
-        }
-        groupsOk = groupsOk && hipMalloc(&G.dTables, sizeof(StepTable) * kTableRing) == hipSuccess;
-        groupsOk = groupsOk && hipHostMalloc((void **)&G.hTables, sizeof(StepTable) * kTableRing, hipHostMallocDefault) == hipSuccess &&
-                   hipHostGetDevicePointer((void **)&G.dTablesHost, G.hTables, 0) == hipSuccess;
-        groupsOk = groupsOk && hipEventCreateWithFlags(&G.evUser, hipEventDisableTiming) == hipSuccess;
-        for (int k = 0; k < kTableRing; ++k) groupsOk = groupsOk && hipEventCreateWithFlags(&G.tableCopied[k], hipEventDisableTiming) == hipSuccess;
-        for (int k = 0; k < kTableRing; ++k) groupsOk = groupsOk && hipEventCreateWithFlags(&G.statusEv[k], hipEventDisableTiming) == hipSuccess;
-        groupsOk = groupsOk && hipHostMalloc((void **)&G.hQCount, sizeof(uint32_t) * kTableRing * kMaxSlots * kMaxBounceSlots, hipHostMallocDefault) == hipSuccess;
-        groupsOk = groupsOk && hipHostMalloc((void **)&G.hCounts, sizeof(uint32_t) * (kTableRing * kMaxSegs + 1), kHostSpun) == hipSuccess;
-        groupsOk = groupsOk && hipHostMalloc((void **)&G.hSeq, sizeof(unsigned long long) * kTableRing, kHostSpun) == hipSuccess;
-        groupsOk = groupsOk && hipHostGetDevicePointer((void **)&G.dCounts, G.hCounts, 0) == hipSuccess &&
-                   hipHostGetDevicePointer((void **)&G.dSeq, (void *)G.hSeq, 0) == hipSuccess;
-        groupsOk = groupsOk && hipHostMalloc((void **)&G.hProbe, sizeof(unsigned long long) * kTableRing * 8, kHostSpun) == hipSuccess &&
-                   hipHostGetDevicePointer((void **)&G.dProbeHost, (void *)G.hProbe, 0) == hipSuccess;
-        if (groupsOk)
-            G.hCounts[kTableRing * kMaxSegs] = 0u; // (the last word: StepTable::hostCameraCount)
-        if (groupsOk)
-            for (int k = 0; k < kTableRing; ++k) G.hSeq[k] = 0ull, G.hProbe[8 * k] = 0ull, G.hProbe[8 * k + 1] = 0ull, G.hProbe[8 * k + 2] = 0ull, G.hProbe[8 * k + 3] = 0ull, G.hProbe[8 * k + 4] = 0ull;
+        int least = 0, greatest = 0;
+        CREATE_TRY(hipDeviceGetStreamPriorityRange(&least, &greatest));
+        CREATE_TRY(G.stream.createWithPriority(hipStreamNonBlocking, c->tune.prio ? greatest : 0));
+        CREATE_TRY(G.streamB.createWithPriority(hipStreamNonBlocking, c->tune.prio ? greatest : 0));
+        CREATE_TRY(G.evFork.create(hipEventDisableTiming));
+        CREATE_TRY(G.evJoin.create(hipEventDisableTiming));
+        CREATE_TRY(G.dTables.alloc(kTableRing));
+        CREATE_TRY(G.hTables.alloc(kTableRing));
+        CREATE_TRY(G.hTables.devicePointer(&G.dTablesHost));
+        CREATE_TRY(G.evUser.create(hipEventDisableTiming));
+        for (Event &e : G.tableCopied) CREATE_TRY(e.create(hipEventDisableTiming));
+        for (Event &e : G.statusEv) CREATE_TRY(e.create(hipEventDisableTiming));
+        CREATE_TRY(G.hQCount.alloc((size_t)kTableRing * kMaxSlots * kMaxBounceSlots));
+        CREATE_TRY(G.hCounts.alloc(kTableRing * kMaxSegs + 1, kHostSpun));
+        CREATE_TRY(G.hSeq.alloc(kTableRing, kHostSpun));
+        CREATE_TRY(G.hCounts.devicePointer(&G.dCounts));
+        CREATE_TRY(G.hSeq.devicePointer(&G.dSeq));
+        CREATE_TRY(G.hProbe.alloc(kTableRing * 8, kHostSpun));
+        CREATE_TRY(G.hProbe.devicePointer(&G.dProbeHost));
+        G.hCounts[kTableRing * kMaxSegs] = 0u; // (the last word: StepTable::hostCameraCount)
+        for (int k = 0; k < kTableRing; ++k) G.hSeq[k] = 0ull, G.hProbe[8 * k] = 0ull, G.hProbe[8 * k + 1] = 0ull, G.hProbe[8 * k + 2] = 0ull, G.hProbe[8 * k + 3] = 0ull, G.hProbe[8 * k + 4] = 0ull;
         std::memset(G.statusOrder, 0, sizeof(G.statusOrder));
     }
-    groupsOk = groupsOk && hipHostMalloc((void **)&c->hOverflow, 4 * sizeof(uint32_t), kHostSpun) == hipSuccess &&
-               hipHostGetDevicePointer((void **)&c->dOverflowHost, (void *)c->hOverflow, 0) == hipSuccess;
-    if (groupsOk) c->hOverflow[0] = c->hOverflow[1] = c->hOverflow[2] = c->hOverflow[3] = 0u;
-    if (!groupsOk || hipMalloc(&c->dScene, sizeof(SceneDev)) != hipSuccess ||
-        hipMalloc(&c->dStats, sizeof(Stats) * kStatSlots) != hipSuccess || hipMalloc(&c->dScratch, sizeof(uint32_t) * 6 * kBoundSlots) != hipSuccess ||
-        hipMalloc(&c->dZero, 64) != hipSuccess || hipMalloc(&c->selector.dProbe, 64) != hipSuccess || hipMemset(c->selector.dProbe, 0, 64) != hipSuccess ||
-        hipStreamCreateWithFlags(&c->selector.probeStream, hipStreamNonBlocking) != hipSuccess || hipEventCreateWithFlags(&c->selector.evProbeA, hipEventDisableTiming) != hipSuccess ||
-        hipEventCreateWithFlags(&c->selector.evProbeB, hipEventDisableTiming) != hipSuccess || hipMalloc(&c->dCounters, sizeof(Counters) * kMaxSlots) != hipSuccess ||
-        hipMalloc(&c->dStepLog, sizeof(unsigned long long) * 3 * kStepLogCap) != hipSuccess) {
-        delete c;
-        return HR_ERR_DEVICE;
-    }
+    CREATE_TRY(c->hOverflow.alloc(4, kHostSpun));
+    CREATE_TRY(c->hOverflow.devicePointer(&c->dOverflowHost));
+    c->hOverflow[0] = c->hOverflow[1] = c->hOverflow[2] = c->hOverflow[3] = 0u;
+    CREATE_TRY(c->dScene.alloc(1));
+    CREATE_TRY(c->dStats.alloc(kStatSlots));
+    CREATE_TRY(c->dScratch.alloc(6 * kBoundSlots));
+    CREATE_TRY(c->dZero.alloc(64 / sizeof(uint32_t)));
+    CREATE_TRY(c->selector.dProbe.alloc(64 / sizeof(unsigned long long)));
+    CREATE_TRY(hipMemset(c->selector.dProbe, 0, 64));
+    CREATE_TRY(c->selector.probeStream.create(hipStreamNonBlocking));
+    CREATE_TRY(c->selector.evProbeA.create(hipEventDisableTiming));
+    CREATE_TRY(c->selector.evProbeB.create(hipEventDisableTiming));
+    CREATE_TRY(c->dCounters.alloc(kMaxSlots));
+    CREATE_TRY(c->dStepLog.alloc(3 * kStepLogCap));
+#undef CREATE_TRY
     hipMemset(c->dStats, 0, sizeof(Stats) * kStatSlots);
     hipMemset(c->dZero, 0, 64);
     *out = c;
     return HR_OK;
 }
 
+// What must happen in order happens here; then the context is deleted and every handle it holds frees what it owns.  The one invariant
+// that replaces a list of frees: nothing may still be in flight when the members go, and the steps before the delete ensure that.
 int hr_ctx_destroy(hr_ctx *c)
 {
     if (!c) return HR_OK;
@@ -321,52 +308,11 @@ int hr_ctx_destroy(hr_ctx *c)
     drainPipeline(c);
     hipStreamSynchronize(c->stream);
     c->query.wait(); // (ray queries in flight on a caller's stream)
-    if (c->selector.probeStream) hipStreamSynchronize(c->selector.probeStream), hipStreamDestroy(c->selector.probeStream);
-    if (c->selector.evProbeA) hipEventDestroy(c->selector.evProbeA);
-    if (c->selector.evProbeB) hipEventDestroy(c->selector.evProbeB);
+    if (c->selector.probeStream) hipStreamSynchronize(c->selector.probeStream);
     c->drainTimes();
-    for (hipEvent_t e : c->eventPool) hipEventDestroy(e);
-    if (c->evPack) hipEventDestroy(c->evPack);
-    if (c->evCopyOut) hipEventDestroy(c->evCopyOut);
-    freeQueues(c);
-    freeSceneDevice(c);
-    for (Texture &t : c->textures) hipFree(t.dpx);
-    hipFree(c->fbInternal);
-    c->pinned.release();
-    hipFree(c->dDisplay);
     featuresDestroyed(c);
-    c->meshReleaseAll();
+    freeTree(c); // (the two kept raw: the tree, and the bindings of deformable meshes)
     for (Geom &g : c->geoms) deformRelease(g);
-    for (int k = 0; k < 2; ++k) {
-        if (c->stage[k]) hipHostFree(c->stage[k]);
-        if (c->stageEv[k]) hipEventDestroy(c->stageEv[k]);
-    }
-    hipFree(c->dConsts);
-    hipFree(c->dEnvRowCdf), hipFree(c->dEnvColCdf), hipFree(c->dEnvProb), hipFree(c->dEnvRowGuide), hipFree(c->dEnvColGuide);
-    if (c->hConsts) hipHostFree(c->hConsts);
-    c->pinnedDisplay.release();
-    hipFree(c->dMaterials), hipFree(c->dTextures), hipFree(c->dSeq), hipFree(c->dAperture), hipFree(c->dSeqOffsets);
-    hipFree(c->dTexDensity);
-    for (Texture &t : c->textures) hipFree(t.dmips);
-    hipFree(c->dScene), hipFree(c->dStats), hipFree(c->dScratch), hipFree(c->dZero), hipFree(c->selector.dProbe), hipFree(c->dCounters), hipFree(c->dStepLog);
-    if (c->hOverflow) hipHostFree((void *)c->hOverflow);
-    for (hr_ctx::Group &G : c->groups) {
-        if (G.hQCount) hipHostFree(G.hQCount);
-        if (G.hCounts) hipHostFree(G.hCounts);
-        if (G.hSeq) hipHostFree((void *)G.hSeq);
-        if (G.hProbe) hipHostFree((void *)G.hProbe);
-        for (hipEvent_t e : G.statusEv)
-            if (e) hipEventDestroy(e);
-        if (G.stream) hipStreamDestroy(G.stream);
-        if (G.streamB) hipStreamDestroy(G.streamB);
-        if (G.evFork) hipEventDestroy(G.evFork);
-        if (G.evJoin) hipEventDestroy(G.evJoin);
-        hipFree(G.dTables);
-        if (G.hTables) hipHostFree(G.hTables);
-        if (G.evUser) hipEventDestroy(G.evUser);
-        for (hipEvent_t e : G.tableCopied)
-            if (e) hipEventDestroy(e);
-    }
     delete c;
     return HR_OK;
 }
@@ -412,7 +358,7 @@ int hr_frame_pack_owned(hr_ctx *c, void *device_out, void *stream)
     fr.fb = c->fb();
     hipStream_t st = stream ? (hipStream_t)stream : c->stream;
     if (st != c->stream) { // the resolves enqueued so far run on the ctx stream: order the copy behind them
-        if (!c->evPack) HIP_TRY(c, hipEventCreateWithFlags(&c->evPack, hipEventDisableTiming));
+        if (!c->evPack) HIP_TRY(c, c->evPack.create(hipEventDisableTiming));
         HIP_TRY(c, hipEventRecord(c->evPack, c->stream));
         HIP_TRY(c, hipStreamWaitEvent(st, c->evPack, 0));
     }
@@ -442,12 +388,8 @@ static size_t displayPixelBytes(int32_t format) { return format == HR_DISPLAY_RG
 // the display read-backs' device staging and its pinned host copy, at least `need` bytes each; they only grow
 static int growDisplay(hr_ctx *c, size_t need)
 {
-    if (c->pinnedDisplay.bytes >= need) return HR_OK;
-    c->pinnedDisplay.release(); // (first: a failure below leaves no size behind, the next call starts over)
-    hipFree(c->dDisplay);
-    c->dDisplay = nullptr;
-    HIP_TRY(c, hipMalloc(&c->dDisplay, need));
-    return c->pinnedDisplay.grow(c, need);
+    HIP_TRY(c, c->dDisplay.reserve(need));
+    return growPinned(c, c->pinnedDisplay, need);
 }
 
 int hr_display(hr_ctx *c, const hr_display_params *params, int32_t format, void *device_out, uint32_t *passes_shown)
@@ -514,9 +456,9 @@ int hr_display_readback(hr_ctx *c, const hr_display_params *params, int32_t form
     int rc = hr_display(c, params, format, c->dDisplay, passes_shown);
     if (rc) return rc;
     const size_t bytes = (size_t)c->W * c->H * displayPixelBytes(format & ~HR_DISPLAY_PROGRESSIVE);
-    HIP_TRY(c, hipMemcpyAsync(c->pinnedDisplay.ptr, c->dDisplay, bytes, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipMemcpyAsync(c->pinnedDisplay.get(), c->dDisplay, bytes, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(c, hipStreamSynchronize(c->stream));
-    *pixels = c->pinnedDisplay.ptr;
+    *pixels = c->pinnedDisplay.get();
     if (width) *width = c->W;
     if (height) *height = c->H;
     return HR_OK;
@@ -541,15 +483,14 @@ int hr_frame_resize(hr_ctx *c, int32_t w, int32_t h)
     c->snapshotEpoch++;
     c->selector.sceneOrSizeChanged(); // (another resolution)
     freeLagged(c->progFrame), freeLagged(c->progDisplay);
-    hipFree(c->fbInternal);
-    c->fbInternal = nullptr;
+    c->fbInternal.reset();
     c->fbExternal = nullptr;
     featuresFrameResized(c); // (the sample mask goes with the frame it was made for, and so do a captured history and the progressive merge's examined bits)
     const size_t fbBytes = (size_t)w * h * 4 * sizeof(float);
-    HIP_TRY(c, hipMalloc(&c->fbInternal, fbBytes));
+    HIP_TRY(c, c->fbInternal.alloc((size_t)w * h * 4));
     HIP_TRY(c, hipMemsetAsync(c->fbInternal, 0, fbBytes, c->stream));
     c->frameZeroedAt = c->nextResolveOrder;
-    if (int rc = c->pinned.grow(c, fbBytes)) return rc;
+    if (int rc = growPinned(c, c->pinned, fbBytes)) return rc;
     FrameDev &f = c->frame;
     f.W = w, f.H = h, f.rank = c->rank, f.world = c->world, f.tile = c->tile;
     f.tilesX = (w + c->tile - 1) / c->tile, f.tilesY = (h + c->tile - 1) / c->tile;
@@ -623,13 +564,13 @@ int hr_readback(hr_ctx *c, const float **rgba, int32_t *w, int32_t *h)
         int rc = drainPipeline(c);
         if (rc) return rc;
     }
-    HIP_TRY(c, hipMemcpyAsync(c->pinned.ptr, c->fb(), bytes, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipMemcpyAsync(c->pinned.get(), c->fb(), bytes, hipMemcpyDeviceToHost, c->stream));
     QUIESCE(c);
     {
         const int rc = overflowCheck(c);
         if (rc) return rc;
     }
-    *rgba = c->pinned.ptr;
+    *rgba = c->pinned.get();
     if (w) *w = c->W;
     if (h) *h = c->H;
     return HR_OK;
@@ -666,27 +607,25 @@ int hr_debug_trace(hr_ctx *c, int32_t n, const float *o, const float *d, const f
     if (n <= 0 || !o || !d || !out) FAIL(c, HR_ERR_INVALID, "bad arguments");
     int rc = uploadScene(c);
     if (rc) return rc;
-    float *dO = nullptr, *dD = nullptr, *dT = nullptr;
-    int *dS = nullptr;
-    hr_hit *dH = nullptr;
-    HIP_TRY(c, hipMalloc(&dO, (size_t)n * 12));
-    HIP_TRY(c, hipMalloc(&dD, (size_t)n * 12));
-    HIP_TRY(c, hipMalloc(&dH, (size_t)n * sizeof(hr_hit)));
+    DeviceBuf<float> dO, dD, dT;
+    DeviceBuf<int> dS;
+    DeviceBuf<hr_hit> dH;
+    HIP_TRY(c, dO.alloc((size_t)n * 3));
+    HIP_TRY(c, dD.alloc((size_t)n * 3));
+    HIP_TRY(c, dH.alloc((size_t)n));
     HIP_TRY(c, hipMemcpy(dO, o, (size_t)n * 12, hipMemcpyHostToDevice));
     HIP_TRY(c, hipMemcpy(dD, d, (size_t)n * 12, hipMemcpyHostToDevice));
     if (tmax) {
-        HIP_TRY(c, hipMalloc(&dT, (size_t)n * 4));
+        HIP_TRY(c, dT.alloc((size_t)n));
         HIP_TRY(c, hipMemcpy(dT, tmax, (size_t)n * 4, hipMemcpyHostToDevice));
     }
     if (skip) {
-        HIP_TRY(c, hipMalloc(&dS, (size_t)n * 4));
+        HIP_TRY(c, dS.alloc((size_t)n));
         HIP_TRY(c, hipMemcpy(dS, skip, (size_t)n * 4, hipMemcpyHostToDevice));
     }
     launchDebugTrace(c->cfg(c->stream), c->dScene, n, dO, dD, dT, dS, anyHit, dH);
-    hipError_t e = hipStreamSynchronize(c->stream);
-    if (e == hipSuccess) e = hipMemcpy(out, dH, (size_t)n * sizeof(hr_hit), hipMemcpyDeviceToHost);
-    hipFree(dO), hipFree(dD), hipFree(dT), hipFree(dS), hipFree(dH);
-    HIP_TRY(c, e);
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    HIP_TRY(c, hipMemcpy(out, dH, (size_t)n * sizeof(hr_hit), hipMemcpyDeviceToHost));
     return HR_OK;
 }
 

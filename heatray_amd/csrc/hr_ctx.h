@@ -1,12 +1,16 @@
 // hr_ctx.h — the context behind the opaque hr_ctx handle of include/hrcore.h: everything one context owns on the device and the
 // state of its pass pipeline, plus the error macros of the host side.  Included by hr_core.hip only (ONE translation unit: the
 // host side's helpers keep internal linkage); hr_scene.inl and hr_pipeline.inl are that file's two large sections.  The state of the
-// optional post-process features is one member each, of the structs of hr_features.h (with PinnedBuf and ResultCounters).
+// optional post-process features is one member each, of the structs of hr_features.h (with ResultCounters).
+// Ownership: every device buffer, pinned buffer, event and stream the context holds is a handle of hr_owned.h, freed when the context
+// (or the struct it is a member of) goes or is assigned a fresh one.  A raw pointer member owns nothing and says so: it aliases a
+// handle's memory, is the caller's, or is one of the three kept raw on purpose (tree, Geom::dBlock, Geom::deform; DESIGN.md, "Ownership").
 #pragma once
 #include "hr_kernels.h"
 #include "hr_trace.h"
 #include "hr_tune.h"
 #include "hr_step_memory.h"
+#include "hr_owned.h"
 #include "hr_features.h"
 
 #include <algorithm>
@@ -29,8 +33,8 @@ using namespace hr;
 namespace {
 
 struct Texture {
-    void *dpx = nullptr;
-    float *dmips = nullptr; // levels >= 1 (HR_TEXTURE_LOD_CONE), built on first use
+    DeviceBuf<char> dpx;
+    DeviceBuf<float> dmips; // levels >= 1 (HR_TEXTURE_LOD_CONE), built on first use
     TexDesc desc{};
     bool alive = false;
 };
@@ -58,7 +62,7 @@ struct Geom {
     int mode = HR_TRIANGLES;
     float world[16];
     int frontFaceCW = 0, isOccluder = 1, material = 0;
-    char *dBlock = nullptr;   // inside chunk `chunk` of the context's mesh arena
+    char *dBlock = nullptr;   // inside chunk `chunk` of the context's mesh arena, which owns it
     int chunk = -1;
     size_t blockBytes = 0;
     size_t off[7] = {0, 0, 0, 0, 0, 0, 0}; // byte offsets of pos, nrm, uv, tan, bit, col, idx in the block
@@ -88,7 +92,7 @@ static_assert(kMaxSlots == 2 * kMaxSegs, "hr_tune.h bounds depth= by the step ta
 
 struct hr_ctx {
     int device = 0;
-    hipStream_t stream = nullptr;
+    hipStream_t stream = nullptr; // the caller's (hr_ctx_desc::stream, hr_ctx_set_stream): not owned
     bool collectStats = false;
     bool textureLodUsed = false; // a pass has asked for HR_TEXTURE_LOD_CONE (kernel variant, see LaunchCfg)
     bool allLightsUsed = false;  // a pass has asked for HR_ESTIMATOR_ALL_LIGHTS: pass slots hold two occlusion rays per path and a second partial sum
@@ -98,19 +102,20 @@ struct hr_ctx {
 
     // frame
     int W = 0, H = 0;
-    float *fbInternal = nullptr, *fbExternal = nullptr;
-    PinnedBuf pinned; // hr_readback's host buffer
-    hipEvent_t evPack = nullptr; // orders hr_frame_pack_owned on a foreign stream against the resolves on the ctx stream
-    hipEvent_t evCopyOut = nullptr; // orders a post-process feature's copy out on a foreign stream against the ctx stream (copyOutOnStream)
-    void *dDisplay = nullptr; // display resolve: device staging + pinned host copy, grown together (growDisplay)
-    PinnedBuf pinnedDisplay;
+    DeviceBuf<float> fbInternal;
+    float *fbExternal = nullptr; // the caller's memory (hr_frame_bind_external): not owned
+    PinnedBuf<float> pinned; // hr_readback's host buffer
+    Event evPack; // made by the first call that needs it; orders hr_frame_pack_owned on a foreign stream against the resolves on the ctx stream
+    Event evCopyOut; // made by the first call that needs it; orders a post-process feature's copy out on a foreign stream against the ctx stream (copyOutOnStream)
+    DeviceBuf<char> dDisplay; // display resolve: device staging + pinned host copy, grown together (growDisplay)
+    PinnedBuf<char> pinnedDisplay;
     // Progressive snapshots are handed out one call late from rotating buffers: the host then waits for a copy enqueued a
     // whole call ago instead of for everything it has just enqueued, so the GPU always has the next step queued
     // (waiting for the latest copy cost 0.8 ms of idle GPU per pass).
     struct Lagged {
-        void *pinned[3] = {nullptr, nullptr, nullptr};
-        void *dev[3] = {nullptr, nullptr, nullptr}; // device staging (display snapshots only)
-        hipEvent_t ev[3] = {nullptr, nullptr, nullptr};
+        PinnedBuf<char> pinned[3];
+        DeviceBuf<char> dev[3]; // device staging (display snapshots only)
+        Event ev[3];
         uint32_t passes[3] = {0, 0, 0};
         unsigned long long epoch[3] = {0, 0, 0};
         int32_t format[3] = {-1, -1, -1};
@@ -131,13 +136,13 @@ struct hr_ctx {
         bool everResolved = false;
         unsigned long long resolvedAt = 0; // value of nextResolveOrder when this slot's last pass was resolved
         int group = 0;           // pipeline group (worker stream) the pass runs on
-        hipEvent_t evFinal = nullptr;    // recorded on the worker stream after the pass's last stage
-        hipEvent_t evResolved = nullptr; // recorded on the caller's stream after the pass buffer was added to the frame
+        Event evFinal;    // recorded on the worker stream after the pass's last stage
+        Event evResolved; // recorded on the caller's stream after the pass buffer was added to the frame
         // Passes that finish in one macro step, and passes one k_resolve launch adds, share ONE recorded event (a record or a wait is a
         // packet of ~4-8 us on its stream: twelve of each per batch delayed the resolve of a batch by 0.1 ms and its next injection by as
         // much).  The slot that owns the recorded event may be reused later; whoever waits has enqueued the wait before that (same call).
-        hipEvent_t finalEv = nullptr;    // the event to wait on for this pass's last stage (some slot's evFinal)
-        hipEvent_t resolvedEv = nullptr; // ... for the launch that added this pass buffer to the frame (some slot's evResolved)
+        hipEvent_t finalEv = nullptr;    // the event to wait on for this pass's last stage (some slot's evFinal: not owned)
+        hipEvent_t resolvedEv = nullptr; // ... for the launch that added this pass buffer to the frame (some slot's evResolved: not owned)
         int step = 0, nIter = 0;
         unsigned long long order = 0; // injection order (passes resolve in this order)
         hr_pass_params pp{};
@@ -147,10 +152,10 @@ struct hr_ctx {
         ShadowQueue scur{};    // occlusion rays of the pass's next stage
         uint32_t capCur = 0;   // rays qcur can hold (= upper bound of what it holds)
         uint32_t sCapCur = 0;  // occlusion rays scur can hold
-        float *passbuf = nullptr;
-        float *passbufB = nullptr; // second partial sum (allLightsUsed): passbuf + W * H * 4, same allocation
-        float *aov = nullptr;      // HR_AOV_SURFACE: the pass's AOV record (two float4 per pixel) behind the partial sums, same allocation
-        Counters *ctr = nullptr;
+        DeviceBuf<float> passbuf;
+        float *passbufB = nullptr; // second partial sum (allLightsUsed): passbuf + W * H * 4, same allocation (not owned)
+        float *aov = nullptr;      // HR_AOV_SURFACE: the pass's AOV record (two float4 per pixel) behind the partial sums, same allocation (not owned)
+        Counters *ctr = nullptr;   // this slot's entry of dCounters (not owned)
     };
     PassSlot slots[kMaxSlots];
     int nSlotsAllocated = 0;
@@ -159,20 +164,20 @@ struct hr_ctx {
     // group's persistent trace kernel (waves running dry) is back-filled by the other group's kernels.  Resolves run on
     // the caller's stream, strictly in pass order.
     struct Group {
-        hipStream_t stream = nullptr;
-        StepTable *dTables = nullptr;   // ring of device step tables
-        StepTable *hTables = nullptr;   // pinned staging ring
-        StepTable *dTablesHost = nullptr; // ... as the device addresses it
-        hipEvent_t tableCopied[4] = {nullptr, nullptr, nullptr, nullptr};
+        Stream stream;
+        DeviceBuf<StepTable> dTables;   // ring of device step tables
+        PinnedBuf<StepTable> hTables;   // pinned staging ring
+        StepTable *dTablesHost = nullptr; // ... as the device addresses it (not owned)
+        Event tableCopied[4];
         bool tableUsed[4] = {false, false, false, false};
         unsigned long long stepCounter = 0;
-        hipEvent_t evUser = nullptr;    // caller-stream state this group has to wait for
+        Event evUser;    // caller-stream state this group has to wait for
         bool needUserSync = true;
         // Pass-through scenes (single-sided / alpha-masked materials): a pass has no fixed number of stages, so after every
         // macro step the closest-queue lengths of all pass slots are copied to a pinned ring; the host reads the copy of TWO
         // steps ago (a step that has long finished while newer ones are still queued: it never waits for work it has just
         // enqueued) and retires the passes whose queue ran empty.
-        uint32_t *hQCount = nullptr;    // [kStatusRing][kMaxSlots][kMaxBounceSlots], pinned
+        PinnedBuf<uint32_t> hQCount;    // [kStatusRing][kMaxSlots][kMaxBounceSlots], pinned
         // Ray memory of the group (round 4).  A pass used to own two ray queues, an occlusion queue, hit records and a hit list, all
         // sized for EVERY owned pixel, for its whole life: 196 B x pixels x 120 slots = 53 GB for a 1080p render, while a pass past
         // its first bounce holds a few percent of the pixels.  Now every macro step carves what it needs out of three regions:
@@ -185,23 +190,23 @@ struct hr_ctx {
         // finished and all of step t - 1 is still queued: the device never runs dry); only a pass's FIRST stage is sized by pixels.
         // Regions grow on demand (a synchronisation of the group's stream, during the first passes of a render).
         struct Region {
-            char *base = nullptr;
-            size_t cap = 0;
+            DeviceBuf<char> base;
+            size_t cap = 0; // bytes handed out of `base` (growRegion may get more than it asked for)
         };
         Region arena[2], scratch;
         size_t arenaHighWater = 0; // most either half ever needed: both halves are kept that large (consecutive steps see the same load)
-        uint32_t *hCounts = nullptr;                   // [kTableRing][kMaxSegs], pinned: closest-hit queue length per table entry
-        volatile unsigned long long *hSeq = nullptr;   // [kTableRing], pinned: step number + 1 whose lengths the entry holds
-        uint32_t *dCounts = nullptr;                   // the same two arrays as the device addresses them
+        PinnedBuf<uint32_t> hCounts;                   // [kTableRing][kMaxSegs], pinned: closest-hit queue length per table entry
+        PinnedBuf<volatile unsigned long long> hSeq;   // [kTableRing], pinned: step number + 1 whose lengths the entry holds
+        uint32_t *dCounts = nullptr;                   // the same two arrays as the device addresses them (not owned)
         unsigned long long *dSeq = nullptr;
-        hipStream_t streamB = nullptr;                 // HR_TUNE corun=1: the fused packet kernel of a step runs here, beside k_trace (experiment)
-        hipEvent_t evFork = nullptr, evJoin = nullptr;
-        volatile unsigned long long *hProbe = nullptr; // [kTableRing][8] (five used), pinned: the packet probe's totals as of that step's k_trace (packet selector below)
-        unsigned long long *dProbeHost = nullptr;      // ... as the device addresses it
+        Stream streamB;                                // HR_TUNE corun=1: the fused packet kernel of a step runs here, beside k_trace (experiment)
+        Event evFork, evJoin;
+        PinnedBuf<volatile unsigned long long> hProbe; // [kTableRing][8] (five used), pinned: the packet probe's totals as of that step's k_trace (packet selector below)
+        unsigned long long *dProbeHost = nullptr;      // ... as the device addresses it (not owned)
         int countN[4] = {0, 0, 0, 0};                  // entries of the step table that went with ring entry r
         int countSlot[4][HR_MAX_SEGS];                 // ... their pass slots
         unsigned long long countOrder[4][HR_MAX_SEGS]; // ... and passes (order + 1)
-        hipEvent_t statusEv[4] = {nullptr, nullptr, nullptr, nullptr};
+        Event statusEv[4];
         bool statusUsed[4] = {false, false, false, false};
         unsigned long long statusOrder[4][2 * HR_MAX_SEGS]; // pass (order + 1) a slot held when the snapshot was taken, 0 = none
     };
@@ -218,13 +223,13 @@ struct hr_ctx {
     int injectBatch = 1;
     int lastDepth = -1;
     unsigned long long injected = 0;
-    uint32_t *dZero = nullptr;    // a zero word (occlusion count of a pass's first step)
-    Counters *dCounters = nullptr; // one per pass slot, contiguous (copied to the host in one piece in pass-through scenes)
-    unsigned long long *dStepLog = nullptr; // kStepLogCap records of three words (StepTable::stepLog)
+    DeviceBuf<uint32_t> dZero;    // a zero word (occlusion count of a pass's first step)
+    DeviceBuf<Counters> dCounters; // one per pass slot, contiguous (copied to the host in one piece in pass-through scenes)
+    DeviceBuf<unsigned long long> dStepLog; // kStepLogCap records of three words (StepTable::stepLog)
     // Sticky report of a ray queue that turned out longer than its capacity (hr_wave.h: queueOverflow): four pinned, coherent words
     // the kernels write — kind of queue, step, table entry, count.  Checked wherever the caller learns about finished work.
-    volatile uint32_t *hOverflow = nullptr;
-    uint32_t *dOverflowHost = nullptr; // ... as the device addresses them
+    PinnedBuf<volatile uint32_t> hOverflow;
+    uint32_t *dOverflowHost = nullptr; // ... as the device addresses them (not owned)
     // hr_ctx_desc::memory_budget: device bytes the pipeline may hold for rays and pass buffers (0: unlimited).  Bounds the passes
     // injected per step (budgetBatch): first by what a batch needs when every queue is as long as it can get, then — once a full
     // pipeline has shown the real lengths — by what it was seen to need (rayBytesSeen / batchSeen), with a fifth on top.
@@ -249,8 +254,8 @@ struct hr_ctx {
     // mesh has been removed is empty again: one such chunk is kept for the next add (a lone dynamic mesh that is removed and re-added
     // every frame costs no hipFree + hipMalloc), further ones are released, and their entries in the vector are reused.
     struct MeshChunk {
-        char *base = nullptr;
-        size_t cap = 0, used = 0;
+        DeviceBuf<char> base; // (its capacity: the chunk's bytes)
+        size_t used = 0;
         int live = 0;
     };
     std::vector<MeshChunk> meshChunks;
@@ -260,7 +265,7 @@ struct hr_ctx {
         // the newest chunk first (it is the one being filled), then any other with room (e.g. one that ran empty)
         for (int i = (int)meshChunks.size() - 1; i >= 0; --i) {
             MeshChunk &k = meshChunks[i];
-            if (k.base && k.cap - k.used >= need) {
+            if (k.base && k.base.capacity() - k.used >= need) {
                 char *p = k.base + k.used;
                 k.used += need, k.live += 1;
                 *chunkOut = i;
@@ -268,18 +273,18 @@ struct hr_ctx {
             }
         }
         MeshChunk k;
-        k.cap = need > ((size_t)64 << 20) ? need : ((size_t)64 << 20);
-        if (hipMalloc((void **)&k.base, k.cap) != hipSuccess) return nullptr;
+        if (k.base.alloc(need > ((size_t)64 << 20) ? need : ((size_t)64 << 20)) != hipSuccess) return nullptr;
         k.used = need, k.live = 1;
+        char *const p = k.base;
         for (size_t i = 0; i < meshChunks.size(); ++i)
             if (!meshChunks[i].base) { // a released chunk's entry (other meshes refer to chunks by index, so entries never move)
-                meshChunks[i] = k;
+                meshChunks[i] = std::move(k);
                 *chunkOut = (int)i;
-                return k.base;
+                return p;
             }
-        meshChunks.push_back(k);
+        meshChunks.push_back(std::move(k));
         *chunkOut = (int)meshChunks.size() - 1;
-        return k.base;
+        return p;
     }
     void meshRelease(int chunk)
     {
@@ -289,16 +294,9 @@ struct hr_ctx {
         k.live = 0, k.used = 0; // empty: its space is handed out again
         int spare = 0;
         for (const MeshChunk &o : meshChunks) spare += (o.base && o.live == 0) ? 1 : 0;
-        if (spare > 1 || k.cap > ((size_t)64 << 20)) { // keep ONE empty default-sized chunk
-            hipFree(k.base);
-            k.base = nullptr, k.cap = 0;
-        }
+        if (spare > 1 || k.base.capacity() > ((size_t)64 << 20)) k.base.reset(); // keep ONE empty default-sized chunk
     }
-    void meshReleaseAll()
-    {
-        for (MeshChunk &k : meshChunks) hipFree(k.base);
-        meshChunks.clear();
-    }
+    void meshReleaseAll() { meshChunks.clear(); }
     // scene (host mirror)
     std::vector<Geom> geoms;
     std::vector<Texture> textures;
@@ -306,8 +304,8 @@ struct hr_ctx {
     hr_lights lights{};
     int32_t blockNx = 0, blockNy = 0, blockCoords[32] = {0};
     // importance table of the environment map (HR_ESTIMATOR_ENV_MIS), built on the device when a pass first asks for it
-    float *dEnvRowCdf = nullptr, *dEnvColCdf = nullptr, *dEnvProb = nullptr;
-    uint16_t *dEnvRowGuide = nullptr, *dEnvColGuide = nullptr;
+    DeviceBuf<float> dEnvRowCdf, dEnvColCdf, dEnvProb;
+    DeviceBuf<uint16_t> dEnvRowGuide, dEnvColGuide;
     int envW = 0, envH = 0, envTex = -2;
     float envMeanLum = 0.0f;
     bool committed = false, sceneDirty = true, hasPassthrough = false;
@@ -352,9 +350,9 @@ struct hr_ctx {
         unsigned long long probeWaves = 0;   // waves of the pending probe: it is complete when the third total has grown by as many
         double lastUnion = 0.0;              // U of the last probe (HR_DEBUG_PIPE prints it)
         float probeCamera[21] = {0};         // fov, aspect, focus distance, aperture, view matrix, interactive mode of the probed pass
-        unsigned long long *dProbe = nullptr; // five device counters (of eight words) the probe launches add to (never reset)
-        hipStream_t probeStream = nullptr;   // the probe runs beside the pipeline: it makes its own camera rays and writes only the counters
-        hipEvent_t evProbeA = nullptr, evProbeB = nullptr; // scene and tables as the group's stream sees them -> probe may start; probe done
+        DeviceBuf<unsigned long long> dProbe; // five device counters (of eight words) the probe launches add to (never reset)
+        Stream probeStream;                  // the probe runs beside the pipeline: it makes its own camera rays and writes only the counters
+        Event evProbeA, evProbeB; // scene and tables as the group's stream sees them -> probe may start; probe done
         bool probeGuard = false;             // evProbeB has not been waited for yet (drainPipeline does: the scene may change afterwards)
 
         void sceneOrSizeChanged() { probeCountdown = 0; } // another tree, another resolution: the next injecting step probes
@@ -410,65 +408,60 @@ struct hr_ctx {
         }
     };
     PacketSelector selector;
-    // persistent device arrays of the committed scene (grow-only capacities, reused across commits)
-    GeomDev *dG = nullptr;
-    size_t dGCap = 0;
-    Tri *trisPrim = nullptr;  // prim-order triangles (input of a full build)
-    size_t trisPrimCap = 0;
-    size_t attrsCap = 0, attrsExtCap = 0;
-    BuildResult tree{};       // nodes, leaf-order triangles, node boxes, prim -> slot map, level ranges
+    // persistent device arrays of the committed scene (grow-only: reserve; reused across commits)
+    DeviceBuf<GeomDev> dG;
+    DeviceBuf<Tri> trisPrim;  // prim-order triangles (input of a full build)
+    BuildResult tree{};       // nodes, leaf-order triangles, node boxes, prim -> slot map, level ranges: raw, shared with the build unit; freeTree frees it
     uint32_t treeTris = 0;
-    SceneConsts *dConsts = nullptr;
-    SceneConsts *hConsts = nullptr; // pinned
+    DeviceBuf<SceneConsts> dConsts;
+    PinnedBuf<SceneConsts> hConsts;
     float builtAreaSum = 0.0f; // (sum of the node boxes' areas) / (sum of the triangles' areas) right after the last full build (refit quality reference)
     std::string cachePath;          // hr_scene_cache
     // pinned staging ring for mesh uploads
-    char *stage[2] = {nullptr, nullptr};
-    hipEvent_t stageEv[2] = {nullptr, nullptr};
+    PinnedBuf<char> stage[2];
+    Event stageEv[2];
     bool stageBusy[2] = {false, false};
     int stageTurn = 0;
     hr_scene_info info{};
     hr_tree_info treeInfo{}; // include/hrcore_tree.h: of the last commit that built the tree
 
-    // scene (device); nodes / tris alias tree.nodes / tree.tris
+    // scene (device); nodes / tris alias tree.nodes / tree.tris (not owned)
     Node4 *nodes = nullptr;
     Tri *tris = nullptr;
-    TriAttr *attrs = nullptr;
-    TriAttrExt *attrsExt = nullptr;
-    hr_material *dMaterials = nullptr;
-    size_t dMaterialsCap = 0;
-    TexDesc *dTextures = nullptr;
-    size_t dTexturesCap = 0;
-    float *dTexDensity = nullptr; // HR_TEXTURE_LOD_CONE: per-triangle level offset, rebuilt after every commit once the mode was used
-    size_t texDensityCap = 0;
+    DeviceBuf<TriAttr> attrs;
+    DeviceBuf<TriAttrExt> attrsExt;
+    DeviceBuf<hr_material> dMaterials;
+    DeviceBuf<TexDesc> dTextures;
+    DeviceBuf<float> dTexDensity; // HR_TEXTURE_LOD_CONE: per-triangle level offset, rebuilt after every commit once the mode was used
     bool texDensityStale = true;
-    float2 *dSeq = nullptr, *dAperture = nullptr, *dSeqOffsets = nullptr;
+    DeviceBuf<float2> dSeq, dAperture, dSeqOffsets;
     int nSeq = 0, seqLen = 0, nSeqOffsets = 0;
     SceneDev hScene{};
-    SceneDev *dScene = nullptr;
-    Stats *dStats = nullptr;
-    uint32_t *dScratch = nullptr; // 8 words: ordered bounds etc.
+    DeviceBuf<SceneDev> dScene;
+    DeviceBuf<Stats> dStats;
+    DeviceBuf<uint32_t> dScratch; // 8 words: ordered bounds etc.
 
     // optional per-kernel timing (HR_CTX_TIME_KERNELS)
     bool timeKernels = false;
     struct Timed {
         int kind;
-        hipEvent_t e0, e1;
+        hipEvent_t e0, e1; // entries of timingEvents (not owned)
         bool e0Shared; // e0 is the e1 of the entry before (timeNext): one record between two kernels enqueued back to back
     };
     std::vector<Timed> pending;
-    std::vector<hipEvent_t> eventPool;
+    std::vector<Event> timingEvents;    // every event getEvent has made
+    std::vector<hipEvent_t> eventPool;  // ... those of them not in `pending` (not owned)
     float kernelMs[HR_KERNEL_COUNT] = {0, 0, 0, 0};
     uint32_t kernelLaunches[HR_KERNEL_COUNT] = {0, 0, 0, 0};
     hipEvent_t getEvent()
     {
-        hipEvent_t e = nullptr;
-        if (!eventPool.empty()) {
-            e = eventPool.back();
-            eventPool.pop_back();
-        } else {
-            hipEventCreate(&e);
+        if (eventPool.empty()) {
+            timingEvents.emplace_back();
+            timingEvents.back().create();
+            return timingEvents.back();
         }
+        const hipEvent_t e = eventPool.back();
+        eventPool.pop_back();
         return e;
     }
     void timeBegin(int kind, hipStream_t st)
@@ -553,11 +546,9 @@ struct hr_ctx {
     HIP_TRY(ctx, hipSetDevice((ctx)->device))
 
 
-inline int PinnedBuf::grow(hr_ctx *c, size_t need)
+// a read-back's pinned staging: at least `needBytes`, grow-only (a shrinking frame keeps its buffer); reports through the context
+template <class T> inline int growPinned(hr_ctx *c, PinnedBuf<T> &b, size_t needBytes)
 {
-    if (bytes >= need) return HR_OK;
-    release();
-    HIP_TRY(c, hipHostMalloc((void **)&ptr, need, hipHostMallocDefault));
-    bytes = need;
+    HIP_TRY(c, b.reserve((needBytes + sizeof(T) - 1) / sizeof(T)));
     return HR_OK;
 }

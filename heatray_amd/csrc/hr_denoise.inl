@@ -29,8 +29,8 @@ static int denoiseCheckParams(hr_ctx *c, const hr_denoise_params *in, hr_denoise
 static int denoiseEnsureBuffers(hr_ctx *c, bool needOut)
 {
     const size_t px = (size_t)c->W * c->H;
-    if (!c->denoise.work) HIP_TRY(c, hipMalloc((void **)&c->denoise.work, px * kDenoiseBytesPerPixel));
-    if (needOut && !c->denoise.out) HIP_TRY(c, hipMalloc((void **)&c->denoise.out, px * 16));
+    if (!c->denoise.work) HIP_TRY(c, c->denoise.work.alloc(px * kDenoiseBytesPerPixel / sizeof(float)));
+    if (needOut && !c->denoise.out) HIP_TRY(c, c->denoise.out.alloc(px * 4));
     return HR_OK;
 }
 
@@ -120,13 +120,13 @@ static int denoiseReadback(hr_ctx *c, const hr_denoise_params *params, const Den
 {
     int rc = denoiseRun(c, params, nullptr, passes, spatial, source);
     const size_t bytes = (size_t)c->W * c->H * 16;
-    if (rc == HR_OK) rc = c->denoise.pinned.grow(c, bytes);
+    if (rc == HR_OK) rc = growPinned(c, c->denoise.pinned, bytes);
     if (rc) return rc;
-    HIP_TRY(c, hipMemcpyAsync(c->denoise.pinned.ptr, c->denoise.out, bytes, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipMemcpyAsync(c->denoise.pinned.get(), c->denoise.out, bytes, hipMemcpyDeviceToHost, c->stream));
     if (spatial) HIP_TRY(c, c->denoise.spatial.fetch(c->stream));
     HIP_TRY(c, hipStreamSynchronize(c->stream)); // (one wait for the image and the counters)
     denoiseSpatialFill(c, result);
-    *rgba = c->denoise.pinned.ptr;
+    *rgba = c->denoise.pinned.get();
     if (w) *w = c->W;
     if (h) *h = c->H;
     return HR_OK;

@@ -36,7 +36,7 @@ static void despeckleFill(const hr_ctx *c, hr_despeckle_result *out)
 
 static int despeckleEnsurePlanes(hr_ctx *c)
 {
-    if (!c->despeckle.planes) HIP_TRY(c, hipMalloc((void **)&c->despeckle.planes, (size_t)c->W * c->H * 32));
+    if (!c->despeckle.planes) HIP_TRY(c, c->despeckle.planes.alloc((size_t)c->W * c->H * 8));
     return HR_OK;
 }
 static float *despeckleMomentsPlane(const hr_ctx *c) { return c->despeckle.planes + (size_t)c->W * c->H * 4; }
@@ -156,13 +156,13 @@ int hr_despeckle_readback(hr_ctx *c, const hr_despeckle_params *params, const fl
     uint32_t n = 0;
     if (rc == HR_OK) rc = despeckleOwnFrame(c, p, HR_AOV_MOMENTS, true, nullptr, nullptr, &n);
     const size_t bytes = (size_t)c->W * c->H * 16;
-    if (rc == HR_OK) rc = c->despeckle.pinned.grow(c, 2 * bytes);
+    if (rc == HR_OK) rc = growPinned(c, c->despeckle.pinned, 2 * bytes);
     if (rc) return rc;
-    HIP_TRY(c, hipMemcpyAsync(c->despeckle.pinned.ptr, c->despeckle.planes, moments ? 2 * bytes : bytes, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipMemcpyAsync(c->despeckle.pinned.get(), c->despeckle.planes, moments ? 2 * bytes : bytes, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(c, hipStreamSynchronize(c->stream)); // (one wait for the images and the counters)
     despeckleFill(c, result);
-    *rgba = c->despeckle.pinned.ptr;
-    if (moments) *moments = c->despeckle.pinned.ptr + bytes / sizeof(float);
+    *rgba = c->despeckle.pinned.get();
+    if (moments) *moments = c->despeckle.pinned.get() + bytes / sizeof(float);
     if (w) *w = c->W;
     if (h) *h = c->H;
     if (passes) *passes = n;

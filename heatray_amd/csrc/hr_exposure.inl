@@ -86,7 +86,7 @@ static int exposureRun(hr_ctx *c, const hr_exposure_params *params, const void *
     if (rc) return rc;
     HIP_TRY(c, c->exposure.bins.ensure(kExWords));
     if (!c->exposure.state) {
-        HIP_TRY(c, hipMalloc((void **)&c->exposure.state, 2 * sizeof(uint32_t)));
+        HIP_TRY(c, c->exposure.state.alloc(2));
         HIP_TRY(c, hipMemsetAsync(c->exposure.state, 0, 2 * sizeof(uint32_t), c->stream));
     }
     HIP_TRY(c, c->exposure.bins.zero(c->stream));

@@ -23,16 +23,16 @@ struct GroupState {
     struct Member {
         hr_ctx *ctx = nullptr;   // written and used by the member's thread only
         int device = 0;
-        hipStream_t stream = nullptr;  // the member context's stream (created by its thread, on its device)
-        hipEvent_t evPacked = nullptr; // its device: the member's packed pixels (and their copy to the first device) are complete
+        Stream stream;  // the member context's stream (created by its thread, on its device, and reset there)
+        Event evPacked; // its device: the member's packed pixels (and their copy to the first device) are complete
         std::thread thread;
         std::deque<std::function<int(hr_ctx *)>> jobs; // guarded by GroupState::mu
         int queued = 0;                                // jobs posted and not finished yet (guarded)
         int err = HR_OK;                               // first failure of a job since the group's last call reported one (guarded)
         std::string errMsg;
         // assembly (written by the member's job, read by the caller after waiting for it)
-        float *packed = nullptr;  // its device: owned pixels in pack order, slots x RGBA32F
-        float *staging = nullptr; // the first device: their copy (members on another device; caller's thread allocates it)
+        DeviceBuf<float> packed;  // its device: owned pixels in pack order, slots x RGBA32F (reset by the member's thread)
+        DeviceBuf<float> staging; // the first device: their copy (members on another device; caller's thread allocates it)
         uint64_t slots = 0;
         uint32_t passes = 0;      // complete passes in the last packed pixels
         bool idle = true;         // no pass of the member was pending or in flight when it last packed
@@ -42,7 +42,7 @@ struct GroupState {
     std::mutex mu;
     std::condition_variable cvJob, cvDone;
     bool stop = false;
-    hipEvent_t evGathered = nullptr; // the first device: recorded on the assembly stream behind the last gather
+    Event evGathered; // the first device: recorded on the assembly stream behind the last gather
     bool gathered = false;
 };
 
@@ -157,11 +157,7 @@ static int groupDestroy(hr_ctx *c)
             hipSetDevice(M.device);
             if (m) hr_ctx_destroy(m);
             M.ctx = nullptr;
-            hipFree(M.packed);
-            M.packed = nullptr;
-            if (M.evPacked) hipEventDestroy(M.evPacked);
-            if (M.stream) hipStreamDestroy(M.stream);
-            M.evPacked = nullptr, M.stream = nullptr;
+            M.packed.reset(), M.evPacked.reset(), M.stream.reset(); // (on the member's thread, its device current)
             return HR_OK;
         }, 1 << 30);
     {
@@ -176,15 +172,7 @@ static int groupDestroy(hr_ctx *c)
     }
     for (int i = 0; i < g->n; ++i)
         if (g->m[i].thread.joinable()) g->m[i].thread.join();
-    hipSetDevice(c->device);
-    for (int i = 0; i < g->n; ++i) hipFree(g->m[i].staging);
-    if (g->evGathered) hipEventDestroy(g->evGathered);
-    freeLagged(c->progFrame), freeLagged(c->progDisplay);
-    hipFree(c->fbInternal);
-    c->pinned.release();
-    hipFree(c->dDisplay);
-    c->pinnedDisplay.release();
-    if (c->evCopyOut) hipEventDestroy(c->evCopyOut);
+    hipSetDevice(c->device); // (the first device: what the group itself holds lives there — staging, evGathered, the assembled frame)
     featuresDestroyed(c);
     delete g;
     delete c;
@@ -207,29 +195,26 @@ static int groupResize(hr_ctx *c, int32_t w, int32_t h)
         GroupState::Member &M = g->m[i];
         int rc = hr_frame_resize(m, w, h);
         if (rc) return rc;
-        hipFree(M.packed);
-        M.packed = nullptr;
+        M.packed.reset();
         M.slots = (uint64_t)m->frame.nOwnedTiles * (uint64_t)(m->tile * m->tile);
-        if (M.slots) HIP_TRY(m, hipMalloc(&M.packed, M.slots * 16));
+        if (M.slots) HIP_TRY(m, M.packed.alloc(M.slots * 4));
         return HR_OK;
     });
     if (rc) return rc;
     for (int i = 0; i < g->n; ++i) {
         GroupState::Member &M = g->m[i];
-        hipFree(M.staging);
-        M.staging = nullptr;
-        if (M.device != c->device && M.slots) HIP_TRY(c, hipMalloc(&M.staging, M.slots * 16));
+        M.staging.reset();
+        if (M.device != c->device && M.slots) HIP_TRY(c, M.staging.alloc(M.slots * 4));
     }
     c->W = w, c->H = h;
     c->snapshotEpoch++;
     freeLagged(c->progFrame), freeLagged(c->progDisplay);
-    hipFree(c->fbInternal);
-    c->fbInternal = nullptr;
+    c->fbInternal.reset();
     featuresFrameResized(c); // (the group's copy of the sample mask; the members' went with their frames)
     const size_t fbBytes = (size_t)w * h * 4 * sizeof(float);
-    HIP_TRY(c, hipMalloc(&c->fbInternal, fbBytes));
+    HIP_TRY(c, c->fbInternal.alloc((size_t)w * h * 4));
     HIP_TRY(c, hipMemsetAsync(c->fbInternal, 0, fbBytes, c->stream));
-    if ((rc = c->pinned.grow(c, fbBytes))) return rc;
+    if ((rc = growPinned(c, c->pinned, fbBytes))) return rc;
     FrameDev &f = c->frame; // the assembled frame: rank 0 of world 1
     f.W = w, f.H = h, f.rank = 0, f.world = 1, f.tile = c->tile;
     f.tilesX = (w + c->tile - 1) / c->tile, f.tilesY = (h + c->tile - 1) / c->tile;
@@ -292,9 +277,9 @@ static int groupReadback(hr_ctx *c, const float **rgba, int32_t *w, int32_t *h)
     if (c->W <= 0 || !rgba) FAIL(c, HR_ERR_INVALID, "no frame");
     int rc = groupAssemble(c, true, nullptr, nullptr);
     if (rc) return rc;
-    HIP_TRY(c, hipMemcpyAsync(c->pinned.ptr, c->fbInternal, (size_t)c->W * c->H * 4 * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipMemcpyAsync(c->pinned.get(), c->fbInternal, (size_t)c->W * c->H * 4 * sizeof(float), hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(c, hipStreamSynchronize(c->stream));
-    *rgba = c->pinned.ptr;
+    *rgba = c->pinned.get();
     if (w) *w = c->W;
     if (h) *h = c->H;
     return HR_OK;
@@ -367,9 +352,9 @@ static int groupDisplayReadback(hr_ctx *c, const hr_display_params *params, int3
         if ((rc = growDisplay(c, need))) return rc;
         rc = groupDisplayTo(c, params, format, c->dDisplay, &passes, nullptr);
         if (rc) return rc;
-        HIP_TRY(c, hipMemcpyAsync(c->pinnedDisplay.ptr, c->dDisplay, bytes, hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(c, hipMemcpyAsync(c->pinnedDisplay.get(), c->dDisplay, bytes, hipMemcpyDeviceToHost, c->stream));
         HIP_TRY(c, hipStreamSynchronize(c->stream));
-        *pixels = c->pinnedDisplay.ptr;
+        *pixels = c->pinnedDisplay.get();
         if (shown) *shown = passes;
     }
     if (rc) return rc;
@@ -530,7 +515,7 @@ int hr_ctx_create_group(const hr_ctx_desc *desc, const int32_t *device_ids, int3
     GroupState *g = new GroupState();
     c->grp = g;
     g->n = (int)dev.size();
-    if (hipEventCreateWithFlags(&g->evGathered, hipEventDisableTiming) != hipSuccess) {
+    if (g->evGathered.create(hipEventDisableTiming) != hipSuccess) {
         groupDestroy(c);
         return HR_ERR_DEVICE;
     }
@@ -543,8 +528,7 @@ int hr_ctx_create_group(const hr_ctx_desc *desc, const int32_t *device_ids, int3
         md.rank = i, md.device_id = dev[i];
         groupPost(g, i, [g, i, md](hr_ctx *) mutable { // (the member's own thread creates it)
             GroupState::Member &M = g->m[i];
-            if (hipSetDevice(M.device) != hipSuccess || hipStreamCreateWithFlags(&M.stream, hipStreamNonBlocking) != hipSuccess ||
-                hipEventCreateWithFlags(&M.evPacked, hipEventDisableTiming) != hipSuccess)
+            if (hipSetDevice(M.device) != hipSuccess || M.stream.create(hipStreamNonBlocking) != hipSuccess || M.evPacked.create(hipEventDisableTiming) != hipSuccess)
                 return HR_ERR_DEVICE;
             md.stream = M.stream;
             return hr_ctx_create(&md, &M.ctx);

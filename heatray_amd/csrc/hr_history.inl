@@ -58,7 +58,7 @@ int hr_history_capture(hr_ctx *c, const hr_pass_params *camera)
     uint32_t n = 0;
     rc = historyCheckFrame(c, "history capture", &n);
     if (rc) return rc;
-    if (!c->history.hist) HIP_TRY(c, hipMalloc((void **)&c->history.hist, (size_t)c->W * c->H * kHistoryBytesPerPixel));
+    if (!c->history.hist) HIP_TRY(c, c->history.hist.alloc((size_t)c->W * c->H * kHistoryBytesPerPixel / sizeof(float)));
     c->history.captured = false;
     launchHistoryCapture(c->stream, c->W, c->H, c->fb(), c->aov.plane[HR_AOV_PLANE_ALBEDO], c->aov.plane[HR_AOV_PLANE_NORMAL_DEPTH], c->aov.plane[HR_AOV_PLANE_MOMENTS], c->history.hist);
     HIP_TRY(c, hipGetLastError());

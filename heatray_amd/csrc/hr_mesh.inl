@@ -96,12 +96,9 @@ static int meshScratch(hr_ctx *c, size_t V, size_t T, size_t nIdx, bool normals,
     const size_t oGN = reserve(V * 12), oGC = reserve(V);
     const size_t oOutN = reserve(normals ? V * 12 : 0), oOutT = reserve(tangents ? V * 12 : 0), oOutB = reserve(tangents ? V * 12 : 0);
     const size_t oExtra = reserve(extraBytes);
-    if (c->meshPrep.scratchBytes < total) {
+    if (c->meshPrep.scratch.capacity() < total) {
         HIP_TRY(c, hipStreamSynchronize(c->stream)); // (an earlier call's kernels have been waited for; the ring's copies too)
-        hipFree(c->meshPrep.scratch);
-        c->meshPrep.scratch = nullptr, c->meshPrep.scratchBytes = 0;
-        HIP_TRY(c, hipMalloc((void **)&c->meshPrep.scratch, total));
-        c->meshPrep.scratchBytes = total;
+        HIP_TRY(c, c->meshPrep.scratch.reserve(total));
     }
     char *base = c->meshPrep.scratch;
     const auto F32 = [&](size_t o) { return (float *)(base + o); };

@@ -34,7 +34,7 @@ static int allocSlot(hr_ctx *c, hr_ctx::PassSlot &ps, hipStream_t st)
     const size_t sums = c->allLightsUsed ? 4 : 1;
     // (with HR_ESTIMATOR_ALL_LIGHTS the sample's further partial sums lie right behind the first: k_trace indexes one buffer; the AOV record
     // of HR_AOV_SURFACE behind them)
-    const hipError_t e = hipMalloc(&ps.passbuf, fbBytes * (sums + c->aov.framesPerSlot()));
+    const hipError_t e = ps.passbuf.alloc((size_t)c->W * c->H * 4 * (sums + c->aov.framesPerSlot()));
     if (e != hipSuccess) { // say what ran out: a pass slot is the unit the pipeline's memory grows in
         size_t freeB = 0, totalB = 0;
         hipMemGetInfo(&freeB, &totalB);
@@ -49,8 +49,8 @@ static int allocSlot(hr_ctx *c, hr_ctx::PassSlot &ps, hipStream_t st)
         HIP_TRY(c, hipStreamSynchronize(st));
     }
     ps.ctr = c->dCounters + (&ps - c->slots);
-    HIP_TRY(c, hipEventCreateWithFlags(&ps.evFinal, hipEventDisableTiming));
-    HIP_TRY(c, hipEventCreateWithFlags(&ps.evResolved, hipEventDisableTiming));
+    HIP_TRY(c, ps.evFinal.create(hipEventDisableTiming));
+    HIP_TRY(c, ps.evResolved.create(hipEventDisableTiming));
     ps.allocated = true;
     c->nSlotsAllocated++;
     return HR_OK;
@@ -82,20 +82,19 @@ static int ensureRegion(hr_ctx *c, hr_ctx::Group &G, hr_ctx::Group::Region &r, s
     if (c->tune.debugPipe) fprintf(stderr, "  grow %s: need %.1f MiB, had %.1f MiB (step %llu)\n", what, (double)need / 1048576.0, (double)r.cap / 1048576.0, G.stepCounter);
     HIP_TRY(c, hipStreamSynchronize(G.stream));
     const size_t hadCap = r.cap;
-    hipFree(r.base);
-    r.base = nullptr, r.cap = 0;
+    r.base.reset(), r.cap = 0;
     // a third of headroom: counts vary from pass to pass, and while the pipeline fills (the first depth + 2 steps of a render) every
     // step carries one more generation of passes — for the benchmark soup the steady state needs 27 % more than the step that
     // triggered the last growth (profiles/r4m_mem.txt); a step that needs more regrows once more
     size_t want = need + need / 3;
     if (hadCap && !c->memBudget && want < hadCap + hadCap / 2) want = hadCap + hadCap / 2; // (a region that has to grow again grows by half at least: few events; under a memory budget only by what is needed)
     want = (want + ((size_t)2 << 20)) & ~(((size_t)2 << 20) - 1);
-    hipError_t e = hipMalloc((void **)&r.base, want);
+    hipError_t e = r.base.alloc(want);
     size_t got = want;
     if (e != hipSuccess) {
         (void)hipGetLastError();
         got = align256(need);
-        e = hipMalloc((void **)&r.base, got);
+        e = r.base.alloc(got);
     }
     if (e != hipSuccess) {
         size_t freeB = 0, totalB = 0;

@@ -1,6 +1,6 @@
 // hr_postprocess.inl — a section of hr_core.hip (included before the feature sections): the host plumbing that the AOV planes, the
 // denoiser, adaptive sampling, history reprojection, the progressive merge, auto-exposure, the convergence metric and firefly suppression share ("Adding a post-process feature"), and
-// the one table of when each feature's state goes; the state itself, with ResultCounters and PinnedBuf, is in hr_features.h.
+// the one table of when each feature's state goes; the state itself, with ResultCounters, is in hr_features.h.
 
 // `bytes` of device memory that is complete on the ctx stream -> dst, on `stream` (null: the ctx stream).  On a foreign stream the copy
 // waits for everything enqueued on the ctx stream so far, and the ctx's next work goes behind the copy: the next resolve, filter or update
@@ -12,7 +12,7 @@ static int copyOutOnStream(hr_ctx *c, void *dst, const void *src, size_t bytes, 
         HIP_TRY(c, hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToDevice, st));
         return HR_OK;
     }
-    if (!c->evCopyOut) HIP_TRY(c, hipEventCreateWithFlags(&c->evCopyOut, hipEventDisableTiming));
+    if (!c->evCopyOut) HIP_TRY(c, c->evCopyOut.create(hipEventDisableTiming));
     HIP_TRY(c, hipEventRecord(c->evCopyOut, c->stream));
     HIP_TRY(c, hipStreamWaitEvent(st, c->evCopyOut, 0));
     HIP_TRY(c, hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToDevice, st));
@@ -21,7 +21,8 @@ static int copyOutOnStream(hr_ctx *c, void *dst, const void *src, size_t bytes, 
     return HR_OK;
 }
 
-// ---- when the features' state goes.  These four are the only callers of a feature's release() (hr_history_drop apart) and the only
+// ---- when the features' state goes.  These four are the only callers of a feature's release() (hr_history_drop apart; the context's
+// destructor would free what is left, but hr_ctx_destroy and groupDestroy come through featuresDestroyed first) and the only
 // code that resets a feature's flags; a plain context, a group's handle and its members all come through them.  Every caller has
 // drained or synchronised what could still use the memory.
 // The AOV planes are going (aovAllocPlanes: hr_frame_resize, hr_aov_enable): so does what was computed from them at their size.
@@ -29,7 +30,7 @@ static void featuresPlanesGone(hr_ctx *c)
 {
     c->denoise.release();   // (the denoiser's buffers live and die with the planes it reads)
     c->despeckle.release(); // (... and so do the despeckled frame and moments the denoiser can be run from)
-    c->aov.pinned.release();
+    c->aov.pinned.reset();
 }
 // The frame has another size (hr_frame_resize, groupResize): what was made for the old one goes, an installed sample mask included.
 static void featuresFrameResized(hr_ctx *c)

@@ -14,12 +14,9 @@
 static int queryScratch(hr_ctx *c, size_t bytes)
 {
     QueryState &q = c->query;
-    if (q.scratchBytes >= bytes) return HR_OK;
+    if (q.scratch.capacity() >= bytes) return HR_OK;
     HIP_TRY(c, q.wait()); // (the host calls are synchronous: nothing of theirs is in flight; a device-side query does not use the scratch)
-    hipFree(q.scratch);
-    q.scratch = nullptr, q.scratchBytes = 0;
-    HIP_TRY(c, hipMalloc((void **)&q.scratch, bytes));
-    q.scratchBytes = bytes;
+    HIP_TRY(c, q.scratch.reserve(bytes));
     return HR_OK;
 }
 
@@ -29,8 +26,8 @@ static int queryPrepare(hr_ctx *c)
     QueryState &q = c->query;
     int rc = uploadScene(c);
     if (rc) return rc;
-    if (!q.evOrder) HIP_TRY(c, hipEventCreateWithFlags(&q.evOrder, hipEventDisableTiming));
-    if (!q.evDone) HIP_TRY(c, hipEventCreateWithFlags(&q.evDone, hipEventDisableTiming));
+    if (!q.evOrder) HIP_TRY(c, q.evOrder.create(hipEventDisableTiming));
+    if (!q.evDone) HIP_TRY(c, q.evDone.create(hipEventDisableTiming));
     HIP_TRY(c, q.counters.ensure(kQyCounterWords));
     if (q.geomsStale) { // (set by every commit, which has waited for the queries in flight)
         std::vector<QyGeom> t;
@@ -41,11 +38,9 @@ static int queryPrepare(hr_ctx *c)
             t.push_back(QyGeom{nTris, (int32_t)id});
             nTris += g.nTris();
         }
-        if (q.geomsCap < t.size() || !q.geoms) {
+        if (q.geoms.capacity() < t.size() || !q.geoms) {
             HIP_TRY(c, q.wait());
-            hipFree(q.geoms);
-            q.geoms = nullptr, q.geomsCap = t.size() + 16;
-            HIP_TRY(c, hipMalloc((void **)&q.geoms, q.geomsCap * sizeof(QyGeom)));
+            HIP_TRY(c, q.geoms.reserve(t.size(), 16));
         }
         if (!t.empty()) HIP_TRY(c, hipMemcpy(q.geoms, t.data(), t.size() * sizeof(QyGeom), hipMemcpyHostToDevice));
         q.nGeoms = (int)t.size(), q.geomsStale = false;

@@ -34,7 +34,7 @@ static int previewRun(hr_ctx *c, const hr_pass_params *camera, const hr_history_
     int rc = reprojectPrepare(c, "reproject preview", camera, params, &p, &n);
     if (rc) return rc;
     if (!dst) {
-        if (!c->reproject.out) HIP_TRY(c, hipMalloc((void **)&c->reproject.out, (size_t)c->W * c->H * 16));
+        if (!c->reproject.out) HIP_TRY(c, c->reproject.out.alloc((size_t)c->W * c->H * 4));
         dst = c->reproject.out;
     }
     const HsCam cam = hsCameras(c->history.view, c->history.aspect, c->history.fovTan, camera->view_matrix, camera->aspect_ratio, camera->fov_tan);
@@ -65,7 +65,7 @@ int hr_reproject_merge(hr_ctx *c, const hr_pass_params *camera, const hr_history
         FAIL(c, HR_ERR_INVALID, "reproject merge: hr_history_merge has already merged the history into this frame (a progressive merge would count it twice): hr_clear first");
     const size_t words = rpExaminedWords(c->W, c->H);
     if (!c->reproject.examined) {
-        HIP_TRY(c, hipMalloc((void **)&c->reproject.examined, words * 8));
+        HIP_TRY(c, c->reproject.examined.alloc(words));
         c->reproject.stale = true;
     }
     if (c->reproject.stale) HIP_TRY(c, hipMemsetAsync(c->reproject.examined, 0, words * 8, c->stream));
@@ -126,13 +126,13 @@ int hr_reproject_preview_readback(hr_ctx *c, const hr_pass_params *camera, const
     int rc = previewRun(c, camera, params, nullptr, nullptr);
     if (rc) return rc;
     const size_t bytes = (size_t)c->W * c->H * 16;
-    rc = c->reproject.pinned.grow(c, bytes);
+    rc = growPinned(c, c->reproject.pinned, bytes);
     if (rc) return rc;
-    HIP_TRY(c, hipMemcpyAsync(c->reproject.pinned.ptr, c->reproject.out, bytes, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipMemcpyAsync(c->reproject.pinned.get(), c->reproject.out, bytes, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(c, c->reproject.result.fetch(c->stream));
     HIP_TRY(c, hipStreamSynchronize(c->stream)); // (one wait for the image and the counters)
     previewFill(c, out);
-    *rgba = c->reproject.pinned.ptr;
+    *rgba = c->reproject.pinned.get();
     if (w) *w = c->W;
     if (h) *h = c->H;
     return HR_OK;

@@ -7,8 +7,8 @@ static int stagedUpload(hr_ctx *c, char *dst, const char *src, size_t bytes)
 {
     for (int k = 0; k < 2; ++k) {
         if (!c->stage[k]) {
-            HIP_TRY(c, hipHostMalloc((void **)&c->stage[k], kStageBytes, hipHostMallocDefault));
-            HIP_TRY(c, hipEventCreateWithFlags(&c->stageEv[k], hipEventDisableTiming));
+            HIP_TRY(c, c->stage[k].alloc(kStageBytes));
+            HIP_TRY(c, c->stageEv[k].create(hipEventDisableTiming));
         }
     }
     for (size_t at = 0; at < bytes; at += kStageBytes) {
@@ -251,8 +251,8 @@ bool cachedTreeIsSane(const CacheHeader &h, const char *nodesBytes, const uint32
 // digest of everything the tree depends on: geometry bytes (hashed on the device), transforms, modes, strides
 static int sceneKey(hr_ctx *c, unsigned long long *key)
 {
-    unsigned long long *dKey = nullptr;
-    HIP_TRY(c, hipMalloc(&dKey, 8));
+    DeviceBuf<unsigned long long> dKey;
+    HIP_TRY(c, dKey.alloc(1));
     hipError_t e = hipMemsetAsync(dKey, 0, 8, c->stream);
     unsigned long long host = 0xC0FFEE1234ull;
     auto mix = [&](const void *p, size_t bytes) {
@@ -269,7 +269,6 @@ static int sceneKey(hr_ctx *c, unsigned long long *key)
     unsigned long long dev = 0;
     if (e == hipSuccess) e = hipMemcpyAsync(&dev, dKey, 8, hipMemcpyDeviceToHost, c->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-    hipFree(dKey);
     HIP_TRY(c, e);
     // (which tree a build produces also depends on the builder options: a file made with other ones is another scene's as far as the cache goes)
     mix(&c->tune.ploc, sizeof(c->tune.ploc)), mix(&c->tune.plocr, sizeof(c->tune.plocr));
@@ -306,7 +305,7 @@ static bool loadTree(hr_ctx *c, unsigned long long key, uint32_t nTris, BuildRes
     }
     fclose(f);
     if (!ok) {
-        hipFree(br.nodes), hipFree(br.nodes32), hipFree(br.leafKeys), hipFree(br.nodeBox), hipFree(br.slotOfPrim), hipFree(br.tris);
+        freeTree(br);
         return false;
     }
     br.nNodes = (int32_t)h.nNodes, br.levels = (int32_t)h.levels, br.rootLeafCount = (int32_t)h.rootLeafCount, br.triSlots = h.triSlots;
@@ -345,14 +344,12 @@ static void saveTree(hr_ctx *c, unsigned long long key, uint32_t nTris, const Bu
 // Device temporaries and timing events of one commit: released on every exit path.
 namespace {
 struct CommitScratch {
-    hipEvent_t e0 = nullptr, e1 = nullptr;
+    Event e0, e1;
     BuildResult br{};
-    bool keepBuild = false;
+    bool keepBuild = false; // the context has taken the tree over
     ~CommitScratch()
     {
-        if (e0) hipEventDestroy(e0);
-        if (e1) hipEventDestroy(e1);
-        if (!keepBuild) hipFree(br.nodes), hipFree(br.nodes32), hipFree(br.leafKeys), hipFree(br.tris), hipFree(br.nodeBox), hipFree(br.slotOfPrim);
+        if (!keepBuild) freeTree(br);
     }
 };
 } // namespace
@@ -365,12 +362,12 @@ int hr_scene_commit(hr_ctx *c)
     // until this call succeeds there is no scene to render: a failed re-commit must not leave `committed` set over stale arrays
     c->committed = false, c->sceneDirty = true;
     CommitScratch cs;
-    HIP_TRY(c, hipEventCreate(&cs.e0));
-    HIP_TRY(c, hipEventCreate(&cs.e1));
+    HIP_TRY(c, cs.e0.create());
+    HIP_TRY(c, cs.e1.create());
     HIP_TRY(c, hipEventRecord(cs.e0, c->stream));
     if (!c->dConsts) {
-        HIP_TRY(c, hipMalloc(&c->dConsts, sizeof(SceneConsts)));
-        HIP_TRY(c, hipHostMalloc((void **)&c->hConsts, sizeof(SceneConsts), hipHostMallocDefault));
+        HIP_TRY(c, c->dConsts.alloc(1));
+        HIP_TRY(c, c->hConsts.alloc(1));
     }
     // ---- descriptors of the live geometries (their data is on the device already: hr_geom_add)
     std::vector<GeomDev> gd;
@@ -400,10 +397,10 @@ int hr_scene_commit(hr_ctx *c)
     if (nTris == 0) {
         freeTree(c);
     } else {
-        int rc = ensureCap(c, &c->dG, &c->dGCap, gd.size());
-        if (rc == HR_OK) rc = ensureCap(c, &c->attrs, &c->attrsCap, (size_t)nTris);
-        if (rc == HR_OK && anyExt) rc = ensureCap(c, &c->attrsExt, &c->attrsExtCap, (size_t)nTris);
-        if (rc != HR_OK) return rc;
+        HIP_TRY(c, c->dG.reserve(gd.size()));
+        HIP_TRY(c, c->attrs.reserve((size_t)nTris));
+        if (anyExt) HIP_TRY(c, c->attrsExt.reserve((size_t)nTris));
+        int rc = HR_OK;
         TriAttrExt *ext = anyExt ? c->attrsExt : nullptr;
         HIP_TRY(c, hipMemcpyAsync(c->dG, gd.data(), gd.size() * sizeof(GeomDev), hipMemcpyHostToDevice, c->stream));
         // A commit after transform edits only keeps the tree's topology: triangles are re-assembled straight into their leaf
@@ -430,8 +427,7 @@ int hr_scene_commit(hr_ctx *c)
             if (c->builtAreaSum > 0.0f && nowQ > 0.01f * (float)c->tune.guard * c->builtAreaSum) refit = false;
         }
         if (!refit) {
-            rc = ensureCap(c, &c->trisPrim, &c->trisPrimCap, (size_t)nTris);
-            if (rc != HR_OK) return rc;
+            HIP_TRY(c, c->trisPrim.reserve((size_t)nTris));
             launchAssemble(c->stream, c->dG, (int)gd.size(), nTris, c->trisPrim, nullptr, c->attrs, ext, c->dScratch);
             launchSceneConsts(c->stream, c->dScratch, c->dConsts, nullptr);
             HIP_TRY(c, hipMemcpyAsync(c->hConsts, c->dConsts, sizeof(SceneConsts), hipMemcpyDeviceToHost, c->stream));
@@ -472,7 +468,8 @@ int hr_scene_commit(hr_ctx *c)
             launchTriAreaSum(c->stream, c->tree.tris, c->tree.triSlots, c->dConsts);
             HIP_TRY(c, hipMemcpyAsync(c->hConsts, c->dConsts, sizeof(SceneConsts), hipMemcpyDeviceToHost, c->stream));
             HIP_TRY(c, hipStreamSynchronize(c->stream));
-            c->builtAreaSum = c->hConsts->triAreaSum > 0.0f ? c->hConsts->areaSum / c->hConsts->triAreaSum : 0.0f;
+            const SceneConsts &built = *c->hConsts;
+            c->builtAreaSum = built.triAreaSum > 0.0f ? built.areaSum / built.triAreaSum : 0.0f;
         }
         const SceneConsts &k = *c->hConsts;
         c->nodes = c->tree.nodes, c->tris = c->tree.tris;
@@ -542,11 +539,11 @@ int hr_texture_create(hr_ctx *c, const hr_texture_desc *d, const void *pixels, h
     // float(byte) / 255.0f on fetch, the conversion the reference's loader would otherwise leave to the RL texture unit)
     const size_t bytes = n * (d->dtype == HR_TEX_U8 ? 1 : sizeof(float));
     Texture t;
-    HIP_TRY(c, hipMalloc(&t.dpx, bytes));
+    HIP_TRY(c, t.dpx.alloc(bytes));
     HIP_TRY(c, hipMemcpy(t.dpx, pixels, bytes, hipMemcpyHostToDevice));
-    t.desc = TexDesc{t.dpx, d->width, d->height, d->channels, d->wrap_s, d->wrap_t, d->filter, d->dtype, 0, nullptr, 0.0f, 0};
+    t.desc = TexDesc{t.dpx.get(), d->width, d->height, d->channels, d->wrap_s, d->wrap_t, d->filter, d->dtype, 0, nullptr, 0.0f, 0};
     t.alive = true;
-    c->textures.push_back(t);
+    c->textures.push_back(std::move(t));
     c->sceneDirty = true;
     if (out) *out = (hr_tex_id)c->textures.size() - 1;
     return HR_OK;
@@ -558,7 +555,6 @@ int hr_texture_destroy(hr_ctx *c, hr_tex_id id)
     if (c->grp) return groupAll(c, [&](hr_ctx *m, int) { return hr_texture_destroy(m, id); });
     if (id < 0 || id >= (int)c->textures.size() || !c->textures[id].alive) FAIL(c, HR_ERR_INVALID, "bad texture id");
     QUIESCE(c);
-    hipFree(c->textures[id].dpx), hipFree(c->textures[id].dmips);
     c->textures[id] = Texture();
     if (c->envTex == id) c->envTex = -2, c->envW = c->envH = 0;
     c->sceneDirty = true;
@@ -610,13 +606,11 @@ int hr_interactive_blocks_set(hr_ctx *c, const int32_t *coords, int32_t nx, int3
 }
 
 // ----------------------------------------------------------------------------------- sample tables
-static int setTable(hr_ctx *c, float2 **dst, const float *src, size_t n)
+static int setTable(hr_ctx *c, DeviceBuf<float2> &dst, const float *src, size_t n)
 {
     QUIESCE(c);
-    hipFree(*dst);
-    *dst = nullptr;
-    HIP_TRY(c, hipMalloc(dst, n * sizeof(float2)));
-    if (src) HIP_TRY(c, hipMemcpy(*dst, src, n * sizeof(float2), hipMemcpyHostToDevice));
+    HIP_TRY(c, dst.alloc(n));
+    if (src) HIP_TRY(c, hipMemcpy(dst, src, n * sizeof(float2), hipMemcpyHostToDevice));
     return HR_OK;
 }
 
@@ -625,9 +619,9 @@ int hr_sequences_set(hr_ctx *c, const float *seq, const float *ap, int32_t nSeq,
     ENTER(c);
     if (c->grp) return groupAll(c, [&](hr_ctx *m, int) { return hr_sequences_set(m, seq, ap, nSeq, len); });
     if (!seq || !ap || nSeq <= 0 || nSeq > 255 || len <= 0) FAIL(c, HR_ERR_INVALID, "bad sequence table");
-    int rc = setTable(c, &c->dSeq, seq, (size_t)nSeq * len);
+    int rc = setTable(c, c->dSeq, seq, (size_t)nSeq * len);
     if (rc) return rc;
-    rc = setTable(c, &c->dAperture, ap, (size_t)nSeq * len);
+    rc = setTable(c, c->dAperture, ap, (size_t)nSeq * len);
     if (rc) return rc;
     c->nSeq = nSeq, c->seqLen = len;
     c->sceneDirty = true;
@@ -639,7 +633,7 @@ int hr_seq_offsets_set(hr_ctx *c, const float *off, int32_t n)
     ENTER(c);
     if (c->grp) return groupAll(c, [&](hr_ctx *m, int) { return hr_seq_offsets_set(m, off, n); });
     if (!off || n <= 0) FAIL(c, HR_ERR_INVALID, "bad offsets table");
-    int rc = setTable(c, &c->dSeqOffsets, off, (size_t)n);
+    int rc = setTable(c, c->dSeqOffsets, off, (size_t)n);
     if (rc) return rc;
     c->nSeqOffsets = n;
     c->sceneDirty = true;
@@ -685,13 +679,11 @@ static int sampleTablesOnDevice(hr_ctx *c, int32_t mode, uint32_t seq0, int nSeq
     if (mode == HR_SAMPLE_RANDOM) {
         launchMtTables(c->stream, seq0, nSeq, count, 0, nullptr, nullptr, d, stride);
     } else if (mode == HR_SAMPLE_BLUE_NOISE) {
-        float2 *cand = nullptr;
-        if (count > 1) HIP_TRY(c, hipMalloc(&cand, (size_t)nSeq * (count - 1u) * 30u * sizeof(float2)));
+        DeviceBuf<float2> cand;
+        if (count > 1) HIP_TRY(c, cand.alloc((size_t)nSeq * (count - 1u) * 30u));
         launchBlueNoise(c->stream, (int32_t)seq0, nSeq, count, d, stride, cand);
-        hipError_t e = hipGetLastError();
-        if (e == hipSuccess) e = hipStreamSynchronize(c->stream); // (the scratch is freed here, so the launches must be done)
-        if (cand) hipFree(cand);
-        HIP_TRY(c, e);
+        HIP_TRY(c, hipGetLastError());
+        HIP_TRY(c, hipStreamSynchronize(c->stream)); // (the scratch goes at the end of this block, so the launches must be done)
     } else {
         for (int s = 0; s < nSeq; ++s) launchQmc(c->stream, mode, seq0 + (uint32_t)s, count, d + (size_t)s * stride);
     }
@@ -714,10 +706,8 @@ static bool knownBokeh(int32_t b) { return b >= HR_BOKEH_CIRCULAR && b <= HR_BOK
 
 static int tableToHost(hr_ctx *c, float2 *d, uint32_t count, float *out)
 {
-    hipError_t e = hipMemcpyAsync(out, d, (size_t)count * sizeof(float2), hipMemcpyDeviceToHost, c->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-    hipFree(d);
-    HIP_TRY(c, e);
+    HIP_TRY(c, hipMemcpyAsync(out, d, (size_t)count * sizeof(float2), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
     return HR_OK;
 }
 
@@ -728,13 +718,10 @@ int hr_qmc_generate(hr_ctx *c, int32_t mode, uint32_t seqIndex, uint32_t count, 
     if (!knownSampleMode(mode)) FAIL(c, HR_ERR_INVALID, "unknown sample mode");
     if (radial && mode != HR_SAMPLE_SOBOL) FAIL(c, HR_ERR_INVALID, "radial is defined for Sobol only");
     if (count == 0 || !out) FAIL(c, HR_ERR_INVALID, "bad count / output");
-    float2 *d = nullptr;
-    HIP_TRY(c, hipMalloc(&d, (size_t)count * sizeof(float2)));
+    DeviceBuf<float2> d;
+    HIP_TRY(c, d.alloc(count));
     int rc = sampleTablesOnDevice(c, mode, seqIndex, 1, count, d, count);
-    if (rc) {
-        hipFree(d);
-        return rc;
-    }
+    if (rc) return rc;
     rc = tableToHost(c, d, count, out);
     if (rc) return rc;
     if (radial) radialOnHost(reinterpret_cast<float2 *>(out), count);
@@ -747,13 +734,10 @@ int hr_aperture_generate(hr_ctx *c, int32_t bokeh, uint32_t seqIndex, uint32_t c
     if (c->grp) return groupOne(c, 0, [&](hr_ctx *m) { return hr_aperture_generate(m, bokeh, seqIndex, count, out); });
     if (!knownBokeh(bokeh)) FAIL(c, HR_ERR_INVALID, "unknown bokeh shape");
     if (count == 0 || !out) FAIL(c, HR_ERR_INVALID, "bad count / output");
-    float2 *d = nullptr;
-    HIP_TRY(c, hipMalloc(&d, (size_t)count * sizeof(float2)));
+    DeviceBuf<float2> d;
+    HIP_TRY(c, d.alloc(count));
     int rc = apertureTablesOnDevice(c, bokeh, seqIndex, 1, count, d, count);
-    if (rc) {
-        hipFree(d);
-        return rc;
-    }
+    if (rc) return rc;
     rc = tableToHost(c, d, count, out);
     if (rc) return rc;
     if (bokeh == HR_BOKEH_CIRCULAR) radialOnHost(reinterpret_cast<float2 *>(out), count);
@@ -768,9 +752,9 @@ int hr_sequences_generate(hr_ctx *c, int32_t sampleMode, int32_t bokeh, int32_t 
     if (!knownBokeh(bokeh)) FAIL(c, HR_ERR_INVALID, "unknown bokeh shape");
     if (len <= 0) FAIL(c, HR_ERR_INVALID, "bad sequence length");
     const int nSeq = HR_NUM_RANDOM_SEQUENCES;
-    int rc = setTable(c, &c->dSeq, nullptr, (size_t)nSeq * len);
+    int rc = setTable(c, c->dSeq, nullptr, (size_t)nSeq * len);
     if (rc) return rc;
-    rc = setTable(c, &c->dAperture, nullptr, (size_t)nSeq * len);
+    rc = setTable(c, c->dAperture, nullptr, (size_t)nSeq * len);
     if (rc) return rc;
     rc = sampleTablesOnDevice(c, sampleMode, 0, nSeq, (uint32_t)len, c->dSeq, (size_t)len); // PassGenerator.cpp:614-637
     if (rc) return rc;
@@ -795,7 +779,7 @@ int hr_seq_offsets_generate(hr_ctx *c)
     if (c->grp) return groupAll(c, [](hr_ctx *m, int) { return hr_seq_offsets_generate(m); });
     if (c->W <= 0) FAIL(c, HR_ERR_INVALID, "no frame");
     const size_t n = (size_t)c->W * c->H;
-    int rc = setTable(c, &c->dSeqOffsets, nullptr, n);
+    int rc = setTable(c, c->dSeqOffsets, nullptr, n);
     if (rc) return rc;
     launchQmc(c->stream, HR_SAMPLE_SOBOL, 0, (uint32_t)n, c->dSeqOffsets); // PassGenerator.cpp:150-159
     HIP_TRY(c, hipGetLastError());
@@ -808,29 +792,22 @@ int hr_multiscatter_lut_generate(hr_ctx *c, float *out, hr_tex_id *outTex)
 {
     ENTER(c);
     if (c->grp) return groupMultiscatter(c, out, outTex);
-    float2 *seq = nullptr;
-    float *lut = nullptr;
-    HIP_TRY(c, hipMalloc(&seq, 4096 * sizeof(float2)));
-    HIP_TRY(c, hipMalloc(&lut, 128 * 128 * sizeof(float)));
+    DeviceBuf<float2> seq;
+    DeviceBuf<char> lut; // (bytes, like a texture's pixels, which it may become)
+    HIP_TRY(c, seq.alloc(4096));
+    HIP_TRY(c, lut.alloc(128 * 128 * sizeof(float)));
     launchQmc(c->stream, HR_SAMPLE_SOBOL, 0, 4096, seq); // MultiScatterUtil.cpp:102-104
-    launchMultiscatterLUT(c->stream, seq, lut);
-    hipError_t e = hipStreamSynchronize(c->stream);
-    if (e == hipSuccess && out) e = hipMemcpy(out, lut, 128 * 128 * sizeof(float), hipMemcpyDeviceToHost);
-    hipFree(seq);
-    if (e != hipSuccess) {
-        hipFree(lut);
-        HIP_TRY(c, e);
-    }
+    launchMultiscatterLUT(c->stream, seq, (float *)lut.get());
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    if (out) HIP_TRY(c, hipMemcpy(out, lut, 128 * 128 * sizeof(float), hipMemcpyDeviceToHost));
     if (outTex) { // loadMultiscatterTexture: LINEAR + CLAMP_TO_EDGE sampler (TextureLoader.cpp:36-41)
         Texture t;
-        t.dpx = lut;
-        t.desc = TexDesc{lut, 128, 128, 1, HR_WRAP_CLAMP_TO_EDGE, HR_WRAP_CLAMP_TO_EDGE, HR_FILTER_LINEAR, HR_TEX_F32, 0, nullptr, 0.0f, 0};
+        t.dpx = std::move(lut);
+        t.desc = TexDesc{t.dpx.get(), 128, 128, 1, HR_WRAP_CLAMP_TO_EDGE, HR_WRAP_CLAMP_TO_EDGE, HR_FILTER_LINEAR, HR_TEX_F32, 0, nullptr, 0.0f, 0};
         t.alive = true;
-        c->textures.push_back(t);
+        c->textures.push_back(std::move(t));
         c->sceneDirty = true;
         *outTex = (hr_tex_id)c->textures.size() - 1;
-    } else {
-        hipFree(lut);
     }
     return HR_OK;
 }
@@ -840,18 +817,10 @@ static int uploadScene(hr_ctx *c)
 {
     if (!c->sceneDirty) return HR_OK;
     QUIESCE(c);
-    if (c->dMaterialsCap < c->materials.size() || !c->dMaterials) {
-        hipFree(c->dMaterials);
-        c->dMaterialsCap = c->materials.size() + 16;
-        HIP_TRY(c, hipMalloc(&c->dMaterials, c->dMaterialsCap * sizeof(hr_material)));
-    }
+    HIP_TRY(c, c->dMaterials.reserve(c->materials.size(), 16));
     if (!c->materials.empty())
         HIP_TRY(c, hipMemcpy(c->dMaterials, c->materials.data(), c->materials.size() * sizeof(hr_material), hipMemcpyHostToDevice));
-    if (c->dTexturesCap < c->textures.size() || !c->dTextures) {
-        hipFree(c->dTextures);
-        c->dTexturesCap = c->textures.size() + 16;
-        HIP_TRY(c, hipMalloc(&c->dTextures, c->dTexturesCap * sizeof(TexDesc)));
-    }
+    HIP_TRY(c, c->dTextures.reserve(c->textures.size(), 16));
     std::vector<TexDesc> td(c->textures.size());
     for (size_t i = 0; i < td.size(); ++i) {
         td[i] = c->textures[i].desc;
@@ -901,32 +870,27 @@ static int ensureEnvTable(hr_ctx *c)
     if (c->envTex == id && c->envW == t.w && c->envH == t.h) return HR_OK;
     if (t.w > 65535 || t.h > 65535) FAIL(c, HR_ERR_UNSUPPORTED, "environment map too large for the importance table (65535 texels per side)");
     QUIESCE(c);
-    hipFree(c->dEnvRowCdf), hipFree(c->dEnvColCdf), hipFree(c->dEnvProb), hipFree(c->dEnvRowGuide), hipFree(c->dEnvColGuide);
-    c->dEnvRowCdf = c->dEnvColCdf = c->dEnvProb = nullptr, c->envW = c->envH = 0, c->envTex = -2;
-    c->dEnvRowGuide = c->dEnvColGuide = nullptr;
+    c->dEnvRowCdf.reset(), c->dEnvColCdf.reset(), c->dEnvProb.reset(), c->dEnvRowGuide.reset(), c->dEnvColGuide.reset();
+    c->envW = c->envH = 0, c->envTex = -2;
     const size_t n = (size_t)t.w * t.h;
-    float *lum = nullptr, *dil = nullptr;
-    uint32_t *wq = nullptr, *maxBits = nullptr;
-    unsigned long long *rowSum = nullptr;
-    hipError_t e = hipMalloc(&c->dEnvRowCdf, sizeof(float) * ((size_t)t.h + 1));
-    if (e == hipSuccess) e = hipMalloc(&c->dEnvColCdf, sizeof(float) * (size_t)t.h * ((size_t)t.w + 1));
-    if (e == hipSuccess) e = hipMalloc(&c->dEnvProb, sizeof(float) * n);
-    if (e == hipSuccess) e = hipMalloc(&c->dEnvRowGuide, sizeof(uint16_t) * (kEnvRowGuide + 1));
-    if (e == hipSuccess) e = hipMalloc(&c->dEnvColGuide, sizeof(uint16_t) * (size_t)t.h * (kEnvColGuide + 1));
-    if (e == hipSuccess) e = hipMalloc(&lum, sizeof(float) * n);
-    if (e == hipSuccess) e = hipMalloc(&dil, sizeof(float) * n);
-    if (e == hipSuccess) e = hipMalloc(&wq, sizeof(uint32_t) * n);
-    if (e == hipSuccess) e = hipMalloc(&rowSum, sizeof(unsigned long long) * ((size_t)t.h + 1));
-    if (e == hipSuccess) e = hipMalloc(&maxBits, 16);
-    if (e == hipSuccess) {
-        float *dMean = reinterpret_cast<float *>(maxBits) + 1;
-        launchEnvTable(c->stream, t, lum, dil, wq, rowSum, rowSum + t.h, maxBits, c->dEnvRowCdf, c->dEnvColCdf, c->dEnvProb, dMean);
-        launchEnvGuides(c->stream, c->dEnvRowCdf, c->dEnvColCdf, t.w, t.h, c->dEnvRowGuide, c->dEnvColGuide);
-        e = hipMemcpyAsync(&c->envMeanLum, dMean, sizeof(float), hipMemcpyDeviceToHost, c->stream);
-        if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-    }
-    hipFree(lum), hipFree(dil), hipFree(wq), hipFree(rowSum), hipFree(maxBits);
-    HIP_TRY(c, e);
+    DeviceBuf<float> lum, dil;
+    DeviceBuf<uint32_t> wq, maxBits;
+    DeviceBuf<unsigned long long> rowSum;
+    HIP_TRY(c, c->dEnvRowCdf.alloc((size_t)t.h + 1));
+    HIP_TRY(c, c->dEnvColCdf.alloc((size_t)t.h * ((size_t)t.w + 1)));
+    HIP_TRY(c, c->dEnvProb.alloc(n));
+    HIP_TRY(c, c->dEnvRowGuide.alloc(kEnvRowGuide + 1));
+    HIP_TRY(c, c->dEnvColGuide.alloc((size_t)t.h * (kEnvColGuide + 1)));
+    HIP_TRY(c, lum.alloc(n));
+    HIP_TRY(c, dil.alloc(n));
+    HIP_TRY(c, wq.alloc(n));
+    HIP_TRY(c, rowSum.alloc((size_t)t.h + 1));
+    HIP_TRY(c, maxBits.alloc(4));
+    float *dMean = reinterpret_cast<float *>(maxBits.get()) + 1;
+    launchEnvTable(c->stream, t, lum, dil, wq, rowSum, rowSum + t.h, maxBits, c->dEnvRowCdf, c->dEnvColCdf, c->dEnvProb, dMean);
+    launchEnvGuides(c->stream, c->dEnvRowCdf, c->dEnvColCdf, t.w, t.h, c->dEnvRowGuide, c->dEnvColGuide);
+    HIP_TRY(c, hipMemcpyAsync(&c->envMeanLum, dMean, sizeof(float), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream)); // (the temporaries go at the end of this function: the launches are done)
     c->envW = t.w, c->envH = t.h, c->envTex = id;
     c->sceneDirty = true;
     return HR_OK;
@@ -950,7 +914,7 @@ static int ensureTextureLod(hr_ctx *c)
             elems += (size_t)w * h * d.c;
         }
         if (levels > 1) {
-            HIP_TRY(c, hipMalloc(&t.dmips, elems * sizeof(float)));
+            HIP_TRY(c, t.dmips.alloc(elems));
             launchMipChain(c->stream, d, levels, t.dmips);
         }
         d.nLevels = levels, d.mips = t.dmips;
@@ -962,12 +926,7 @@ static int ensureTextureLod(hr_ctx *c)
             quiesced = true;
         }
         const size_t nTris = c->treeTris;
-        if (c->texDensityCap < nTris || !c->dTexDensity) {
-            hipFree(c->dTexDensity);
-            c->dTexDensity = nullptr, c->texDensityCap = 0;
-            HIP_TRY(c, hipMalloc(&c->dTexDensity, sizeof(float) * (nTris ? nTris : 1)));
-            c->texDensityCap = nTris;
-        }
+        HIP_TRY(c, c->dTexDensity.reserve(nTris ? nTris : 1));
         const uint32_t slots = c->tree.triSlots ? c->tree.triSlots : (uint32_t)nTris;
         launchTexDensity(c->stream, c->tree.tris, slots, c->attrs, c->dTexDensity);
         c->texDensityStale = false;
