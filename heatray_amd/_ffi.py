@@ -443,6 +443,38 @@ class QueryResult(C.Structure):
         return {k: int(getattr(self, k)) for k in ("rays", "hits", "invalid")}
 
 
+# every symbol include/hrcore_motion.h declares (motion reprojection: the history gathered where a moved or deformed surface was).
+# Resolved lazily like the AOV symbols
+HR_MOTION_API_VERSION = 1
+MOTION_SYMBOLS = ["motion_api_version", "motion_default_params", "motion_snapshot", "motion_trace", "motion_merge", "motion_vectors", "motion_vectors_readback",
+                  "motion_readback", "motion_snapshot_readback", "motion_drop", "motion_info"]
+
+
+class MotionTraceResult(C.Structure):
+    """hr_motion_trace_result"""
+    _fields_ = [("surface_pixels", C.c_uint64), ("sky_pixels", C.c_uint64), ("unmatched_pixels", C.c_uint64), ("reserved", C.c_uint64)]
+
+    def as_dict(self):
+        return {k: int(getattr(self, k)) for k in ("surface_pixels", "sky_pixels", "unmatched_pixels")}
+
+
+class MotionResult(C.Structure):
+    """hr_motion_result"""
+    _fields_ = [("reused_pixels", C.c_uint64), ("rejected_pixels", C.c_uint64), ("history_samples", C.c_uint64), ("history_passes", C.c_uint32),
+                ("passes", C.c_uint32), ("surface_pixels", C.c_uint64), ("sky_pixels", C.c_uint64), ("unmatched_pixels", C.c_uint64)]
+
+    def as_dict(self):
+        return {k: int(getattr(self, k)) for k, _ in self._fields_}
+
+
+class MotionInfo(C.Structure):
+    """hr_motion_info_t"""
+    _fields_ = [("snapshot", C.c_int32), ("traced", C.c_int32), ("triangles", C.c_uint32), ("meshes", C.c_uint32), ("bytes", C.c_uint64)]
+
+    def as_dict(self):
+        return {"snapshot": bool(self.snapshot), "traced": bool(self.traced), "triangles": int(self.triangles), "meshes": int(self.meshes), "bytes": int(self.bytes)}
+
+
 # The optional headers: feature ->(its symbols, the version the binding was written against, what "this library has no ..." calls it);
 # the version function is <feature>_api_version.  Engine._feature_call checks a feature on its first call
 FEATURES = {
@@ -459,6 +491,7 @@ FEATURES = {
     "mesh": (MESH_SYMBOLS, HR_MESH_API_VERSION, "mesh preparation"),
     "deform": (DEFORM_SYMBOLS, HR_DEFORM_API_VERSION, "deformable meshes"),
     "query": (QUERY_SYMBOLS, HR_QUERY_API_VERSION, "ray queries"),
+    "motion": (MOTION_SYMBOLS, HR_MOTION_API_VERSION, "motion reprojection"),
 }
 
 
@@ -1259,6 +1292,62 @@ class Engine:
         """{"rays", "hits", "invalid"} of the last successful query; completes the queries in flight."""
         r = QueryResult()
         self._feature_call("query", "query_last", C.byref(r))
+        return r.as_dict()
+
+    # -- motion reprojection (include/hrcore_motion.h)
+    def motion_snapshot(self):
+        """Remember the committed pose: every triangle's world-space (p0, e1, e2) and the table of meshes.  Survives clear(), commits
+        and resize(); a second snapshot replaces it."""
+        self._feature_call("motion", "motion_snapshot")
+
+    def motion_trace(self, pass_params):
+        """One pixel-centre ray per pixel of the camera of `pass_params` against the committed scene: where was each pixel's surface
+        point in the snapshot's pose?  Writes the motion planes (motion_planes()); returns {"surface_pixels", "sky_pixels",
+        "unmatched_pixels"}."""
+        r = MotionTraceResult()
+        self._feature_call("motion", "motion_trace", C.byref(pass_params), C.byref(r))
+        return r.as_dict()
+
+    def motion_merge(self, pass_params, params=None):
+        """history_merge, gathering where the snapshot says each pixel's surface point was; once per clear(), instead of history_merge or
+        reproject_merge.  params: a HistoryParams (heatray_amd.motion.default_params()), None = those defaults.  Returns the
+        MotionResult as a dict: history_merge's keys and motion_trace's."""
+        r = MotionResult()
+        self._feature_call("motion", "motion_merge", C.byref(pass_params), C.byref(params) if params is not None else None, C.byref(r))
+        return r.as_dict()
+
+    def motion_planes(self):
+        """The motion planes of the last trace as 2 x H x W x 4 float32: Mv0 (the surface point in the previous pose, 1 / the hit point,
+        -1 / 0 0 0 0 for sky), Mv1 (the previous pose's geometric normal, depth; +inf: sky)."""
+        out = np.empty((2, self.height, self.width, 4), dtype=np.float32)
+        self._feature_call("motion", "motion_readback", _ptr(out))
+        return out
+
+    def motion_vectors(self, old_pass_params=None):
+        """The screen-space motion of every pixel as H x W x 4 float32: (dx, dy, the point's depth in the old camera, Mv0.w), from the
+        planes of the last trace.  old_pass_params None: the captured history's camera."""
+        out = np.empty((self.height, self.width, 4), dtype=np.float32)
+        self._feature_call("motion", "motion_vectors_readback", C.byref(old_pass_params) if old_pass_params is not None else None, _ptr(out))
+        return out
+
+    def motion_vectors_to_device(self, device_ptr, old_pass_params=None, stream=None):
+        """Asynchronous: the same image into device memory (a raw pointer, 16-byte aligned) on `stream` (None: the context's)."""
+        self._feature_call("motion", "motion_vectors", C.byref(old_pass_params) if old_pass_params is not None else None, C.c_void_p(device_ptr),
+                           C.c_void_p(stream or 0))
+
+    def motion_snapshot_triangles(self):
+        """The snapshot as T x 12 float32 in submission order: p0.xyz e1.xyz e2.xyz 0 0 0."""
+        out = np.empty((self.motion_info()["triangles"], 12), dtype=np.float32)
+        self._feature_call("motion", "motion_snapshot_readback", _ptr(out) if out.size else C.pointer(C.c_float()))
+        return out
+
+    def motion_drop(self):
+        self._feature_call("motion", "motion_drop")
+
+    def motion_info(self):
+        """{"snapshot", "traced", "triangles", "meshes", "bytes"}"""
+        r = MotionInfo()
+        self._feature_call("motion", "motion_info", C.byref(r))
         return r.as_dict()
 
     def debug_trace(self, origins, dirs, tmax=None, skip_prim=None, any_hit=False):

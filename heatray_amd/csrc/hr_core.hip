@@ -21,6 +21,7 @@
 //   hr_mesh.inl       mesh preparation: smooth normals and tangent frames for a mesh without them (include/hrcore_mesh.h)
 //   hr_deform.inl     deformable meshes: vertex updates in place, device posing, read-back (include/hrcore_deform.h)
 //   hr_query.inl      ray queries: the caller's rays traced against the committed scene, with surface records (include/hrcore_query.h)
+//   hr_motion.inl     motion reprojection: the history gathered where a moved or deformed surface was (include/hrcore_motion.h)
 //   hr_adaptive.inl   the sample mask and the error estimate that builds it (include/hrcore_adaptive.h)
 //   hr_history.inl    history reprojection across a camera change (include/hrcore_history.h)
 //   hr_reproject.inl  its progressive form and the preview of unsampled pixels (include/hrcore_reproject.h)
@@ -672,3 +673,6 @@ int hr_debug_trace(hr_ctx *c, int32_t n, const float *o, const float *d, const f
 
 // ------------------------------------------------------------------------------------------ ray queries
 #include "hr_query.inl"
+
+// ------------------------------------------------------------------------------------------ motion reprojection
+#include "hr_motion.inl"

@@ -517,6 +517,7 @@ struct hr_ctx {
     MeshPrepState meshPrep;
     DeformState deform;
     QueryState query;
+    MotionState motion;
     // Context group (include/hrcore_group.h): non-null when this handle is a group.  Its own fields then describe the ASSEMBLED frame on the
     // group's first device (W, H, frame, fbInternal, the read-back buffers) and `stream` is the assembly stream; no pass pipeline runs on it.
     GroupState *grp = nullptr;

@@ -1,9 +1,11 @@
 // hr_features.h — the state of the optional post-process features, one struct per feature, each a member of hr_ctx (hr_ctx.h includes this
 // file).  What a struct owns is a handle of hr_owned.h, so assigning it a default-constructed one frees everything and resets every flag:
-// that is release().  The four lifetime functions of hr_postprocess.inl are the only callers (hr_history_drop apart) and the only code
+// that is release().  The four lifetime functions of hr_postprocess.inl are the only callers (hr_history_drop and hr_motion_drop apart) and the only code
 // that resets a feature's flags.  A read-back's pinned staging only grows (growPinned, hr_ctx.h): a shrinking frame keeps its buffer.
 #pragma once
 #include "hr_owned.h"
+
+#include <vector>
 
 // The result counters of a post-process feature: a few device words its kernel adds into and their pinned host copy.  A call runs
 // ensure, zero, its launches and fetch (each under HIP_TRY), synchronises the stream and fills its result struct from `host`.
@@ -148,4 +150,31 @@ struct QueryState {
         return hipEventSynchronize(evDone);
     }
     void release() { wait(), *this = QueryState(); } // (nothing may read the memory or wait on evDone when the members go)
+};
+
+// Motion reprojection (include/hrcore_motion.h).  The snapshot (the committed pose's triangles and its table of meshes) does not depend on
+// the frame: it survives hr_clear, commits and hr_frame_resize and goes with hr_motion_drop, a second snapshot and the context.  The
+// motion planes and what hangs on them go with the frame's size (releaseFrame).  Nothing here is counted against memBudget.
+struct MotionState {
+    struct Mesh {
+        int32_t id;            // hr_geom_id
+        uint32_t first, count; // its triangles in `snap`
+    };
+    DeviceBuf<float> snap;   // kMotionSnapshotFloatsPerTri per triangle, prim order
+    std::vector<Mesh> meshes; // the committed meshes that have triangles, in id order
+    uint32_t nTris = 0;
+    bool have = false;        // there is a snapshot (of a scene without triangles: `snap` is null)
+    DeviceBuf<float> planes;  // kMotionPlaneBytesPerPixel x W x H: Mv0, Mv1
+    bool traced = false;      // `planes` holds a trace
+    float view[16] = {0}, fovTan = 0.0f, aspect = 0.0f; // ... and its camera
+    DeviceBuf<int32_t> remap; // per committed mesh: its first triangle in `snap`, or -1 (rebuilt by every trace)
+    DeviceBuf<float> out;     // the motion vectors on their way to the host (W x H float4)
+    PinnedBuf<float> pinned;  // the read-backs' host buffer
+    ResultCounters<unsigned long long> result; // kMotionTraceResultWords, then kMotionMergeResultWords
+    void releaseFrame() // what was made for the frame's size
+    {
+        planes.reset(), out.reset();
+        traced = false;
+    }
+    void release() { *this = MotionState(); }
 };

@@ -16,6 +16,7 @@
 #include "../../include/hrcore_mesh.h"
 #include "../../include/hrcore_deform.h"
 #include "../../include/hrcore_query.h"
+#include "../../include/hrcore_motion.h"
 
 #include <cstddef>
 
@@ -351,6 +352,32 @@ struct QyCamera {
     float fovTan, aspect, focus, W, H;
 };
 void launchQueryCamera(hipStream_t st, const QyCamera &cam, int n, const float *xy, float *rays);
+
+// ---- hr_motion.hip (include/hrcore_motion.h)
+struct MvCam; // hr_motion.h: the two cameras of a merge or of the motion vectors
+static const size_t kMotionSnapshotFloatsPerTri = 12; // (p0, e1, e2) padded to three float4
+static const size_t kMotionPlaneBytesPerPixel = 2 * 16; // Mv0, Mv1: two planes of W x H float4 one after the other
+// the committed triangles (leaf order, found through slotOfPrim) -> out: kMotionSnapshotFloatsPerTri floats per triangle in prim order
+void launchMotionSnapshot(hipStream_t st, uint32_t nTris, const Tri *tris, const uint32_t *slotOfPrim, float *out);
+// One trace of the pixel-centre rays of a W x H frame; every pointer is device memory.  geoms / nGeoms: the query's table of the committed
+// meshes; remap[m]: the first triangle of mesh m in the snapshot `snap`, or -1 where the snapshot does not hold it with the same count.
+// planes: Mv0 then Mv1.  result = {surface, sky, unmatched pixels}, zeroed by the caller.
+struct MvTraceArgs {
+    const SceneDev *scene;
+    const QyGeom *geoms;
+    const int32_t *remap;
+    const float4 *snap;
+    int32_t nGeoms, W, H;
+    float view[16], aspect, fov; // the camera: view_matrix, aspect_ratio, fov_tan
+    float *planes;
+    unsigned long long *result;
+};
+static const size_t kMotionTraceResultWords = 3, kMotionMergeResultWords = 3;
+void launchMotionTrace(hipStream_t st, const MvTraceArgs &a);
+// launchHistoryMerge, gathering where the motion planes `mv` say; result as kHistoryResultWords, zeroed by the caller
+void launchMotionMerge(hipStream_t st, int W, int H, const MvCam &cam, const HsParams &P, const float *mv, const float *hist, float *frame, float *albedo, float *normalDepth,
+                       float *moments, unsigned long long *result);
+void launchMotionVectors(hipStream_t st, int W, int H, const MvCam &cam, const float *mv, float *out); // out: W x H float4
 
 // ---- hr_build.hip
 // Per-geometry descriptor for the assemble kernel; all pointers are device pointers.  Attributes are addressed with a stride

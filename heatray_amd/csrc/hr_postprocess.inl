@@ -21,7 +21,7 @@ static int copyOutOnStream(hr_ctx *c, void *dst, const void *src, size_t bytes, 
     return HR_OK;
 }
 
-// ---- when the features' state goes.  These four are the only callers of a feature's release() (hr_history_drop apart; the context's
+// ---- when the features' state goes.  These four are the only callers of a feature's release() (hr_history_drop and hr_motion_drop apart; the context's
 // destructor would free what is left, but hr_ctx_destroy and groupDestroy come through featuresDestroyed first) and the only
 // code that resets a feature's flags; a plain context, a group's handle and its members all come through them.  Every caller has
 // drained or synchronised what could still use the memory.
@@ -39,6 +39,7 @@ static void featuresFrameResized(hr_ctx *c)
     c->frame.mask = nullptr;
     c->history.release();
     c->reproject.release();
+    c->motion.releaseFrame(); // (include/hrcore_motion.h: the planes go, the snapshot stays)
 }
 // The frame starts afresh (hr_clear, groupClear).
 static void featuresFrameCleared(hr_ctx *c)
@@ -58,6 +59,7 @@ static void featuresDestroyed(hr_ctx *c)
     c->meshPrep.release();
     c->deform.release();
     c->query.release();
+    c->motion.release();
 }
 
 // ---- "a full-frame post-process wants this frame"

@@ -78,6 +78,7 @@
  *   - No history for pixels the new view has not sampled yet (interactive mode's blocks before all sub-passes ran, masked pixels).
  *   - A non-finite history colour is not filtered: it spreads into the at most four pixels that tap it, like any sample would.
  *   - The history does not know about scene edits: a caller that changes geometry, materials or lights calls hr_history_drop.
+ *     (Geometry that moved or deformed: include/hrcore_motion.h gathers this history where the surface was; materials and lights still drop.)
  *   - Context groups and tile-sharded contexts (world > 1) are refused: the gather reads across tiles.
  *
  * Memory: three float4 per pixel (48 B) on the context's device, allocated by the first capture, not counted against
