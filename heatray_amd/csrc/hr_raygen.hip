@@ -163,9 +163,9 @@ HRD void packetTriangles(ConstTris tris, int first, int count, v3 o, v3 d, float
         const v3 qvec = cross(tvec, e1);
         const float v = dot(d, qvec) * inv;
         if (!(v >= 0.0f) || u + v > 1.0f) continue;
-        const float t = dot(e2, qvec) * inv;
+        float t = dot(e2, qvec) * inv;
         if (!(t > tmin) || !(t < tmax)) continue;
-        if (!hitInTriBox(v0, e1, e2, o, d, t, hitPad)) continue;
+        if (!hitInTriBox(v0, e1, e2, o, d, t, hitPad) && !hitOnPlane<true>(tris, first + k, o, d, tmin, tmax, hitPad, t)) continue;
         const uint32_t bp = best.prim & 0x7FFFFFFFu;
         if (best.prim == kMissPrim || t < best.t || (t == best.t && prim < bp)) {
             best.prim = prim | ((det > 0.0f) ? 0x80000000u : 0u);

@@ -169,6 +169,100 @@ HRD bool hitInTriBox(v3 v0, v3 e1, v3 e2, v3 o, v3 d, float t, float h)
            hitInTriBoxAxis(v0.z, e1.z, e2.z, o.z, d.z, t, h);
 }
 
+// THE PLANE RETRY, the cold path behind a candidate that passed Möller–Trumbore (u, v, t in range) and FAILED the box
+// condition.  On a thin triangle the float32 error of Möller–Trumbore's t grows like eps * distance / aspect and exceeds `h`; where the
+// triangle's box is thin too (it lies in a nearly axis-aligned plane: a floor board, a wall strip) the box then rejects the real hit.
+// The distance to the triangle's PLANE, t' = n.(v0 - o) / n.d with n = e1 x e2, is well conditioned exactly there: n has one dominant
+// component and its scale cancels.  The candidate is a hit at t' iff t' is in (tmin, tmax) and o + t' d passes the box condition —
+// so an accepted hit still lies inside its triangle's half-padded box, whichever of the two distances it carries, and the answer stays
+// a function of the ray and the triangle alone (condition 2 holds for BOTH distances: the retry is reached only with Möller–Trumbore's
+// t in range; the running closest-hit limit plays no part, it only culls boxes).  u and v stay Möller–Trumbore's.  A sliver whose
+// normal is rounding noise is never retried (its phantom hits, tests/golden/phantom_hits.npz, would come back): the normal must be at
+// least s |e1| |e2| long, s = 3e-5 — the fixture's slivers have s <= 3.9e-6, a real 1:10 000 triangle s >= 1.4e-4.
+// Same operations, same order as oracle_bvh.cpp::hitOnPlane; on success t is replaced.
+//
+// HOW IT IS WRITTEN.  k_trace has no register to spare around its triangle test and the packet kernel none above its 64, and what the
+// compiler makes of a cold block still counts: given nine live triangle values and a free hand it overlaps everything (packed
+// multiplies on register pairs, copies of scalar operands, 64-bit addresses) and took 6 to 26 more VGPRs.  So the retry (a) reads the
+// triangle AGAIN, one or two values at a time, through a 32-bit element index the compiler cannot see through (Opaque: per lane in a
+// VGPR, or wave-uniform in an SGPR for the packet kernel's scalar reads) — the first read's registers die with the box test that failed
+// and no 64-bit address is held between the reads — and (b) pins every intermediate (pin), so that the operations are issued one by
+// one in the order written: seven VGPRs at its widest.  The values and their order are the contract's; none of this changes a bit.
+static const float kRetryS2 = 9e-10f; // s * s
+template <bool UNIFORM> struct Opaque { // the index, made unknown to the compiler again and ordered behind the value `after`
+    static HRD void index(uint32_t &i, float &after) { asm volatile("" : "+v"(i), "+v"(after)); }
+};
+template <> struct Opaque<true> {
+    static HRD void index(uint32_t &i, float &after) { asm volatile("" : "+s"(i), "+v"(after)); }
+};
+HRD float pin(float x)
+{
+    asm volatile("" : "+v"(x));
+    return x;
+}
+// tris[index] is the triangle the caller has just tested (index < nTris < 2^28: twelve floats each, the element index fits 32 bits)
+template <bool UNIFORM, class TriPtr> HRD bool hitOnPlane(TriPtr tris, int index, v3 o, v3 d, float tmin, float tmax, float h, float &t)
+{
+    // the triangle as floats: v0, e1, e2 are its first nine (hr_types.h: Tri)
+    const auto base = &tris->p.x;
+    uint32_t e = (uint32_t)index * (uint32_t)(sizeof(*tris) / sizeof(float));
+    float tp = t;
+    Opaque<UNIFORM>::index(e, tp);
+#define HR_V0X base[e + 0u]
+#define HR_V0Y base[e + 1u]
+#define HR_V0Z base[e + 2u]
+#define HR_E1X base[e + 3u]
+#define HR_E1Y base[e + 4u]
+#define HR_E1Z base[e + 5u]
+#define HR_E2X base[e + 6u]
+#define HR_E2Y base[e + 7u]
+#define HR_E2Z base[e + 8u]
+    float a, b, c;
+    a = pin(HR_E1X * HR_E1X), b = pin(HR_E1Y * HR_E1Y), a = pin(a + b), b = pin(HR_E1Z * HR_E1Z), a = pin(a + b);
+    a = pin(kRetryS2 * a); // kRetryS2 * dot(e1, e1) * dot(e2, e2) ...
+    b = pin(HR_E2X * HR_E2X), c = pin(HR_E2Y * HR_E2Y), b = pin(b + c), c = pin(HR_E2Z * HR_E2Z), b = pin(b + c);
+    a = pin(a * b);
+    Opaque<UNIFORM>::index(e, a);
+    b = pin(HR_E1Y * HR_E2Z), c = pin(HR_E1Z * HR_E2Y);
+    const float nx = pin(b - c);
+    float nx1 = nx;
+    Opaque<UNIFORM>::index(e, nx1);
+    b = pin(HR_E1Z * HR_E2X), c = pin(HR_E1X * HR_E2Z);
+    const float ny = pin(b - c);
+    float ny1 = ny;
+    Opaque<UNIFORM>::index(e, ny1);
+    b = pin(HR_E1X * HR_E2Y), c = pin(HR_E1Y * HR_E2X);
+    const float nz = pin(b - c);
+    b = pin(nx1 * nx1), c = pin(ny1 * ny1), b = pin(b + c), c = pin(nz * nz);
+    const float nn = pin(b + c);
+    if (!(nn >= a)) return false; // ... against dot(n, n), n = cross(e1, e2)
+    a = pin(nx1 * d.x), b = pin(ny1 * d.y), a = pin(a + b), b = pin(nz * d.z);
+    const float den = pin(a + b);
+    if (den == 0.0f) return false;
+    a = pin(HR_V0X - o.x), a = pin(nx1 * a), b = pin(HR_V0Y - o.y), b = pin(ny1 * b), a = pin(a + b), b = pin(HR_V0Z - o.z), b = pin(nz * b);
+    tp = pin(a + b);
+    a = pin(1.0f / den);
+    tp = pin(tp * a); // dot(n, v0 - o) * (1 / dot(n, d))
+    if (!(tp > tmin) || !(tp < tmax)) return false;
+    Opaque<UNIFORM>::index(e, tp); // the box condition, one axis at a time
+    if (!hitInTriBoxAxis(HR_V0X, HR_E1X, HR_E2X, o.x, d.x, tp, h)) return false;
+    Opaque<UNIFORM>::index(e, tp);
+    if (!hitInTriBoxAxis(HR_V0Y, HR_E1Y, HR_E2Y, o.y, d.y, tp, h)) return false;
+    Opaque<UNIFORM>::index(e, tp);
+    if (!hitInTriBoxAxis(HR_V0Z, HR_E1Z, HR_E2Z, o.z, d.z, tp, h)) return false;
+#undef HR_V0X
+#undef HR_V0Y
+#undef HR_V0Z
+#undef HR_E1X
+#undef HR_E1Y
+#undef HR_E1Z
+#undef HR_E2X
+#undef HR_E2Y
+#undef HR_E2Z
+    t = tp;
+    return true;
+}
+
 // Per-ray constants of the slab test: 1 / d and the ray origin over d
 HRD RayK rayFrame(v3 o, float idx, float idy, float idz) { return RayK{idx, idy, idz, o.x * idx, o.y * idy, o.z * idz}; }
 
@@ -275,9 +369,9 @@ HRD void traverse(const SceneDev &S, v3 o, v3 d, float tmin, float tmax, uint32_
                 const v3 qvec = cross(tvec, e1);
                 const float v = dot(d, qvec) * inv;
                 if (!(v >= 0.0f) || u + v > 1.0f) continue;
-                const float t = dot(e2, qvec) * inv;
+                float t = dot(e2, qvec) * inv;
                 if (!(t > tmin) || !(t < tmax)) continue;
-                if (!hitInTriBox(v0, e1, e2, o, d, t, S.hitPad)) continue;
+                if (!hitInTriBox(v0, e1, e2, o, d, t, S.hitPad) && !hitOnPlane<false>(S.tris, first + k, o, d, tmin, tmax, S.hitPad, t)) continue;
                 if (ANY) {
                     if ((__float_as_uint(trr.z) & TF_NON_OCCLUDER) && alphaPasses(S, prim, u, v)) continue;
                     best.prim = prim;

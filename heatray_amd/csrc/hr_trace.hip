@@ -118,6 +118,14 @@ HRD RayK traceFrame(const SceneDev &S, v3 o, v3 d)
     return rayFrame32(S, o, idx, idy, idz);
 }
 
+// An index whose address arithmetic is done where it is used (the ray-merge slots of the draining phase: their addresses, computed once
+// ahead of the triangle loop, held two registers through it that the loop has not got)
+HRD uint32_t hereOnly(uint32_t i)
+{
+    asm volatile("" : "+v"(i));
+    return i;
+}
+
 template <bool STATS>
 __global__ __launch_bounds__(kTraceBlock, 5) void k_trace(const SceneDev *__restrict__ Sp, const int *__restrict__ leafKeys, const Node32 *__restrict__ nodes32,
                                                   const Tri *__restrict__ tris, StepTable *__restrict__ tbl, Stats *stats)
@@ -440,18 +448,18 @@ __global__ __launch_bounds__(kTraceBlock, 5) void k_trace(const SceneDev *__rest
                     const v3 qvec = cross(tvec, e1);
                     const float v = dot(d, qvec) * inv;
                     if (!(v >= 0.0f) || u + v > 1.0f) continue;
-                    const float t = dot(e2, qvec) * inv;
+                    float t = dot(e2, qvec) * inv;
                     if (!(t > tmin) || !(t < tmax)) continue;
                     // (the hit test's second half, hr_trace.h.  On the live triangle: re-reading it from L1 one axis at a time, to shorten
                     // the live ranges, measured 0.5-1.5 % slower — profiles/r5b_hitbox_ab.txt.  The kernel keeps its five waves per SIMD
                     // because its launch bounds say so: the compiler then allocates for 96 registers without spilling.)
-                    if (!hitInTriBox(v0, e1, e2, o, d, t, hitPad)) continue;
+                    if (!hitInTriBox(v0, e1, e2, o, d, t, hitPad) && !hitOnPlane<false>(tris, first + k, o, d, tmin, tmax, hitPad, t)) continue; // (the plane retry: cold)
                     if (isAny) {
                         if ((__float_as_uint(trr.z) & TF_NON_OCCLUDER) && alphaPasses(S, prim, u, v)) continue;
                         best.prim = 0u; // occluded (anything but kMissPrim)
                         cur = kSentinel;
                         sp = 0;
-                        if (draining) atomicMin(&mKey[wave][slot], 0ull); // the ray's other fragments stop at their next round
+                        if (draining) atomicMin(&mKey[wave][hereOnly(slot)], 0ull); // the ray's other fragments stop at their next round
                         break;
                     }
                     const uint32_t bp = best.prim & 0x7FFFFFFFu;
@@ -462,9 +470,10 @@ __global__ __launch_bounds__(kTraceBlock, 5) void k_trace(const SceneDev *__rest
                         if (draining) { // publish at once: subtrees handed to other lanes are speculative until a hit bounds them
                             const unsigned long long kk = ((unsigned long long)__float_as_uint(t) << 32) | ((unsigned long long)prim << 1) |
                                                           (unsigned long long)(det > 0.0f ? 1u : 0u);
-                            atomicMin(&mKey[wave][slot], kk);
+                            const uint32_t sl = hereOnly(slot);
+                            atomicMin(&mKey[wave][sl], kk);
                             __builtin_amdgcn_wave_barrier();
-                            if (((volatile unsigned long long *)mKey[wave])[slot] == kk) mUV[wave][slot] = make_float2(u, v);
+                            if (((volatile unsigned long long *)mKey[wave])[sl] == kk) mUV[wave][sl] = make_float2(u, v);
                         }
                     }
                 }

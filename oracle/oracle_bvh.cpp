@@ -9,7 +9,9 @@
 //   * the HIT is defined independently of the acceleration structure: Möller–Trumbore
 //     in the operation order below, accepted for t in (tmin, tmax) when the hit point
 //     o + t d lies inside the triangle's bounding box grown by half the leaf padding
-//     (hitInTriBox), closest hit = lexicographic minimum of (t, triangle id).  A
+//     (hitInTriBox) — or, where it does not, when the point at the distance to the
+//     triangle's plane does (hitOnPlane: the hit then carries that distance); closest
+//     hit = lexicographic minimum of (t, triangle id).  A
 //     brute-force loop over all triangles (ctx.brute) gives the same answer as any
 //     conservative BVH — also for the phantom hits float32 Möller–Trumbore produces
 //     on sliver triangles, which the box condition turns away for everybody.
@@ -234,6 +236,24 @@ static inline bool hitInTriBox(const Tri &tr, vec3 o, vec3 d, float t, float h)
            hitInTriBoxAxis(tr.v0.z, tr.e1.z, tr.e2.z, o.z, d.z, t, h);
 }
 
+// The plane retry (hr_trace.h::hitOnPlane has the reasoning): a candidate that passed Möller–Trumbore with t in range and
+// failed the box condition is tried once more at the distance to the triangle's plane, t' = n.(v0 - o) / n.d with n = e1 x e2 — well
+// conditioned where a thin triangle's box is thin, which is where float32 Möller–Trumbore's t misses the box of a real hit.  It is a hit
+// at t' iff t' is in (tmin, tmax) and o + t' d passes the box condition.  Never for a sliver whose normal is rounding noise.
+static const float kRetryS2 = 9e-10f; // (3e-5)^2
+static inline bool hitOnPlane(const Tri &tr, vec3 o, vec3 d, float tmin, float tmax, float h, float &t)
+{
+    const vec3 n = cross(tr.e1, tr.e2);
+    if (!(dot(n, n) >= kRetryS2 * dot(tr.e1, tr.e1) * dot(tr.e2, tr.e2))) return false;
+    const float den = dot(n, d);
+    if (den == 0.0f) return false;
+    const float tp = dot(n, tr.v0 - o) * (1.0f / den);
+    if (!(tp > tmin) || !(tp < tmax)) return false;
+    if (!hitInTriBox(tr, o, d, tp, h)) return false;
+    t = tp;
+    return true;
+}
+
 // Reciprocal direction for the slab test only: components with |d| < 1e-20 are replaced
 // so that no infinity / NaN enters the box test (the hit itself never uses this).
 static inline float safeInv(float d)
@@ -271,7 +291,7 @@ static bool traverse(const Context &ctx, vec3 o, vec3 d, float tmin, float tmax,
             float t, u, v;
             if (!intersectTri(bvh.tris[i], o, d, t, u, v)) continue;
             if (!(t > tmin) || !(t < tmax)) continue;
-            if (!hitInTriBox(bvh.tris[i], o, d, t, ctx.hitPad)) continue;
+            if (!hitInTriBox(bvh.tris[i], o, d, t, ctx.hitPad) && !hitOnPlane(bvh.tris[i], o, d, tmin, tmax, ctx.hitPad, t)) continue;
             if (ANY) {
                 if ((ctx.attrs[prim].flags & TF_NON_OCCLUDER) && alphaPasses(ctx, prim, u, v)) continue;
                 best.prim = prim, best.t = t, best.u = u, best.v = v;
@@ -325,7 +345,7 @@ template <bool ANY> static bool bruteForce(const Context &ctx, vec3 o, vec3 d, f
         float t, u, v;
         if (!intersectTri(ctx.tris[prim], o, d, t, u, v)) continue;
         if (!(t > tmin) || !(t < tmax)) continue;
-        if (!hitInTriBox(ctx.tris[prim], o, d, t, ctx.hitPad)) continue;
+        if (!hitInTriBox(ctx.tris[prim], o, d, t, ctx.hitPad) && !hitOnPlane(ctx.tris[prim], o, d, tmin, tmax, ctx.hitPad, t)) continue;
         if (ANY) {
             if ((ctx.attrs[prim].flags & TF_NON_OCCLUDER) && alphaPasses(ctx, prim, u, v)) continue;
             best.prim = prim, best.t = t, best.u = u, best.v = v;

@@ -123,6 +123,19 @@ def test_oracle_turns_phantoms_away_with_its_tree_and_by_brute_force():
     h, hb = o.debug_trace(org, d), ob.debug_trace(org, d)
     assert h.tobytes() == hb.tobytes()
     assert (h["prim"] >= n_sl).mean() > 0.99 and (h["prim"] == k + n_sl).mean() > 0.8
+    # ... and against float64 truth, not the oracle's own answer (tests/test_hit_truth.py has the thin triangles): every ray that float64
+    # Möller–Trumbore calls a robust hit of the triangle it was aimed at (u, v > 0.1, u + v < 0.9, t > 10 eps, |d.n| > 0.3) is reported —
+    # on that triangle or on something in front of it — and where it is reported on that triangle, at float64's distance: these
+    # triangles are as wide as they are long, so t carries a few 2^-24 of the coordinates, 1e-5 |diagonal| with a factor of ten to spare
+    import thin_cases
+    every = np.concatenate([np.stack([fx["p0"], fx["p1"], fx["p2"]], axis=1), ordinary])
+    diag = thin_cases.diagonal(every)
+    robust, _, t64 = thin_cases.truth(every, org, d, k + n_sl, o.scene_info().ray_epsilon, 1.0)
+    assert robust.sum() > 1000, robust.sum()
+    assert (h["prim"][robust] >= 0).all(), f"{(h['prim'][robust] < 0).sum()} robust true hits are not reported"
+    assert (h["t"][robust] <= t64[robust] + 1e-5 * diag).all()
+    on = robust & (h["prim"] == k + n_sl)
+    assert on.sum() > 0.8 * robust.sum() and np.abs(h["t"][on] - t64[on]).max() <= 1e-5 * diag
     o.close(), ob.close()
 
 
