@@ -19,8 +19,6 @@
 
 namespace hr {
 
-static constexpr int kHsTileW = 32, kHsTileH = 8; // pixels of a workgroup of k_history_merge: four waves of 8 x 8
-
 __global__ __launch_bounds__(256) void k_history_capture(int n, const dn4 *__restrict__ frame, const dn4 *__restrict__ albedo, const dn4 *__restrict__ normalDepth,
                                                          const dn4 *__restrict__ moments, dn4 *__restrict__ hist)
 {
@@ -38,21 +36,14 @@ __global__ __launch_bounds__(256) void k_history_merge(int W, int H, HsCam cam, 
     __shared__ uint32_t sRed[3];
     wgCountersZero<3>(sRed);
     __syncthreads();
-    const uint32_t tilesX = (uint32_t)(W + kHsTileW - 1) / (uint32_t)kHsTileW; // (a one-dimensional grid: no bound on the image's height)
-    const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
-    const int x = (int)(blockIdx.x % tilesX) * kHsTileW + (int)(wave * 8u + (lane & 7u));
-    const int y = (int)(blockIdx.x / tilesX) * kHsTileH + (int)(lane >> 3);
-    const bool in = x < W && y < H;
+    int x, y;
+    const bool in = postTilePixel(W, H, x, y);
     const int i = in ? y * W + x : 0; // (a lane outside the image reads pixel 0 and writes nothing)
     dn4 F = G(frame)[i], A = G(albedo)[i], Gn = G(normalDepth)[i], M = G(moments)[i];
     const HsPlanes src(hist, (size_t)W * (size_t)H);
     float nh = 0.0f;
     const int st = hsMerge(src, cam, P, in ? x : 0, in ? y : 0, W, H, F, A, Gn, M, &nh);
-    const bool reused = in && st == HS_REUSED, rejected = in && st == HS_REJECTED;
-    if (reused) G(frame)[i] = F, G(albedo)[i] = A, G(normalDepth)[i] = Gn, G(moments)[i] = M;
-    const uint32_t samples = waveSum(reused ? hsCount(nh) : 0u); // (at most 65536 per pixel: a workgroup's sum fits 32 bits)
-    const uint32_t nReused = waveCount(reused), nRejected = waveCount(rejected);
-    if (lane == 0u) atomicAdd(&sRed[0], nReused), atomicAdd(&sRed[1], nRejected), atomicAdd(&sRed[2], samples);
+    mergeTail(in && st == HS_REUSED, in && st == HS_REJECTED, nh, i, F, A, Gn, M, frame, albedo, normalDepth, moments, sRed);
     wgCountersFlush<3>(sRed, result);
 }
 
@@ -66,8 +57,7 @@ void launchHistoryCapture(hipStream_t st, int W, int H, const float *frame, cons
 void launchHistoryMerge(hipStream_t st, int W, int H, const HsCam &cam, const HsParams &P, const float *hist, float *frame, float *albedo, float *normalDepth, float *moments,
                         unsigned long long *result)
 {
-    const dim3 grid(((W + kHsTileW - 1) / kHsTileW) * ((H + kHsTileH - 1) / kHsTileH));
-    hipLaunchKernelGGL(k_history_merge, grid, dim3(256), 0, st, W, H, cam, P, reinterpret_cast<const dn4 *>(hist), reinterpret_cast<dn4 *>(frame),
+    hipLaunchKernelGGL(k_history_merge, postTileGrid(W, H), dim3(256), 0, st, W, H, cam, P, reinterpret_cast<const dn4 *>(hist), reinterpret_cast<dn4 *>(frame),
                        reinterpret_cast<dn4 *>(albedo), reinterpret_cast<dn4 *>(normalDepth), reinterpret_cast<dn4 *>(moments), result);
 }
 

@@ -39,6 +39,19 @@ static int historyCheckFrame(hr_ctx *c, const char *what, uint32_t *passes)
     return frameReady(c, need, &frame, passes);
 }
 
+// what every gather from the captured history is launched with (the merges here, in hr_reproject.inl and hr_motion.inl, and the preview):
+// the captured camera against the new one, and the checked parameters as the kernels take them
+struct HsLaunch {
+    HsCam cam;
+    HsParams P;
+};
+
+static HsLaunch historyLaunch(const hr_ctx *c, const hr_pass_params *camera, const hr_history_params &p)
+{
+    return HsLaunch{hsCameras(c->history.view, c->history.aspect, c->history.fovTan, camera->view_matrix, camera->aspect_ratio, camera->fov_tan),
+                    HsParams{(float)p.max_history, p.normal_cos, p.plane_tol, p.min_weight}};
+}
+
 extern "C" {
 
 uint32_t hr_history_api_version(void) { return HR_HISTORY_API_VERSION; }
@@ -82,9 +95,8 @@ int hr_history_merge(hr_ctx *c, const hr_pass_params *camera, const hr_history_p
     if (c->history.merged) FAIL(c, HR_ERR_INVALID, "history merge: the history has already been merged into this frame (one merge per hr_clear: a second would count it twice)");
     HIP_TRY(c, c->history.result.ensure(kHistoryResultWords));
     HIP_TRY(c, c->history.result.zero(c->stream));
-    const HsCam cam = hsCameras(c->history.view, c->history.aspect, c->history.fovTan, camera->view_matrix, camera->aspect_ratio, camera->fov_tan);
-    const HsParams P{(float)p.max_history, p.normal_cos, p.plane_tol, p.min_weight};
-    launchHistoryMerge(c->stream, c->W, c->H, cam, P, c->history.hist, c->fb(), c->aov.plane[HR_AOV_PLANE_ALBEDO], c->aov.plane[HR_AOV_PLANE_NORMAL_DEPTH],
+    const HsLaunch l = historyLaunch(c, camera, p);
+    launchHistoryMerge(c->stream, c->W, c->H, l.cam, l.P, c->history.hist, c->fb(), c->aov.plane[HR_AOV_PLANE_ALBEDO], c->aov.plane[HR_AOV_PLANE_NORMAL_DEPTH],
                        c->aov.plane[HR_AOV_PLANE_MOMENTS], c->history.result.dev);
     HIP_TRY(c, hipGetLastError());
     c->history.merged = true;

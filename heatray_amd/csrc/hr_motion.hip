@@ -30,7 +30,6 @@
 
 namespace hr {
 
-static constexpr int kMvTileW = 32, kMvTileH = 8; // pixels of a workgroup of k_motion_trace and k_motion_merge: four waves of 8 x 8
 static constexpr int kMvWaves = 4;
 
 __global__ __launch_bounds__(256) void k_motion_snapshot(uint32_t nTris, const Tri *__restrict__ tris, const uint32_t *__restrict__ slotOfPrim, float4 *__restrict__ out)
@@ -43,16 +42,6 @@ __global__ __launch_bounds__(256) void k_motion_snapshot(uint32_t nTris, const T
     o[0] = p, o[1] = q, o[2] = make_float4(r.x, 0.0f, 0.0f, 0.0f);
 }
 
-// the pixel of this lane: a wave is an 8 x 8 block, a workgroup four of them side by side (a one-dimensional grid: no bound on the height)
-HRD bool mvPixel(int W, int H, int &x, int &y)
-{
-    const uint32_t tilesX = (uint32_t)(W + kMvTileW - 1) / (uint32_t)kMvTileW;
-    const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
-    x = (int)(blockIdx.x % tilesX) * kMvTileW + (int)(wave * 8u + (lane & 7u));
-    y = (int)(blockIdx.x / tilesX) * kMvTileH + (int)(lane >> 3);
-    return x < W && y < H;
-}
-
 // result: {surface, sky, unmatched pixels}, zeroed by the caller
 __global__ __launch_bounds__(256) void k_motion_trace(MvTraceArgs a)
 {
@@ -61,7 +50,7 @@ __global__ __launch_bounds__(256) void k_motion_trace(MvTraceArgs a)
     const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
     int *stackLane = &stack[wave][0][lane];
     int x, y;
-    const bool in = mvPixel(a.W, a.H, x, y);
+    const bool in = postTilePixel(a.W, a.H, x, y);
     const float *V = (const float *)a.view;
     v3 o, d;
     mvCameraRay(V, a.aspect, a.fov, in ? x : 0, in ? y : 0, (float)a.W, (float)a.H, o, d);
@@ -117,9 +106,8 @@ __global__ __launch_bounds__(256) void k_motion_merge(int W, int H, MvCam cam, H
     __shared__ uint32_t sRed[3];
     wgCountersZero<3>(sRed);
     __syncthreads();
-    const uint32_t lane = threadIdx.x & 63u;
     int x, y;
-    const bool in = mvPixel(W, H, x, y);
+    const bool in = postTilePixel(W, H, x, y);
     const size_t n = (size_t)W * (size_t)H;
     const int i = in ? y * W + x : 0; // (a lane outside the image reads pixel 0 and writes nothing)
     const dn4 Mv0 = G(mv)[i], Mv1 = G(mv)[n + i];
@@ -127,11 +115,7 @@ __global__ __launch_bounds__(256) void k_motion_merge(int W, int H, MvCam cam, H
     const HsPlanes src(hist, n);
     float nh = 0.0f;
     const int st = mvMerge(src, cam, P, Mv0, Mv1, in ? x : 0, in ? y : 0, W, H, F, A, Gn, M, &nh);
-    const bool reused = in && st == HS_REUSED, rejected = in && st == HS_REJECTED;
-    if (reused) G(frame)[i] = F, G(albedo)[i] = A, G(normalDepth)[i] = Gn, G(moments)[i] = M;
-    const uint32_t samples = waveSum(reused ? hsCount(nh) : 0u); // (at most 65536 per pixel: a workgroup's sum fits 32 bits)
-    const uint32_t nReused = waveCount(reused), nRejected = waveCount(rejected);
-    if (lane == 0u) atomicAdd(&sRed[0], nReused), atomicAdd(&sRed[1], nRejected), atomicAdd(&sRed[2], samples);
+    mergeTail(in && st == HS_REUSED, in && st == HS_REJECTED, nh, i, F, A, Gn, M, frame, albedo, normalDepth, moments, sRed);
     wgCountersFlush<3>(sRed, result);
 }
 
@@ -143,19 +127,17 @@ __global__ __launch_bounds__(256) void k_motion_vectors(int W, int H, MvCam cam,
 }
 
 // ------------------------------------------------------------------------------------------ host
-static dim3 mvTileGrid(int W, int H) { return dim3(((W + kMvTileW - 1) / kMvTileW) * ((H + kMvTileH - 1) / kMvTileH)); }
-
 void launchMotionSnapshot(hipStream_t st, uint32_t nTris, const Tri *tris, const uint32_t *slotOfPrim, float *out)
 {
     if (nTris) hipLaunchKernelGGL(k_motion_snapshot, dim3((nTris + 255u) / 256u), dim3(256), 0, st, nTris, tris, slotOfPrim, reinterpret_cast<float4 *>(out));
 }
 
-void launchMotionTrace(hipStream_t st, const MvTraceArgs &a) { hipLaunchKernelGGL(k_motion_trace, mvTileGrid(a.W, a.H), dim3(256), 0, st, a); }
+void launchMotionTrace(hipStream_t st, const MvTraceArgs &a) { hipLaunchKernelGGL(k_motion_trace, postTileGrid(a.W, a.H), dim3(256), 0, st, a); }
 
 void launchMotionMerge(hipStream_t st, int W, int H, const MvCam &cam, const HsParams &P, const float *mv, const float *hist, float *frame, float *albedo, float *normalDepth,
                        float *moments, unsigned long long *result)
 {
-    hipLaunchKernelGGL(k_motion_merge, mvTileGrid(W, H), dim3(256), 0, st, W, H, cam, P, reinterpret_cast<const dn4 *>(mv), reinterpret_cast<const dn4 *>(hist),
+    hipLaunchKernelGGL(k_motion_merge, postTileGrid(W, H), dim3(256), 0, st, W, H, cam, P, reinterpret_cast<const dn4 *>(mv), reinterpret_cast<const dn4 *>(hist),
                        reinterpret_cast<dn4 *>(frame), reinterpret_cast<dn4 *>(albedo), reinterpret_cast<dn4 *>(normalDepth), reinterpret_cast<dn4 *>(moments), result);
 }
 

@@ -153,9 +153,8 @@ int hr_motion_merge(hr_ctx *c, const hr_pass_params *camera, const hr_history_pa
         FAIL(c, HR_ERR_INVALID, "motion merge: a history has already been merged into this frame (one merge per hr_clear, of whatever kind: a second would count it twice)");
     rc = motionTraceEnqueue(c, "motion merge", camera);
     if (rc) return rc;
-    const MvCam cam = mvCameras(c->history.view, c->history.aspect, c->history.fovTan, camera->view_matrix, camera->aspect_ratio, camera->fov_tan);
-    const HsParams P{(float)p.max_history, p.normal_cos, p.plane_tol, p.min_weight};
-    launchMotionMerge(c->stream, c->W, c->H, cam, P, m.planes, c->history.hist, c->fb(), c->aov.plane[HR_AOV_PLANE_ALBEDO], c->aov.plane[HR_AOV_PLANE_NORMAL_DEPTH],
+    const HsLaunch l = historyLaunch(c, camera, p);
+    launchMotionMerge(c->stream, c->W, c->H, mvCameras(l.cam, c->history.view), l.P, m.planes, c->history.hist, c->fb(), c->aov.plane[HR_AOV_PLANE_ALBEDO], c->aov.plane[HR_AOV_PLANE_NORMAL_DEPTH],
                       c->aov.plane[HR_AOV_PLANE_MOMENTS], m.result.dev + kMotionTraceResultWords);
     HIP_TRY(c, hipGetLastError());
     c->history.merged = true; // (hr_history_merge and hr_reproject_merge refuse from here to the next hr_clear)

@@ -1,8 +1,8 @@
 // hr_reproject.h — the per-pixel arithmetic of the progressive history merge and the preview (include/hrcore_reproject.h states the
 // contract these lines implement).  Pure float32 functions like hr_history.h's, which this header builds on: the progressive merge IS
-// hsMerge, applied to the pixels the examined bits have not seen yet; the preview restates hsMerge's projection and taps for a point,
-// a normal and a class that come from a neighbour (hsMerge itself is left as it is: its kernels' registers are pinned).  The kernels in
-// hr_reproject.hip and the CPU test (tests/host/reproject_cpu.cpp, against heatray_amd/reproject.py) compile the same lines.
+// hsMerge, applied to the pixels the examined bits have not seen yet; the preview finds a point, a normal and a class from a neighbour
+// and hands them to hsMerge's own gather (hsGather, without the moments).  The kernels in hr_reproject.hip and the CPU test
+// (tests/host/reproject_cpu.cpp, against heatray_amd/reproject.py) compile the same lines.
 #pragma once
 #include "hr_history.h"
 
@@ -57,10 +57,9 @@ template <class Q> HRN int rpFindGuide(const Q &guides, int x, int y, int W, int
 }
 
 // The preview of an UNSAMPLED pixel (x, y) from its guide (cls, gx, gy, rec as rpFindGuide gave them; cls RP_GUIDE_NONE: no guide):
-// the history's colour at the point where the pixel's ray cuts the guide's tangent plane, through MERGE's projection and tap tests.
-// Like hsMerge written without a branch around a load: the eight float4 (H0 and H2 of four taps) are read at clamped addresses
-// whatever has been decided, and the sums skip a tap that does not count by a select.  *out = (colour, 1) and RP_PREVIEWED, or
-// 0 0 0 0 and RP_EMPTY.
+// the history's colour at the point where the pixel's ray cuts the guide's tangent plane, through MERGE's projection and tap tests
+// (hsGather without the moments: the eight float4, H0 and H2 of four taps, are read at clamped addresses whatever has been decided).
+// *out = (colour, 1) and RP_PREVIEWED, or 0 0 0 0 and RP_EMPTY.
 template <class S> HRN int rpPreviewFromGuide(const S &s, const HsCam &cam, const HsParams &P, int x, int y, int W, int H, int cls, int gx, int gy, const dn4 &rec, dn4 &out)
 {
     bool ok = cls != RP_GUIDE_NONE;
@@ -81,40 +80,11 @@ template <class S> HRN int rpPreviewFromGuide(const S &s, const HsCam &cam, cons
         ok = ok && sd > 0.0f && sd < __builtin_inff();
         for (int i = 0; i < 3; ++i) q[i] = sd * q[i] + cam.t[i];
     }
-    const float z = -q[2];
-    ok = ok && z > 0.0f;
-    const float sx = (((q[0] / z) / cam.axOld + 1.0f) * 0.5f) * Wf;
-    const float sy = (((q[1] / z) / cam.fovOld + 1.0f) * 0.5f) * Hf;
-    ok = ok && (sx >= -1.0f && sx <= Wf + 1.0f && sy >= -1.0f && sy <= Hf + 1.0f);
-    const float fx = ok ? sx - 0.5f : 0.0f, fy = ok ? sy - 0.5f : 0.0f;
-    const float x0f = floor_(fx), y0f = floor_(fy);
-    const float wx = fx - x0f, wy = fy - y0f;
-    const int x0 = (int)x0f, y0 = (int)y0f;
-    const float tol = P.planeTol * z;
-    float wsum = 0.0f, hs[3] = {0.0f, 0.0f, 0.0f};
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-        const int tx = x0 + (k & 1), ty = y0 + (k >> 1);
-        const float w = ((k & 1) ? wx : 1.0f - wx) * ((k >> 1) ? wy : 1.0f - wy);
-        const bool inside = tx >= 0 && tx < W && ty >= 0 && ty < H;
-        const int ux = tx < 0 ? 0 : (tx >= W ? W - 1 : tx), uy = ty < 0 ? 0 : (ty >= H ? H - 1 : ty);
-        const int i = uy * W + ux;
-        const dn4 h0 = s.h0(i), h2 = s.h2(i);
-        bool use = ok && inside && h0.w > 0.0f && (hsFinite(h2.w) == surf);
-        if (surf) {
-            const float nd = HS_DOT(N[0], N[1], N[2], h2.x, h2.y, h2.z);
-            const float px = h2.w * hsRayX(ux, Wf, cam.aspectOld, cam.fovOld), py = h2.w * hsRayY(uy, Hf, cam.fovOld), pz = h2.w * -1.0f;
-            const float dx = px - q[0], dy = py - q[1], dz = pz - q[2];
-            const float pd = abs_(HS_DOT(Nq[0], Nq[1], Nq[2], dx, dy, dz));
-            use = use && nd >= P.normalCos && pd <= tol;
-        }
-        wsum = use ? wsum + w : wsum;
-        hs[0] = use ? hs[0] + w * h0.x : hs[0], hs[1] = use ? hs[1] + w * h0.y : hs[1], hs[2] = use ? hs[2] + w * h0.z : hs[2];
-    }
-    ok = ok && !(wsum < P.minWeight);
+    HsSums sums;
+    ok = hsGather<false, false>(s, cam, P, ok, surf, q, N, Nq, W, H, sums);
     out = dn4{0.0f, 0.0f, 0.0f, 0.0f};
     if (!ok) return RP_EMPTY;
-    out = dn4{hs[0] / wsum, hs[1] / wsum, hs[2] / wsum, 1.0f};
+    out = dn4{sums.hs[0] / sums.wsum, sums.hs[1] / sums.wsum, sums.hs[2] / sums.wsum, 1.0f};
     return RP_PREVIEWED;
 }
 

@@ -20,8 +20,7 @@
 
 namespace hr {
 
-static constexpr int kRpTileW = 32, kRpTileH = 8;                                              // pixels of a workgroup: four waves of 8 x 8
-static constexpr int kRpHaloW = kRpTileW + 2 * RP_GUIDE_REACH, kRpHaloH = kRpTileH + 2 * RP_GUIDE_REACH; // 36 x 12 staged guide records
+static constexpr int kRpHaloW = kPostTileW + 2 * RP_GUIDE_REACH, kRpHaloH = kPostTileH + 2 * RP_GUIDE_REACH; // 36 x 12 staged guide records
 
 // result: {reused pixels, rejected pixels, samples taken over, pending pixels, examined pixels}, zeroed by the caller
 __global__ __launch_bounds__(256) void k_reproject_merge(int W, int H, HsCam cam, HsParams P, const dn4 *__restrict__ hist, dn4 *__restrict__ frame, dn4 *__restrict__ albedo,
@@ -31,13 +30,11 @@ __global__ __launch_bounds__(256) void k_reproject_merge(int W, int H, HsCam cam
     __shared__ uint32_t sRed[5];
     wgCountersZero<5>(sRed);
     __syncthreads();
-    const uint32_t tilesX = (uint32_t)(W + kRpTileW - 1) / (uint32_t)kRpTileW;
     const uint32_t blocksX = (uint32_t)(W + 7) / 8u;
-    const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
-    const uint32_t blockX = (blockIdx.x % tilesX) * 4u + wave, blockY = blockIdx.x / tilesX; // the wave's 8 x 8 block
-    const int x = (int)(blockX * 8u + (lane & 7u));
-    const int y = (int)(blockY * 8u + (lane >> 3));
-    const bool in = x < W && y < H;
+    const uint32_t lane = threadIdx.x & 63u;
+    int x, y;
+    const bool in = postTilePixel(W, H, x, y);
+    const uint32_t blockX = (uint32_t)x >> 3, blockY = (uint32_t)y >> 3; // the wave's 8 x 8 block
     const int i = in ? y * W + x : 0; // (a lane outside the image reads pixel 0 and writes nothing)
     const bool hasWord = blockX < blocksX; // (the last workgroup of a row may hold waves that lie outside the image altogether)
     const size_t wordAt = (size_t)blockY * blocksX + blockX;
@@ -45,26 +42,17 @@ __global__ __launch_bounds__(256) void k_reproject_merge(int W, int H, HsCam cam
     dn4 F = G(frame)[i];
     const bool todo = in && !((word >> lane) & 1ull) && F.w > 0.0f;
     const unsigned long long todoMask = __ballot(todo);
-    uint32_t nReused = 0u, nRejected = 0u, samples = 0u;
     if (todoMask) { // wave-uniform
         dn4 A = G(albedo)[i], Gn = G(normalDepth)[i], M = G(moments)[i];
         const HsPlanes src(hist, (size_t)W * (size_t)H);
         float nh = 0.0f;
         const int st = hsMerge(src, cam, P, in ? x : 0, in ? y : 0, W, H, F, A, Gn, M, &nh);
-        const bool reused = todo && st == HS_REUSED, rejected = todo && st == HS_REJECTED;
-        if (reused) G(frame)[i] = F, G(albedo)[i] = A, G(normalDepth)[i] = Gn, G(moments)[i] = M;
-        samples = waveSum(reused ? hsCount(nh) : 0u); // (at most 65536 per pixel: a workgroup's sum fits 32 bits)
-        nReused = waveCount(reused), nRejected = waveCount(rejected);
+        mergeTail(todo && st == HS_REUSED, todo && st == HS_REJECTED, nh, i, F, A, Gn, M, frame, albedo, normalDepth, moments, sRed);
         if (lane == 0u) G(examined)[wordAt] = word | todoMask; // (todoMask != 0 implies hasWord)
     }
     const unsigned long long now = word | todoMask;
     const uint32_t nExamined = (uint32_t)__popcll(now), nPending = (uint32_t)__popcll(__ballot(in) & ~now); // (bit masks in hand: no waveCount)
-    if (lane == 0u) {
-        if (nReused) atomicAdd(&sRed[0], nReused);
-        if (nRejected) atomicAdd(&sRed[1], nRejected);
-        if (samples) atomicAdd(&sRed[2], samples);
-        atomicAdd(&sRed[3], nPending), atomicAdd(&sRed[4], nExamined);
-    }
+    if (lane == 0u) atomicAdd(&sRed[3], nPending), atomicAdd(&sRed[4], nExamined);
     wgCountersFlush<5>(sRed, result);
 }
 
@@ -87,8 +75,8 @@ __global__ __launch_bounds__(256) void k_reproject_preview(int W, int H, HsCam c
     __shared__ unsigned char sCls[kRpHaloW * kRpHaloH];
     __shared__ uint32_t sRed[3];
     wgCountersZero<3>(sRed); // (the barrier behind the staging loop comes before the first add)
-    const uint32_t tilesX = (uint32_t)(W + kRpTileW - 1) / (uint32_t)kRpTileW;
-    const int tx0 = (int)(blockIdx.x % tilesX) * kRpTileW, ty0 = (int)(blockIdx.x / tilesX) * kRpTileH;
+    int tx0, ty0;
+    postTileOrigin(W, tx0, ty0);
     for (int e = (int)threadIdx.x; e < kRpHaloW * kRpHaloH; e += 256) {
         const int gx = tx0 - RP_GUIDE_REACH + e % kRpHaloW, gy = ty0 - RP_GUIDE_REACH + e / kRpHaloW;
         const bool inside = gx >= 0 && gx < W && gy >= 0 && gy < H;
@@ -99,10 +87,9 @@ __global__ __launch_bounds__(256) void k_reproject_preview(int W, int H, HsCam c
         sRec[e] = rec, sCls[e] = (unsigned char)cls;
     }
     __syncthreads();
-    const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
-    const int x = tx0 + (int)(wave * 8u + (lane & 7u));
-    const int y = ty0 + (int)(lane >> 3);
-    const bool in = x < W && y < H;
+    const uint32_t lane = threadIdx.x & 63u;
+    int x, y;
+    const bool in = postTilePixel(W, H, x, y);
     const int i = in ? y * W + x : 0;
     const dn4 F = G(frame)[i];
     const bool own = in && F.w > 0.0f, needs = in && !own;
@@ -129,19 +116,17 @@ __global__ __launch_bounds__(256) void k_reproject_preview(int W, int H, HsCam c
     wgCountersFlush<3>(sRed, result);
 }
 
-static dim3 rpGrid(int W, int H) { return dim3(((W + kRpTileW - 1) / kRpTileW) * ((H + kRpTileH - 1) / kRpTileH)); }
-
 void launchReprojectMerge(hipStream_t st, int W, int H, const HsCam &cam, const HsParams &P, const float *hist, float *frame, float *albedo, float *normalDepth, float *moments,
                           unsigned long long *examined, unsigned long long *result)
 {
-    hipLaunchKernelGGL(k_reproject_merge, rpGrid(W, H), dim3(256), 0, st, W, H, cam, P, reinterpret_cast<const dn4 *>(hist), reinterpret_cast<dn4 *>(frame),
+    hipLaunchKernelGGL(k_reproject_merge, postTileGrid(W, H), dim3(256), 0, st, W, H, cam, P, reinterpret_cast<const dn4 *>(hist), reinterpret_cast<dn4 *>(frame),
                        reinterpret_cast<dn4 *>(albedo), reinterpret_cast<dn4 *>(normalDepth), reinterpret_cast<dn4 *>(moments), examined, result);
 }
 
 void launchReprojectPreview(hipStream_t st, int W, int H, const HsCam &cam, const HsParams &P, const float *hist, const float *frame, const float *albedo,
                             const float *normalDepth, float *out, unsigned long long *result)
 {
-    hipLaunchKernelGGL(k_reproject_preview, rpGrid(W, H), dim3(256), 0, st, W, H, cam, P, reinterpret_cast<const dn4 *>(hist), reinterpret_cast<const dn4 *>(frame),
+    hipLaunchKernelGGL(k_reproject_preview, postTileGrid(W, H), dim3(256), 0, st, W, H, cam, P, reinterpret_cast<const dn4 *>(hist), reinterpret_cast<const dn4 *>(frame),
                        reinterpret_cast<const dn4 *>(albedo), reinterpret_cast<const dn4 *>(normalDepth), reinterpret_cast<dn4 *>(out), result);
 }
 

@@ -37,10 +37,9 @@ static int previewRun(hr_ctx *c, const hr_pass_params *camera, const hr_history_
         if (!c->reproject.out) HIP_TRY(c, c->reproject.out.alloc((size_t)c->W * c->H * 4));
         dst = c->reproject.out;
     }
-    const HsCam cam = hsCameras(c->history.view, c->history.aspect, c->history.fovTan, camera->view_matrix, camera->aspect_ratio, camera->fov_tan);
-    const HsParams P{(float)p.max_history, p.normal_cos, p.plane_tol, p.min_weight};
+    const HsLaunch l = historyLaunch(c, camera, p);
     HIP_TRY(c, c->reproject.result.zero(c->stream));
-    launchReprojectPreview(c->stream, c->W, c->H, cam, P, c->history.hist, c->fb(), c->aov.plane[HR_AOV_PLANE_ALBEDO], c->aov.plane[HR_AOV_PLANE_NORMAL_DEPTH], dst, c->reproject.result.dev);
+    launchReprojectPreview(c->stream, c->W, c->H, l.cam, l.P, c->history.hist, c->fb(), c->aov.plane[HR_AOV_PLANE_ALBEDO], c->aov.plane[HR_AOV_PLANE_NORMAL_DEPTH], dst, c->reproject.result.dev);
     HIP_TRY(c, hipGetLastError());
     if (out) {
         HIP_TRY(c, c->reproject.result.fetch(c->stream));
@@ -70,10 +69,9 @@ int hr_reproject_merge(hr_ctx *c, const hr_pass_params *camera, const hr_history
     }
     if (c->reproject.stale) HIP_TRY(c, hipMemsetAsync(c->reproject.examined, 0, words * 8, c->stream));
     c->reproject.stale = false;
-    const HsCam cam = hsCameras(c->history.view, c->history.aspect, c->history.fovTan, camera->view_matrix, camera->aspect_ratio, camera->fov_tan);
-    const HsParams P{(float)p.max_history, p.normal_cos, p.plane_tol, p.min_weight};
+    const HsLaunch l = historyLaunch(c, camera, p);
     HIP_TRY(c, c->reproject.result.zero(c->stream));
-    launchReprojectMerge(c->stream, c->W, c->H, cam, P, c->history.hist, c->fb(), c->aov.plane[HR_AOV_PLANE_ALBEDO], c->aov.plane[HR_AOV_PLANE_NORMAL_DEPTH],
+    launchReprojectMerge(c->stream, c->W, c->H, l.cam, l.P, c->history.hist, c->fb(), c->aov.plane[HR_AOV_PLANE_ALBEDO], c->aov.plane[HR_AOV_PLANE_NORMAL_DEPTH],
                          c->aov.plane[HR_AOV_PLANE_MOMENTS], c->reproject.examined, c->reproject.result.dev);
     HIP_TRY(c, hipGetLastError());
     c->history.merged = c->reproject.merged = true;

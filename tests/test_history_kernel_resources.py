@@ -15,4 +15,5 @@ def test_history_kernels_use_no_scratch_and_keep_their_registers():
     assert kernels["k_history_capture"]["LDS Size"] == 0
     assert kernels["k_history_merge"]["LDS Size"] == 3 * 4  # the workgroup's three counters
     assert (kernels["k_history_capture"]["VGPRs"], kernels["k_history_capture"]["Occupancy"]) == (42, 8), kernels["k_history_capture"]
-    assert (kernels["k_history_merge"]["VGPRs"], kernels["k_history_merge"]["Occupancy"]) == (81, 5), kernels["k_history_merge"]
+    assert (kernels["k_history_merge"]["VGPRs"], kernels["k_history_merge"]["Occupancy"]) == (82, 5), kernels["k_history_merge"]
+    assert kernels["k_history_merge"]["VGPRs"] <= 96  # what five waves per SIMD hold: the budget behind the recorded count

@@ -14,5 +14,7 @@ def test_reproject_kernels_use_no_scratch_and_keep_their_registers():
         assert r["ScratchSize"] == 0 and r["VGPRs Spill"] == 0 and r["SGPRs Spill"] == 0 and r["AGPRs"] == 0, (name, r)
     assert kernels["k_reproject_merge"]["LDS Size"] == 5 * 4                        # the workgroup's five counters
     assert kernels["k_reproject_preview"]["LDS Size"] == 36 * 12 * (16 + 1) + 3 * 4  # the guide records, their classes, three counters
-    assert (kernels["k_reproject_merge"]["VGPRs"], kernels["k_reproject_merge"]["Occupancy"]) == (85, 5), kernels["k_reproject_merge"]
-    assert (kernels["k_reproject_preview"]["VGPRs"], kernels["k_reproject_preview"]["Occupancy"]) == (45, 8), kernels["k_reproject_preview"]
+    assert (kernels["k_reproject_merge"]["VGPRs"], kernels["k_reproject_merge"]["Occupancy"]) == (86, 5), kernels["k_reproject_merge"]
+    assert (kernels["k_reproject_preview"]["VGPRs"], kernels["k_reproject_preview"]["Occupancy"]) == (48, 8), kernels["k_reproject_preview"]
+    # what five and eight waves per SIMD hold: the budgets behind the recorded counts
+    assert kernels["k_reproject_merge"]["VGPRs"] <= 96 and kernels["k_reproject_preview"]["VGPRs"] <= 64
