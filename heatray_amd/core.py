@@ -5,7 +5,7 @@ There is no CPU fallback: if the library is missing or no HIP device is usable t
 import ctypes
 import os
 
-from ._ffi import ABI_SYMBOLS, Engine, EngineError
+from ._ffi import ABI_SYMBOLS, HR_CTX_COLLECT_STATS, HR_CTX_TIME_KERNELS, Engine, EngineError, GroupEngine
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("HRCORE_LIB") or os.path.join(_HERE, "csrc", "libhrcore.so")  # HRCORE_LIB: A/B builds in experiments
@@ -25,17 +25,18 @@ def load_library():
     return _LIB
 
 
+def _flags(collect_stats, time_kernels):
+    return (HR_CTX_COLLECT_STATS if collect_stats else 0) | (HR_CTX_TIME_KERNELS if time_kernels else 0)
+
+
 def create_engine(device_id=0, rank=0, world=1, tile_size=32, stream=None, collect_stats=False, time_kernels=False, memory_budget=0):
-    from ._ffi import HR_CTX_COLLECT_STATS, HR_CTX_TIME_KERNELS
-    flags = (HR_CTX_COLLECT_STATS if collect_stats else 0) | (HR_CTX_TIME_KERNELS if time_kernels else 0)
     return Engine(load_library(), "hr_", device_id=device_id, rank=rank, world=world, tile_size=tile_size,
-                  stream=stream, flags=flags, memory_budget=memory_budget)
+                  stream=stream, flags=_flags(collect_stats, time_kernels), memory_budget=memory_budget)
 
 
 def create_group(device_ids=None, tile_size=32, stream=None, collect_stats=False, time_kernels=False, memory_budget=0):
     """One frame rendered by several member contexts behind one handle (include/hrcore_group.h): member i renders the tiles
     t % n == i on device_ids[i] (ids may repeat; None: every visible device once) and the group assembles them on
     device_ids[0].  memory_budget applies per member; stream is the assembly stream."""
-    from ._ffi import HR_CTX_COLLECT_STATS, HR_CTX_TIME_KERNELS, GroupEngine
-    flags = (HR_CTX_COLLECT_STATS if collect_stats else 0) | (HR_CTX_TIME_KERNELS if time_kernels else 0)
-    return GroupEngine(load_library(), device_ids=device_ids, tile_size=tile_size, stream=stream, flags=flags, memory_budget=memory_budget)
+    return GroupEngine(load_library(), device_ids=device_ids, tile_size=tile_size, stream=stream, flags=_flags(collect_stats, time_kernels),
+                       memory_budget=memory_budget)

@@ -74,7 +74,8 @@ def check_library_exports(header):
 
 
 def check_struct_layout(tmp_path, header, struct, cname, version_macro):
-    """the header compiles as C, and gcc gives `cname` the size and the field offsets of the ctypes `struct`"""
+    """the header compiles as C, and gcc gives `cname` the size and the field offsets of the ctypes `struct`, which names it as its C type"""
+    assert struct._cname_ == cname
     fields = [n for n, _ in struct._fields_]
     src = tmp_path / "layout.c"
     src.write_text(f'#include <stdio.h>\n#include <stddef.h>\n#include "{header}"\nint main(void) {{\n'

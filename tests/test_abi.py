@@ -73,6 +73,7 @@ def test_every_mirrored_struct_has_the_size_and_field_offsets_gcc_gives_the_head
     subprocess.run(["gcc", "-I", os.path.join(ROOT, "include"), str(src), "-o", str(exe)], check=True, capture_output=True, text=True)
     got = dict(l.split() for l in subprocess.run([str(exe)], check=True, capture_output=True, text=True).stdout.splitlines())
     for cname, mirror in pairs:
+        assert mirror._cname_ == cname
         assert int(got[cname]) == ctypes.sizeof(mirror), cname
         for fname, _ in mirror._fields_:
             assert int(got[f"{cname}.{fname}"]) == getattr(mirror, fname).offset, (cname, fname)

@@ -1,0 +1,231 @@
+"""The prototype table of heatray_amd._abi against the headers under include/, and every call site of heatray_amd._ffi against the
+table.  All of it runs without a device: the library turns a null context away before it reads anything else."""
+import ctypes as C
+import os
+import re
+
+import numpy as np
+import pytest
+
+import abi_checks
+from heatray_amd import _abi
+from heatray_amd import _ffi as ffi
+from heatray_amd import core
+
+HEADERS = sorted(os.listdir(abi_checks.INCLUDE))
+STRUCTS = {s._cname_: s for s in vars(_abi).values() if isinstance(s, type) and issubclass(s, _abi.Struct) and s is not _abi.Struct}
+SCALARS = {"int32_t": C.c_int32, "uint32_t": C.c_uint32, "uint8_t": C.c_uint8, "uint64_t": C.c_uint64, "float": C.c_float}
+RESULTS = {"int": C.c_int, "uint32_t": C.c_uint32, "void": None, "const char *": C.c_char_p}
+
+
+def declarations(header):
+    """{name: (result as written, [(base type, levels of indirection) of every parameter])} of the functions a header declares: comments
+    stripped, `const` dropped, an array parameter counted as a pointer"""
+    text = re.sub(r"/\*.*?\*/|//[^\n]*", " ", abi_checks.header_text(header), flags=re.S)
+    out = {}
+    for result, name, params in re.findall(r"^((?:const\s+)?\w+(?:\s*\*)?)\s*(hr_[a-z0-9_]+)\s*\(([^;{]*)\)\s*;", text, re.M):
+        kinds = []
+        for param in [] if params.strip() == "void" else params.split(","):
+            base, stars, array = re.fullmatch(r"\s*(?:const\s+)?(\w+)\s*(\**)\s*\w+\s*(\[\d+\])?\s*", param).groups()
+            kinds.append((base, len(stars) + bool(array)))
+        out[name] = (" ".join(result.split()), kinds)
+    return out
+
+
+def ctype_of(base, depth, typedefs):
+    """what the table must say for a parameter: hr_ctx is opaque, so hr_ctx* goes as void*; void* and char* are ctypes' own pointer types"""
+    base = typedefs.get(base, base)
+    if base in ("hr_ctx", "void", "char"):
+        t, depth = (C.c_char_p if base == "char" else C.c_void_p), depth - 1
+    else:
+        t = SCALARS[base] if base in SCALARS else STRUCTS[base]
+    assert depth >= 0, (base, depth)
+    for _ in range(depth):
+        t = C.POINTER(t)
+    return t
+
+
+def test_every_mirrored_struct_names_a_c_type_of_its_own():
+    mirrors = [s for s in vars(_abi).values() if isinstance(s, type) and issubclass(s, C.Structure) and s is not _abi.Struct]
+    assert len(mirrors) == len(STRUCTS) and all(issubclass(s, _abi.Struct) for s in mirrors)
+
+
+def test_the_table_has_a_block_for_every_header_and_the_symbol_lists_are_its_keys():
+    assert sorted(_abi.PROTOTYPES) == HEADERS and len(HEADERS) == 16
+    for header, (_, _, _, symbols) in abi_checks.HEADERS.items():
+        assert getattr(ffi, symbols) == list(_abi.PROTOTYPES[header])
+    for feature, (symbols, _, _) in ffi.FEATURES.items():
+        assert symbols == list(_abi.PROTOTYPES[f"hrcore_{feature}.h"]) and f"{feature}_api_version" in symbols
+
+
+@pytest.mark.parametrize("header", HEADERS)
+def test_the_table_is_the_header(header):
+    typedefs = dict((new, old) for old, new in re.findall(r"typedef\s+(\w+)\s+(\w+)\s*;", abi_checks.header_text("hrcore.h")))
+    assert typedefs == {"hr_geom_id": "int32_t", "hr_tex_id": "int32_t"}
+    declared = declarations(header)
+    assert sorted(n for n, (result, _) in declared.items() if result in ("int", "void", "uint32_t")) == abi_checks.declared_functions(header)  # (which looks for these three)
+    table = _abi.PROTOTYPES[header]
+    assert sorted("hr_" + n for n in table) == sorted(declared)
+    for name, argtypes in table.items():
+        result, kinds = declared["hr_" + name]
+        assert _abi.restype(name) is RESULTS[result], name
+        assert len(argtypes) == len(kinds), name
+        for i, (argtype, (base, depth)) in enumerate(zip(argtypes, kinds)):
+            assert argtype is ctype_of(base, depth, typedefs), (name, i, base, depth)
+
+
+# -- every call site converts
+
+
+def bare(cls):
+    """an engine over libhrcore.so that has everything but a context, with a 4 x 4 frame noted; reached[...] collects the symbols it uses"""
+    class Recording(dict):
+        def __getitem__(self, name):
+            reached.add(name)
+            return dict.__getitem__(self, name)
+    reached = set()
+    eng = cls.__new__(cls)
+    eng._init(core.load_library(), "hr_")
+    eng._fns = Recording(eng._fns)
+    eng.width = eng.height = 4
+    return eng, reached
+
+
+DEV = 0x1000  # a device pointer or a stream: never looked at, the null context is refused first
+POS = np.array([[0, 0, 0], [1, 0, 0], [0, 1, 0]], np.float32)
+NRM = np.array([[0, 0, 1]] * 3, np.float32)
+UV = np.array([[0, 0], [1, 0], [0, 1]], np.float32)
+IDX = [0, 1, 2]
+O, D = [[0, 0, 1]], [[0, 0, -1]]
+XY = [[0.5, 0.5]]
+
+
+def walk():
+    """(method, args, kwargs): every public method of the engine with the smallest well-formed arguments, the optional ones left out
+    (None) and given"""
+    PP, DP, HP = ffi.PassParams(), ffi.display_params(), ffi.HistoryParams()
+    DN, DS, DK = ffi.DenoiseParams(), ffi.DenoiseSpatialParams(), ffi.DespeckleParams()
+    RGBA32F = ffi.HR_DISPLAY_RGBA32F
+
+    def c(method, *args, **kwargs):
+        return method, args, kwargs
+    return [
+        # include/hrcore.h
+        c("resize", 4, 4), c("bind_external_frame", DEV), c("bind_external_frame", None), c("frame_device_ptr"), c("set_stream", DEV), c("set_stream", None),
+        c("add_mesh", POS, NRM, IDX), c("add_mesh", POS, NRM, IDX, uvs=UV, tangents=NRM, bitangents=NRM, colors=NRM, world=np.eye(4), material_id=1),
+        c("add_mesh_strided", np.zeros((3, 8), np.float32), 0, 3, 6, 8, IDX), c("add_mesh_strided", np.zeros((3, 6), np.float32), 0, 3, None, 6, IDX, world=np.eye(4)),
+        c("remove_mesh", 0), c("set_transform", 0, np.eye(4)), c("clear_scene"), c("set_scene_cache", "tree.cache"), c("set_scene_cache", None), c("commit"),
+        c("scene_info"), c("create_texture", np.zeros((2, 2, 4), np.uint8)), c("create_texture", np.zeros((2, 2), np.float64)), c("destroy_texture", 0),
+        c("set_material", 0, ffi.Material()), c("set_lights", ffi.Lights()), c("set_sequences", np.zeros((16, 4, 2)), np.zeros((16, 4, 2))),
+        c("set_seq_offsets", np.zeros((4, 2))), c("qmc_generate", ffi.HR_SAMPLE_SOBOL, 0, 4), c("qmc_generate", ffi.HR_SAMPLE_HALTON, np.uint32(1), np.int64(4), radial=True),
+        c("aperture_generate", ffi.HR_BOKEH_HEXAGON, 0, 4), c("generate_sequences"), c("generate_seq_offsets"), c("generate_multiscatter_lut"),
+        c("generate_multiscatter_lut", want_host=False), c("clear"), c("render_pass", PP), c("set_interactive_blocks", None),
+        c("set_interactive_blocks", np.zeros((2, 2, 2), np.int64)), c("pass_batch", 4), c("flush"), c("stats"), c("kernel_times"), c("step_log", capacity=4),
+        c("synchronize"), c("readback"), c("readback", copy=False), c("display"), c("display", DP, RGBA32F, with_passes=True), c("passes_resolved"),
+        c("packed_slots", 0, 1), c("pack_owned", DEV), c("pack_owned", DEV, stream=DEV), c("unpack", 0, 1, DEV, DEV), c("unpack", 0, 1, DEV, DEV, stream=DEV),
+        c("display_device", DEV), c("display_device", DEV, DP, RGBA32F), c("readback_progressive"), c("debug_trace", O, D),
+        c("debug_trace", O, D, tmax=[1.0], skip_prim=[0], any_hit=True),
+        # include/hrcore_tree.h, hrcore_aov.h
+        c("tree_info"), c("set_aovs", ffi.HR_AOV_SURFACE | ffi.HR_AOV_MOMENTS), c("aov_mask"), c("aov_plane", ffi.HR_AOV_PLANE_MOMENTS), c("aovs"),
+        c("aov_to_device", 0, DEV), c("aov_to_device", 0, DEV, stream=DEV),
+        # include/hrcore_denoise.h, hrcore_denoise_spatial.h
+        c("denoise"), c("denoise", DN, with_passes=True), c("denoise_to_device", DEV), c("denoise_to_device", DEV, DN, DEV), c("denoise_display", DEV),
+        c("denoise_display", DEV, DP, RGBA32F, DN), c("denoise_spatial"), c("denoise_spatial", DN, DS, with_result=True), c("denoise_spatial_to_device", DEV),
+        c("denoise_spatial_to_device", DEV, DN, DS, DEV), c("denoise_spatial_display", DEV), c("denoise_spatial_display", DEV, DP, RGBA32F, DN, DS),
+        c("denoise_spatial_variance"), c("denoise_spatial_variance", DN, DS, with_result=True),
+        # include/hrcore_adaptive.h
+        c("set_sample_mask", None), c("set_sample_mask", np.ones((4, 4), np.uint8)), c("set_sample_mask", np.ones((4, 4), bool)), c("sample_mask"),
+        c("adaptive_update"), c("adaptive_update", ffi.AdaptiveParams(), install=False), c("adaptive_error_to_device", DEV),
+        c("adaptive_error_to_device", DEV, stream=DEV), c("adaptive_error"),
+        # include/hrcore_history.h, hrcore_reproject.h
+        c("history_capture", PP), c("history_merge", PP), c("history_merge", PP, HP), c("history_drop"), c("history_info"), c("history"),
+        c("reproject_merge", PP), c("reproject_merge", PP, HP), c("reproject_examined"), c("reproject_preview", PP), c("reproject_preview", PP, HP),
+        c("reproject_preview_to_device", DEV, PP), c("reproject_preview_to_device", DEV, PP, HP, DEV),
+        # include/hrcore_exposure.h, hrcore_metric.h
+        c("exposure_meter"), c("exposure_meter", ffi.ExposureParams(), DEV), c("exposure_display", DEV), c("exposure_display", DEV, DP, RGBA32F, ffi.ExposureParams(), DEV),
+        c("exposure_last"), c("exposure_last", with_bins=True), c("exposure_reset"), c("metric_compare", DEV), c("metric_compare", DEV, DEV, ffi.MetricParams()),
+        c("metric_estimate"), c("metric_estimate", ffi.MetricParams()), c("metric_last"), c("metric_last", with_bins=True),
+        # include/hrcore_despeckle.h
+        c("despeckle"), c("despeckle", DK, with_moments=True, with_result=True), c("despeckle_to_device", DEV),
+        c("despeckle_to_device", DEV, DEV, DK, DEV, DEV, DEV, with_result=True), c("despeckle_denoise"), c("despeckle_denoise", DK, DN, True, DS, with_result=True),
+        c("despeckle_denoise_to_device", DEV), c("despeckle_denoise_to_device", DEV, DK, DN, True, DS, DEV),
+        # include/hrcore_mesh.h, hrcore_deform.h
+        c("prepare_mesh", POS, IDX), c("prepare_mesh", POS, IDX, UV, NRM, params=ffi.MeshParams(0, 1, 3), with_result=True), c("add_mesh_prepared", POS, IDX, uvs=UV),
+        c("mesh_last"), c("update_mesh", 0, POS), c("update_mesh", 0, POS, NRM, UV, NRM, NRM, NRM, ffi.DeformParams(), with_result=True),
+        c("mesh_attribute", 7, ffi.HR_GEOM_POSITIONS), c("mesh_attribute", 7, ffi.HR_GEOM_UVS, n_vertices=3), c("deform_bind", 0),
+        c("deform_bind", 0, np.zeros((1, 3, 3)), np.zeros((1, 3, 3)), np.zeros((3, 4), np.int64), np.ones((3, 4))), c("deform_pose", 0),
+        c("deform_pose", 0, [1.0], np.eye(4)[None], ffi.DeformParams(), with_result=True), c("deform_unbind", 0), c("deform_last"),
+        # include/hrcore_query.h
+        c("query", O, D), c("query", O, D, tmax=[1.0], skip_prim=[0], any_hit=True, surface=True, tmin=0.0), c("query", np.zeros((0, 3)), np.zeros((0, 3))),
+        c("query_to_device", 1, DEV, DEV), c("query_to_device", 1, DEV, DEV, DEV, DEV, DEV, DEV, strides=(16, 16, 4, 4), any_hit=True, tmin=0.0, stream=DEV),
+        c("query_pixels", PP, XY), c("query_pixels", PP, XY, surface=False, rays=True), c("query_pixels", PP, np.zeros((0, 2))), c("query_last"),
+        # include/hrcore_motion.h
+        c("motion_snapshot"), c("motion_trace", PP), c("motion_merge", PP), c("motion_merge", PP, HP), c("motion_planes"), c("motion_vectors"),
+        c("motion_vectors", PP), c("motion_vectors_to_device", DEV), c("motion_vectors_to_device", DEV, PP, DEV), c("motion_snapshot_triangles"),
+        c("motion_drop"), c("motion_info"),
+    ]
+
+
+GROUP_WALK = [("group_info", (), {}), ("member_stats", (0,), {}), ("member_stats", (0,), {"kernel_times": True})]
+
+# the symbols no method reaches on a null context, and why.  Every entry point but these begins with the null-context check (ENTER, or
+# the same test written out in hr_group_get_info and hr_group_member_stats), so the walk may call it
+NOT_REACHED = {
+    "abi_version": "the constructor's check, before there is a context",
+    "group_api_version": "the group constructor's check",
+    "ctx_create": "makes the context: it would need a device",
+    "ctx_create_group": "makes the group: it would need devices",
+    "ctx_destroy": "close() does not call it for a null context",
+    "motion_snapshot_readback": "motion_snapshot_triangles asks motion_info for the size first, and that call raises",
+    **{f"{feature}_default_params": "no Engine method: the feature's module calls it on the library" for feature in
+       ("denoise", "denoise_spatial", "adaptive", "history", "exposure", "metric", "despeckle", "mesh", "deform", "motion")},
+}
+
+
+@pytest.mark.parametrize("cls", [ffi.Engine, ffi.GroupEngine])
+def test_every_call_site_passes_what_the_table_declares(cls):
+    eng, reached = bare(cls)
+    calls = walk() + (GROUP_WALK if cls is ffi.GroupEngine else [])
+    for method, args, kwargs in calls:
+        with pytest.raises(ffi.EngineError, match=r"^hr_\w+: status 1: null ctx$"):  # (anything else: the call site and the table disagree)
+            getattr(eng, method)(*args, **kwargs)
+    public = {n for n in dir(cls) if not n.startswith("_") and callable(getattr(cls, n))}
+    assert {method for method, _, _ in calls} == public - {"close"}
+    every = {name for prototypes in _abi.PROTOTYPES.values() for name in prototypes}
+    group_only = set() if cls is ffi.GroupEngine else {"group_get_info", "group_member_stats"}
+    assert every - reached == set(NOT_REACHED) | group_only
+    eng.close()
+
+
+def test_a_wrong_type_is_refused_before_the_call():
+    eng, _ = bare(ffi.Engine)
+    with pytest.raises(C.ArgumentError):  # a hr_history_params where a hr_denoise_params is declared
+        eng._feature_call("denoise", "denoise_readback", ffi.HistoryParams(), None, None, None, None)
+    with pytest.raises(C.ArgumentError):  # a float for an int32_t
+        eng._feature_call("aov", "aov_readback", 0.5, None, None, None, None)
+    with pytest.raises(C.ArgumentError):
+        eng.resize(4.0, 4)
+    with pytest.raises(ffi.EngineError, match="null ctx"):  # (and the right types get through to the library)
+        eng._feature_call("denoise", "denoise_readback", ffi.DenoiseParams(), None, None, None, None)
+
+
+def test_the_binding_leaves_the_shared_library_object_alone(oracle_lib):
+    lib = core.load_library()
+    bare(ffi.Engine)
+    assert lib.hr_render_pass.argtypes is None and ffi._bind(lib, "hr_")["render_pass"] is not lib.hr_render_pass
+    assert ffi._bind(lib, "hr_") is ffi._bind(lib, "hr_")
+    # a library that lacks symbols binds the rest: the oracle has no feature and not the four calls of device-memory plumbing
+    fns = ffi._bind(oracle_lib, "ora_")
+    assert set(ffi.ABI_SYMBOLS) - set(fns) == {"ctx_set_stream", "frame_bind_external", "frame_device_ptr", "get_kernel_times"}
+    assert not any(s in fns for symbols, _, _ in ffi.FEATURES.values() for s in symbols)
+
+
+def test_the_result_dicts_are_the_fields_without_reserved():
+    d = ffi.DeformResult(vertices=3, posed=1)
+    d.mesh.triangles = 2
+    assert d.as_dict() == {"vertices": 3, "triangles": 0, "rejected_vertices": 0, "kept_directions": 0, "regenerated": 0, "posed": 1,
+                           "mesh": {n: 2 if n == "triangles" else 0 for n, _ in ffi.MeshResult._fields_}}
+    assert list(d.as_dict()) == [n for n, _ in ffi.DeformResult._fields_]
+    assert list(ffi.QueryResult(1, 2, 3).as_dict().items()) == [("rays", 1), ("hits", 2), ("invalid", 3)]
+    assert all(type(v) in (int, float) for v in ffi.MetricResult().as_dict().values()) and "reserved" not in ffi.MetricResult().as_dict()
+    assert ffi.MotionInfo(1, 0, 5, 1, 64).as_dict() == {"snapshot": True, "traced": False, "triangles": 5, "meshes": 1, "bytes": 64}
