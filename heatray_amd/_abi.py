@@ -255,14 +255,24 @@ class ReprojectPreviewResult(Struct):
     _fields_ = [("own_pixels", C.c_uint64), ("previewed_pixels", C.c_uint64), ("empty_pixels", C.c_uint64)]
 
 
-# -- include/hrcore_tree.h (what the last tree build did to the radix tree's bottom subtrees)
-HR_TREE_API_VERSION = 1
+# -- include/hrcore_tree.h (what the last tree build did to the radix tree's bottom subtrees; since 2: the committed tree read back)
+HR_TREE_API_VERSION = 2
+HR_TREE_NODE4, HR_TREE_NODE32, HR_TREE_LEAF_KEYS, HR_TREE_TRIS, HR_TREE_NODE_BOX, HR_TREE_SLOT_OF_PRIM = range(6)
+HR_TREE_ARRAYS = 6
 
 
 class TreeInfo(Struct):
     _cname_ = "hr_tree_info"
     _fields_ = [("cost_before", C.c_float), ("cost_after", C.c_float), ("subtrees_found", C.c_uint32), ("subtrees_replaced", C.c_uint32),
                 ("max_triangles", C.c_uint32), ("reserved", C.c_uint32 * 3)]
+
+
+class TreeLayout(Struct):
+    _cname_ = "hr_tree_layout"
+    _fields_ = [("n_nodes", C.c_uint64), ("n_triangles", C.c_uint64), ("tri_slots", C.c_uint64), ("root_leaf_count", C.c_uint32), ("levels", C.c_uint32),
+                ("level_start", C.c_uint32 * 65), ("grid_cell_exp", C.c_uint32 * 3), ("pad", C.c_float), ("hit_pad", C.c_float), ("ray_epsilon", C.c_float),
+                ("grid_lo", C.c_float * 3), ("grid_cell", C.c_float * 3), ("lo", C.c_float * 3), ("hi", C.c_float * 3), ("reserved", C.c_uint32),
+                ("bytes", C.c_uint64 * HR_TREE_ARRAYS)]
 
 
 # -- include/hrcore_exposure.h (auto-exposure: the luminance histogram, its reduce and the metered display)
@@ -522,6 +532,8 @@ PROTOTYPES = {
     "hrcore_tree.h": {
         "tree_api_version": (),
         "scene_get_tree_info": (ctx, P(TreeInfo)),
+        "scene_tree_layout": (ctx, P(TreeLayout)),
+        "scene_tree_read": (ctx, i32, vp, C.c_uint64),
     },
     "hrcore_exposure.h": {
         "exposure_api_version": (),

@@ -228,6 +228,22 @@ class Engine:
         self._feature_call("tree", "scene_get_tree_info", t)
         return t
 
+    def tree_readback(self):
+        """The committed tree as the traversal kernels read it (include/hrcore_tree.h): {"layout": the hr_tree_layout as a dict with
+        numpy arrays for its vectors, "node4": (n, 16) uint32, "node32": (n, 8) uint32, "leaf_keys": (n,) int32, "tris": (slots, 12)
+        float32 in leaf order, "node_box": (n, 6) float32, "slot_of_prim": (triangles,) uint32}.  tests/tree_audit.py reads it."""
+        lay = TreeLayout()
+        self._feature_call("tree", "scene_tree_layout", lay)
+        out = {"layout": {k: np.array(v) if hasattr(v, "__len__") else v for k, v in lay.as_dict().items()}}
+        shapes = (("node4", HR_TREE_NODE4, np.uint32, 16), ("node32", HR_TREE_NODE32, np.uint32, 8), ("leaf_keys", HR_TREE_LEAF_KEYS, np.int32, 0),
+                  ("tris", HR_TREE_TRIS, np.float32, 12), ("node_box", HR_TREE_NODE_BOX, np.float32, 6), ("slot_of_prim", HR_TREE_SLOT_OF_PRIM, np.uint32, 0))
+        for name, what, dtype, width in shapes:
+            a = np.empty(lay.bytes[what] // 4, dtype)
+            if a.size:  # (a root leaf has no nodes, an empty scene nothing: the library refuses a null buffer)
+                self._feature_call("tree", "scene_tree_read", what, a.ctypes.data, a.nbytes)
+            out[name] = a.reshape(-1, width) if width else a
+        return out
+
     # -- textures / materials / lights
     def create_texture(self, pixels, wrap=HR_WRAP_REPEAT, filter=HR_FILTER_LINEAR):
         a = np.ascontiguousarray(pixels)

@@ -628,28 +628,33 @@ __global__ __launch_bounds__(256) void k_encode32(const Node4 *__restrict__ node
         }
         for (int k = 0; k < 3; ++k) nb.lo[k] = fmin_(nb.lo[k], cb[c].lo[k]), nb.hi[k] = fmax_(nb.hi[k], cb[c].hi[k]);
     }
-    // frame: the grid point at or below the node's lower corner (the same float expression k_trace evaluates) and, per axis, the smallest
+    // frame: the grid point at or below the node's lower corner and, per axis, the smallest
     // power-of-two number of cells from there that holds the node: hi <= origin + 255 * scale with scale = cell * 2^(e - 8)
+    // The origin is taken in float64, where gLo + g * cell is EXACT: that sum is what the traversal's decode stands for (rayFrame32 folds
+    // gLo and cell into the ray's constants separately), and as a float32 it is rounded by up to half an ulp of the coordinate once the
+    // scene lies 2^10 or so extents from the world's origin — more than the leaf padding there, so planes quantised against the rounded
+    // origin cut into triangles (tests/tree_audit.py found it: -3.4 hit_pad on the soup at 2^10).  The differences below are exact in
+    // float64 too (two float32 values whose exponents lie within 29 of each other), so floor and ceil see true quotients.
     uint32_t g[3], e[3];
-    float origin[3];
+    double origin[3];
     for (int k = 0; k < 3; ++k) {
         const float f = floor_((nb.lo[k] - gLo[k]) * invCell[k]);
         g[k] = (uint32_t)fmin_(fmax_(f, 0.0f), 255.0f);
-        origin[k] = __builtin_fmaf((float)g[k], cell[k], gLo[k]);
-        if (origin[k] > nb.lo[k] && g[k] > 0u) g[k] -= 1u, origin[k] = __builtin_fmaf((float)g[k], cell[k], gLo[k]); // (the rounding of the sum)
+        origin[k] = (double)gLo[k] + (double)g[k] * (double)cell[k];
+        if (origin[k] > (double)nb.lo[k] && g[k] > 0u) g[k] -= 1u, origin[k] = (double)gLo[k] + (double)g[k] * (double)cell[k]; // (the rounding of f)
         e[k] = 0u;
-        while (e[k] < 15u && nb.hi[k] - origin[k] > 255.0f * __uint_as_float((cexp[k] + e[k] - 8u) << 23)) ++e[k];
+        while (e[k] < 15u && (double)nb.hi[k] - origin[k] > 255.0 * (double)__uint_as_float((cexp[k] + e[k] - 8u) << 23)) ++e[k];
     }
     uint32_t qlo[3] = {0, 0, 0}, qhi[3] = {0, 0, 0};
     for (int k = 0; k < 3; ++k) {
-        const float inv = __uint_as_float((254u - (cexp[k] + e[k] - 8u)) << 23); // 1 / scale
+        const double inv = (double)__uint_as_float((254u - (cexp[k] + e[k] - 8u)) << 23); // 1 / scale
         for (int c = 0; c < 4; ++c) {
             uint32_t lo8 = 255u, hi8 = 0u; // no child: inverted planes, never entered
             if (c < nValid) {
-                const float fl = floor_((cb[c].lo[k] - origin[k]) * inv);
-                const float fh = __builtin_ceilf((cb[c].hi[k] - origin[k]) * inv);
-                lo8 = (uint32_t)fmin_(fmax_(fl, 0.0f), 255.0f);
-                hi8 = (uint32_t)fmin_(fmax_(fh, 0.0f), 255.0f);
+                const double fl = __builtin_floor(((double)cb[c].lo[k] - origin[k]) * inv);
+                const double fh = __builtin_ceil(((double)cb[c].hi[k] - origin[k]) * inv);
+                lo8 = (uint32_t)(fl < 0.0 ? 0.0 : (fl > 255.0 ? 255.0 : fl));
+                hi8 = (uint32_t)(fh < 0.0 ? 0.0 : (fh > 255.0 ? 255.0 : fh));
             }
             qlo[k] |= lo8 << (8 * c);
             qhi[k] |= hi8 << (8 * c);

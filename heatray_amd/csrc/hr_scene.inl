@@ -526,6 +526,57 @@ int hr_scene_get_tree_info(hr_ctx *c, hr_tree_info *out)
     return HR_OK;
 }
 
+// the committed tree read back (hrcore_tree.h, version 2): plain copies on the context's stream, which every commit has finished on
+static void treeArrays(const hr_ctx *c, const void *src[HR_TREE_ARRAYS], uint64_t bytes[HR_TREE_ARRAYS])
+{
+    const BuildResult &t = c->tree;
+    const uint64_t n = t.nNodes > 0 ? (uint64_t)t.nNodes : 0u, live = c->hScene.nTris > 0 && t.tris ? 1u : 0u;
+    src[HR_TREE_NODE4] = t.nodes, bytes[HR_TREE_NODE4] = n * sizeof(Node4);
+    src[HR_TREE_NODE32] = t.nodes32, bytes[HR_TREE_NODE32] = n * sizeof(Node32);
+    src[HR_TREE_LEAF_KEYS] = t.leafKeys, bytes[HR_TREE_LEAF_KEYS] = n * sizeof(int);
+    src[HR_TREE_TRIS] = t.tris, bytes[HR_TREE_TRIS] = live * t.triSlots * sizeof(Tri);
+    src[HR_TREE_NODE_BOX] = t.nodeBox, bytes[HR_TREE_NODE_BOX] = n * sizeof(Box6);
+    src[HR_TREE_SLOT_OF_PRIM] = t.slotOfPrim, bytes[HR_TREE_SLOT_OF_PRIM] = live * (uint64_t)c->hScene.nTris * 4u;
+}
+int hr_scene_tree_layout(hr_ctx *c, hr_tree_layout *out)
+{
+    ENTER(c);
+    if (c->grp) FAIL(c, HR_ERR_INVALID, "tree readback: a context group is not supported");
+    if (!c->committed) FAIL(c, HR_ERR_INVALID, "scene not committed");
+    if (!out) FAIL(c, HR_ERR_INVALID, "tree readback: null output");
+    std::memset(out, 0, sizeof(*out));
+    const void *src[HR_TREE_ARRAYS];
+    treeArrays(c, src, out->bytes);
+    if (c->hScene.nTris <= 0) return HR_OK; // an empty scene: no tree, every count 0
+    const BuildResult &t = c->tree;
+    const SceneConsts &k = *c->hConsts;
+    out->n_nodes = t.nNodes > 0 ? (uint64_t)t.nNodes : 0u, out->n_triangles = (uint64_t)c->hScene.nTris, out->tri_slots = t.triSlots;
+    out->root_leaf_count = (uint32_t)t.rootLeafCount, out->levels = (uint32_t)t.levels;
+    for (int l = 0; l <= kMaxLevels; ++l) out->level_start[l] = l <= t.levels ? t.levelStart[l] : 0u;
+    out->pad = k.pad, out->hit_pad = c->hScene.hitPad, out->ray_epsilon = c->hScene.rayEps;
+    for (int q = 0; q < 3; ++q) {
+        out->grid_lo[q] = c->hScene.gridLo[q], out->grid_cell[q] = c->hScene.gridCell[q], out->grid_cell_exp[q] = c->hScene.gridCellExp[q];
+        out->lo[q] = k.lo[q], out->hi[q] = k.hi[q];
+    }
+    return HR_OK;
+}
+int hr_scene_tree_read(hr_ctx *c, int32_t what, void *dst, uint64_t capacity)
+{
+    ENTER(c);
+    if (c->grp) FAIL(c, HR_ERR_INVALID, "tree readback: a context group is not supported");
+    if (!c->committed) FAIL(c, HR_ERR_INVALID, "scene not committed");
+    if (what < 0 || what >= HR_TREE_ARRAYS) FAIL(c, HR_ERR_INVALID, "tree readback: no such array");
+    const void *src[HR_TREE_ARRAYS];
+    uint64_t bytes[HR_TREE_ARRAYS];
+    treeArrays(c, src, bytes);
+    if (!dst) FAIL(c, HR_ERR_INVALID, "tree readback: null output");
+    if (capacity < bytes[what]) FAIL(c, HR_ERR_INVALID, "tree readback: the buffer is shorter than the array");
+    if (bytes[what] == 0) return HR_OK;
+    HIP_TRY(c, hipMemcpyAsync(dst, src[what], bytes[what], hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    return HR_OK;
+}
+
 // --------------------------------------------------------------------------------------- textures
 int hr_texture_create(hr_ctx *c, const hr_texture_desc *d, const void *pixels, hr_tex_id *out)
 {

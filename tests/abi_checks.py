@@ -73,15 +73,16 @@ def check_library_exports(header):
     assert f() == getattr(ffi, const) == want
 
 
-def check_struct_layout(tmp_path, header, struct, cname, version_macro):
-    """the header compiles as C, and gcc gives `cname` the size and the field offsets of the ctypes `struct`, which names it as its C type"""
+def check_struct_layout(tmp_path, header, struct, cname, version_macro, version=1):
+    """the header compiles as C with `version_macro` at `version`, and gcc gives `cname` the size and the field offsets of the ctypes `struct`,
+    which names it as its C type"""
     assert struct._cname_ == cname
     fields = [n for n, _ in struct._fields_]
     src = tmp_path / "layout.c"
     src.write_text(f'#include <stdio.h>\n#include <stddef.h>\n#include "{header}"\nint main(void) {{\n'
                    f'  printf("%zu", sizeof({cname}));\n'
                    + "".join(f'  printf(" %zu", offsetof({cname}, {f}));\n' for f in fields)
-                   + f"  return (int)({version_macro}) - 1;\n}}\n")
+                   + f"  return (int)({version_macro}) - {int(version)};\n}}\n")
     exe = tmp_path / "layout"
     subprocess.run(["gcc", "-Wall", "-Werror", "-I", INCLUDE, str(src), "-o", str(exe)], check=True, capture_output=True, text=True)
     out = subprocess.run([str(exe)], capture_output=True, text=True)

@@ -37,8 +37,8 @@ def test_binding_header_and_library_agree():
     abi_checks.check_no_version_moved()
     for fn in (lib.hr_exposure_api_version, lib.hr_tree_api_version, lib.hr_metric_api_version):
         fn.restype = ctypes.c_uint32
-    assert (lib.hr_exposure_api_version(), lib.hr_tree_api_version(), lib.hr_metric_api_version()) == (1, 1, 1)
-    assert (ffi.HR_EXPOSURE_API_VERSION, ffi.HR_TREE_API_VERSION, ffi.HR_METRIC_API_VERSION) == (1, 1, 1)
+    assert (lib.hr_exposure_api_version(), lib.hr_tree_api_version(), lib.hr_metric_api_version()) == (1, 2, 1)
+    assert (ffi.HR_EXPOSURE_API_VERSION, ffi.HR_TREE_API_VERSION, ffi.HR_METRIC_API_VERSION) == (1, 2, 1)
 
 
 def test_constants_match_the_header():

@@ -30,7 +30,7 @@ def test_binding_header_and_library_agree():
     assert ffi.FEATURES["metric"] == (ffi.METRIC_SYMBOLS, ffi.HR_METRIC_API_VERSION, "convergence metric")
     abi_checks.check_no_version_moved()
     lib.hr_exposure_api_version.restype = lib.hr_tree_api_version.restype = ctypes.c_uint32
-    assert (lib.hr_exposure_api_version(), lib.hr_tree_api_version()) == (ffi.HR_EXPOSURE_API_VERSION, ffi.HR_TREE_API_VERSION) == (1, 1)
+    assert (lib.hr_exposure_api_version(), lib.hr_tree_api_version()) == (ffi.HR_EXPOSURE_API_VERSION, ffi.HR_TREE_API_VERSION) == (1, 2)
 
 
 def test_constants_match_the_header():

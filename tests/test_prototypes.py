@@ -126,7 +126,7 @@ def walk():
         c("display_device", DEV), c("display_device", DEV, DP, RGBA32F), c("readback_progressive"), c("debug_trace", O, D),
         c("debug_trace", O, D, tmax=[1.0], skip_prim=[0], any_hit=True),
         # include/hrcore_tree.h, hrcore_aov.h
-        c("tree_info"), c("set_aovs", ffi.HR_AOV_SURFACE | ffi.HR_AOV_MOMENTS), c("aov_mask"), c("aov_plane", ffi.HR_AOV_PLANE_MOMENTS), c("aovs"),
+        c("tree_info"), c("tree_readback"), c("set_aovs", ffi.HR_AOV_SURFACE | ffi.HR_AOV_MOMENTS), c("aov_mask"), c("aov_plane", ffi.HR_AOV_PLANE_MOMENTS), c("aovs"),
         c("aov_to_device", 0, DEV), c("aov_to_device", 0, DEV, stream=DEV),
         # include/hrcore_denoise.h, hrcore_denoise_spatial.h
         c("denoise"), c("denoise", DN, with_passes=True), c("denoise_to_device", DEV), c("denoise_to_device", DEV, DN, DEV), c("denoise_display", DEV),
@@ -177,6 +177,7 @@ NOT_REACHED = {
     "ctx_create_group": "makes the group: it would need devices",
     "ctx_destroy": "close() does not call it for a null context",
     "motion_snapshot_readback": "motion_snapshot_triangles asks motion_info for the size first, and that call raises",
+    "scene_tree_read": "tree_readback asks scene_tree_layout for the sizes first, and that call raises",
     **{f"{feature}_default_params": "no Engine method: the feature's module calls it on the library" for feature in
        ("denoise", "denoise_spatial", "adaptive", "history", "exposure", "metric", "despeckle", "mesh", "deform", "motion")},
 }
